@@ -28,6 +28,12 @@ per-GPU shard is configs[4]'s 262144 transforms.  `--extras` additionally append
 headline (N = 8192 / 16384 / 32768) and SURVEY 8(f) rows (fused convolution, real-input packing) on 1 GiB each, same K / W,
 compact (not BASELINE configs, no CPU leg).
 
+Every workload's input is seeded and is restored after the device wake-up, so with the same arguments every run times the
+same W + K steps on the same data.  `--dump-outputs DIR` then writes, per measured workload, what its last timed step left
+in the in-place buffer (what a caller of that path receives) to DIR/<name>.npy -- <name> = the workload, the
+`roofline.configs` key, or extra_<workload>_n<N>_r<radix>_<precision> -- in float32 / float64, whole or as a fixed, seeded
+sample (dump_sample), under 64 MB in all: two builds run with the same arguments can be compared output for output.
+
 `roofline.achieved` = algorithmic bytes per launch (each element read once + written
 once) / average launch duration measured with HIP events on the launch stream inside this run.
 `cpu_baseline` = the reference's own CPU path (oracle/_ref, the real simpledsp headers; falls back
@@ -69,28 +75,60 @@ def parse_args():
     ap.add_argument("--extras", action="store_true", help="also measure the SURVEY 8(f) rows / neighbouring sizes, appended compactly as \"extras\"")
     ap.add_argument("--no-extras", action="store_true", help="(default since round 3; kept so that old command lines still parse)")
     ap.add_argument("--other-cpu-seconds", type=float, default=3.0, help="CPU leg of each other_configs entry")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of each measured workload left in its buffer to DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of large buffers; under 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
-# workloads: each returns (step_fn, units_per_step, algorithmic_bytes_per_unit, describe dict)
+# workloads: each returns (step_fn, units_per_step, algorithmic_bytes_per_unit, describe dict, metric, unit, dtype,
+# objects to keep alive, the in-place buffer a caller receives, restart_fn)
 
-def make_fft4096(sd, torch, dev, args):
-    # N = 1: configs[1] (65536 transforms, 2 GiB).  N > 1: configs[4] -- 2M transforms over 8 GPUs = 262144 (8 GiB) per
-    # GPU, the same shard at every N > 1 (weak scaling; per-transform throughput does not depend on the batch above ~10k)
-    batch = args.batch_per_gpu or (262144 if args.world > 1 else 65536)
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + dev.index)
-    x = torch.view_as_complex(torch.randn((batch, 4096, 2), generator=g, device=dev, dtype=torch.float32))
-    fwd = sd.FftPlan(4096, 4, sd.forward_fft, sd.F32, max_batch=batch, device=dev.index)
-    rev = sd.FftPlan(4096, 4, sd.reverse_fft, sd.F32, max_batch=batch, device=dev.index)
-    if args.variant >= 0:
-        fwd.set_variant(args.variant)
-        rev.set_variant(args.variant)
+def seeded_input(torch, shape, seed, dev, dtype):
+    """a buffer of standard normal samples from a seeded generator, and the function that refills it with the same values.
+    The wake-up of measure() runs for a fixed time, not a fixed number of steps, and every step works in place: measure()
+    refills the buffer after the wake-up so that the warm-up and timed steps of every run see the same inputs."""
+    g = torch.Generator(device=dev)
+    buf = torch.empty(shape, device=dev, dtype=dtype)
+
+    def refill():
+        torch.randn(shape, generator=g.manual_seed(seed), out=buf)
+
+    refill()
+    return buf, g, refill
+
+
+def alternating(fwd, rev, x, refill):
+    """step = forward / reverse in turn, in place; restart = seeded inputs again, next step forward"""
     state = {"i": 0}
 
     def step():
         (fwd if state["i"] % 2 == 0 else rev).exec(x)
         state["i"] += 1
+
+    def restart():
+        refill()
+        state["i"] = 0
+
+    return step, restart
+
+
+def make_fft4096(sd, torch, dev, args):
+    # N = 1: configs[1] (65536 transforms, 2 GiB).  N > 1: configs[4] -- 2M transforms over 8 GPUs = 262144 (8 GiB) per
+    # GPU, the same shard at every N > 1 (weak scaling; per-transform throughput does not depend on the batch above ~10k)
+    batch = args.batch_per_gpu or (262144 if args.world > 1 else 65536)
+    xr, _, refill = seeded_input(torch, (batch, 4096, 2), 0x5D5B + dev.index, dev, torch.float32)
+    x = torch.view_as_complex(xr)
+    fwd = sd.FftPlan(4096, 4, sd.forward_fft, sd.F32, max_batch=batch, device=dev.index)
+    rev = sd.FftPlan(4096, 4, sd.reverse_fft, sd.F32, max_batch=batch, device=dev.index)
+    if args.variant >= 0:
+        fwd.set_variant(args.variant)
+        rev.set_variant(args.variant)
+    step, restart = alternating(fwd, rev, x, refill)
 
     info = fwd.info
     which = "configs[1]" if batch == 65536 else "configs[4] shard (2M transforms / 8 GPUs)" if batch == 262144 else "configs[1] shape"
@@ -100,21 +138,18 @@ def make_fft4096(sd, torch, dev, args):
         "direction": "forward/reverse alternating (keeps the in-place data finite)",
         "kernel": info.kernel.decode(), "hbm_passes": info.hbm_passes,
     }
-    return step, batch, int(info.algorithmic_bytes), desc, "batched complex FFTs/sec (N=4096, radix-4, fp32)", "FFT/s", "f32", (fwd, rev, x)
+    return (step, batch, int(info.algorithmic_bytes), desc, "batched complex FFTs/sec (N=4096, radix-4, fp32)", "FFT/s", "f32",
+            (fwd, rev, x), x, restart)
 
 
 def make_fft1m(sd, torch, dev, args):
     batch = args.batch_per_gpu or 256
     n = 1 << 20
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + 1 + dev.index)
-    x = torch.view_as_complex(torch.randn((batch, n, 2), generator=g, device=dev, dtype=torch.float32))
+    xr, _, refill = seeded_input(torch, (batch, n, 2), 0x5D5B + 1 + dev.index, dev, torch.float32)
+    x = torch.view_as_complex(xr)
     fwd = sd.FftPlan(n, 2, sd.forward_fft, sd.F32, max_batch=batch, device=dev.index)
     rev = sd.FftPlan(n, 2, sd.reverse_fft, sd.F32, max_batch=batch, device=dev.index)
-    state = {"i": 0}
-
-    def step():
-        (fwd if state["i"] % 2 == 0 else rev).exec(x)
-        state["i"] += 1
+    step, restart = alternating(fwd, rev, x, refill)
 
     info = fwd.info
     desc = {
@@ -122,27 +157,23 @@ def make_fft1m(sd, torch, dev, args):
         "n": n, "radix": 2, "batch_per_gpu": batch, "kernel": info.kernel.decode(),
         "hbm_passes": info.hbm_passes,
     }
-    return step, batch, int(info.algorithmic_bytes), desc, "batched complex FFTs/sec (N=2^20, radix-2, fp32)", "FFT/s", "f32", (fwd, rev, x)
+    return (step, batch, int(info.algorithmic_bytes), desc, "batched complex FFTs/sec (N=2^20, radix-2, fp32)", "FFT/s", "f32",
+            (fwd, rev, x), x, restart)
 
 
 def make_fft(sd, torch, dev, args):
     """any size / radix / precision the library covers (not a BASELINE config): 1 GiB of transforms per GPU"""
     n, f64 = args.n, args.precision == "f64"
     batch = args.batch_per_gpu or max(1, (1 << (26 if f64 else 27)) // n)
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + 4 + dev.index)
-    x = torch.view_as_complex(torch.randn((batch, n, 2), generator=g, device=dev,
-                                          dtype=torch.float64 if f64 else torch.float32))
+    xr, _, refill = seeded_input(torch, (batch, n, 2), 0x5D5B + 4 + dev.index, dev, torch.float64 if f64 else torch.float32)
+    x = torch.view_as_complex(xr)
     prec = sd.F64 if f64 else sd.F32
     fwd = sd.FftPlan(n, args.radix, sd.forward_fft, prec, max_batch=batch, device=dev.index)
     rev = sd.FftPlan(n, args.radix, sd.reverse_fft, prec, max_batch=batch, device=dev.index)
     if args.variant >= 0:
         fwd.set_variant(args.variant)
         rev.set_variant(args.variant)
-    state = {"i": 0}
-
-    def step():
-        (fwd if state["i"] % 2 == 0 else rev).exec(x)
-        state["i"] += 1
+    step, restart = alternating(fwd, rev, x, refill)
 
     info = fwd.info
     desc = {
@@ -152,7 +183,7 @@ def make_fft(sd, torch, dev, args):
         "kernel": info.kernel.decode(), "hbm_passes": info.hbm_passes,
     }
     return (step, batch, int(info.algorithmic_bytes), desc,
-            f"batched complex FFTs/sec (N={n}, radix-{args.radix}, {args.precision})", "FFT/s", args.precision, (fwd, rev, x))
+            f"batched complex FFTs/sec (N={n}, radix-{args.radix}, {args.precision})", "FFT/s", args.precision, (fwd, rev, x), x, restart)
 
 
 def make_conv(sd, torch, dev, args):
@@ -161,8 +192,8 @@ def make_conv(sd, torch, dev, args):
     n, f64 = args.n, args.precision == "f64"
     batch = args.batch_per_gpu or max(1, (1 << (26 if f64 else 27)) // n)
     rdt = torch.float64 if f64 else torch.float32
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + 6 + dev.index)
-    x = torch.view_as_complex(torch.randn((batch, n, 2), generator=g, device=dev, dtype=rdt))
+    xr, g, refill = seeded_input(torch, (batch, n, 2), 0x5D5B + 6 + dev.index, dev, rdt)
+    x = torch.view_as_complex(xr)
     ph = torch.rand((n,), generator=g, device=dev, dtype=rdt) * 6.283185307179586
     h = torch.polar(torch.ones_like(ph), ph)
     plan = sd.FftPlan(n, args.radix, sd.forward_fft, sd.F64 if f64 else sd.F32, max_batch=batch, device=dev.index)
@@ -179,22 +210,17 @@ def make_conv(sd, torch, dev, args):
         "n": n, "radix": args.radix, "batch_per_gpu": batch, "kernel": "fused convolution of " + info.kernel.decode(), "hbm_passes": 1,
     }
     return (step, batch, int(info.algorithmic_bytes), desc, f"fast convolutions/sec (N={n}, radix-{args.radix}, {args.precision})",
-            "convolutions/s", args.precision, (plan, x, h))
+            "convolutions/s", args.precision, (plan, x, h), x, refill)
 
 
 def make_rfft(sd, torch, dev, args):
     """real-input packing, SURVEY 8(f)-3 (not a BASELINE config): 1 GiB of real samples, forward / inverse alternating"""
     n_real = args.n
     batch = args.batch_per_gpu or max(1, (1 << 28) // n_real)
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + 7 + dev.index)
-    x = torch.randn((batch, n_real), generator=g, device=dev)
+    x, _, refill = seeded_input(torch, (batch, n_real), 0x5D5B + 7 + dev.index, dev, torch.float32)
     fwd = sd.RfftPlan(n_real, args.radix, sd.forward_fft, max_batch=batch, device=dev.index)
     inv = sd.RfftPlan(n_real, args.radix, sd.reverse_fft, max_batch=batch, device=dev.index)
-    state = {"i": 0}
-
-    def step():
-        (fwd if state["i"] % 2 == 0 else inv).exec(x)
-        state["i"] += 1
+    step, restart = alternating(fwd, inv, x, refill)
 
     info = fwd.info
     desc = {
@@ -203,7 +229,7 @@ def make_rfft(sd, torch, dev, args):
         "n_real": n_real, "radix": args.radix, "batch_per_gpu": batch, "kernel": info.kernel.decode(), "hbm_passes": 1,
     }
     return (step, batch, int(info.algorithmic_bytes), desc, f"real-input FFTs/sec (n_real={n_real}, radix-{args.radix}, f32)", "FFT/s",
-            "f32", (fwd, inv, x))
+            "f32", (fwd, inv, x), x, restart)
 
 
 def make_fir(sd, torch, dev, args):
@@ -211,8 +237,7 @@ def make_fir(sd, torch, dev, args):
     f64 = args.precision == "f64"
     channels = args.batch_per_gpu or ((1 << 19) if f64 else (1 << 20))
     samples = 4096
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + 5 + dev.index)
-    x = torch.randn((channels, samples), generator=g, device=dev, dtype=torch.float64 if f64 else torch.float32)
+    x, _, refill = seeded_input(torch, (channels, samples), 0x5D5B + 5 + dev.index, dev, torch.float64 if f64 else torch.float32)
     bank = sd.fir_filter(args.taps, channels, sd.F64 if f64 else sd.F32, device=dev.index)
     bank.set_lp_coeff(10e3, 100e3)  # unit DC gain: repeated filtering stays bounded
     if args.variant >= 0:
@@ -228,15 +253,14 @@ def make_fir(sd, torch, dev, args):
         "taps": args.taps, "channels_per_gpu": channels, "samples": samples, "kernel": "sdsp_fir_kernel",
     }
     return (step, channels * samples, 16 if f64 else 8, desc, f"FIR samples/sec ({args.taps} taps)", "samples/s",
-            args.precision, (bank, x))
+            args.precision, (bank, x), x, refill)
 
 
 def make_iir(sd, torch, dev, args, f64=False, interleaved=False, lp_class=False, mixed=False):
     channels = args.batch_per_gpu or (1 << 20)
     samples = 4096
     dt = torch.float64 if f64 else torch.float32
-    g = torch.Generator(device=dev).manual_seed(0x5D5B + 2 + dev.index)
-    x = torch.randn((samples, channels) if interleaved else (channels, samples), generator=g, device=dev, dtype=dt)
+    x, _, refill = seeded_input(torch, (samples, channels) if interleaved else (channels, samples), 0x5D5B + 2 + dev.index, dev, dt)
     # casc_2o_iir<4> (testIIR.cpp:465-487) or the numerator-folded casc_2o_iir_lp<4> (:489-494)
     prec = sd.F64 if f64 else sd.F32_F64STATE if mixed else sd.F32
     bank = sd.casc_2o_iir(4, channels, prec, sd.IIR_LP if lp_class else sd.IIR_GENERIC, device=dev.index)
@@ -262,7 +286,8 @@ def make_iir(sd, torch, dev, args, f64=False, interleaved=False, lp_class=False,
     }
     unit_bytes = 16 if f64 else 8
     metric = "IIR samples/sec (4 cascaded biquads, LP" + (", casc_2o_iir_lp class)" if lp_class else ")")
-    return step, channels * samples, unit_bytes, desc, metric, "samples/s", "f64" if f64 else "f32+f64state" if mixed else "f32", (bank, x)
+    return (step, channels * samples, unit_bytes, desc, metric, "samples/s", "f64" if f64 else "f32+f64state" if mixed else "f32",
+            (bank, x), x, refill)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -389,11 +414,37 @@ WORKLOADS = {
 }
 
 
-def measure(name, sd, torch, dev, args, dist, steps, warmup):
+def dump_sample(t, budget: int):
+    """What a caller of the timed path receives, as float32 / float64 numpy (complex buffers get a trailing (re, im) axis):
+    the whole buffer when it fits in `budget` bytes, else a fixed, seeded sample -- rows of the leading dimension, and
+    columns of the rest flattened when one row alone is over the budget."""
+    import numpy as np
+    import torch
+    if t.numel() * t.element_size() > budget:
+        rows = t.shape[0]
+        t = t.reshape(rows, -1)
+        cols, elem = t.shape[1], t.element_size()
+        r = min(rows, max(1, budget // (cols * elem)))
+        c = min(cols, budget // (r * elem))
+        rng = np.random.default_rng(0x5D5B)
+        ri = torch.from_numpy(np.sort(rng.choice(rows, r, replace=False))).to(t.device)
+        ci = torch.from_numpy(np.sort(rng.choice(cols, c, replace=False))).to(t.device)
+        t = t.index_select(0, ri).index_select(1, ci)
+    return (torch.view_as_real(t) if t.is_complex() else t).cpu().numpy()
+
+
+# --dump-outputs: the headline's buffer gets 16 MiB, each other workload 1 MiB; at most 1 + 6 other configs + 24 extras
+# keeps the directory under 64 MB
+DUMP_HEAD_BYTES, DUMP_OTHER_BYTES = 16 << 20, 1 << 20
+
+
+def measure(name, sd, torch, dev, args, dist, steps, warmup, dump=None):
     """One workload: setup, wake-up, W untimed + exactly K timed steps (barrier + synchronize on both sides, max over
-    ranks), HIP events on the launch stream for the kernel time.  Returns the fields of one result object."""
+    ranks), HIP events on the launch stream for the kernel time.  Returns the fields of one result object.
+    dump = (file name, byte budget): rank 0 then writes dump_sample() of the buffer the last timed step left to
+    --dump-outputs DIR / file name."""
     from simpledsp_amd.dist import timed_steps
-    step, units, unit_bytes, desc, metric, unit, dtype, keep = WORKLOADS[name](sd, torch, dev, args)
+    step, units, unit_bytes, desc, metric, unit, dtype, keep, out, restart = WORKLOADS[name](sd, torch, dev, args)
 
     # Setup, not measurement: wake the device up.  The first ~20 back-to-back launches after idle run
     # up to 20 % slower (power/clock transient, profiles/r01_fft4096_summary.md); ~150 ms of untimed
@@ -403,6 +454,9 @@ def measure(name, sd, torch, dev, args, dist, steps, warmup):
         for _ in range(4):
             step()
         torch.cuda.synchronize(dev)
+    # the wake-up ran a number of steps that depends on the clock: start the W + K steps from the seeded inputs again
+    restart()
+    torch.cuda.synchronize(dev)
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     n_calls = {"i": 0}
@@ -417,6 +471,9 @@ def measure(name, sd, torch, dev, args, dist, steps, warmup):
 
     wall = timed_steps(timed_step, steps, warmup, lambda: torch.cuda.synchronize(dev), dist, dev)
     step_ms = ev0.elapsed_time(ev1) / max(1, steps)
+    if dump and args.rank == 0:
+        import numpy as np
+        np.save(Path(args.dump_outputs) / f"{dump[0]}.npy", dump_sample(out, dump[1]))
     # a step whose buffer exceeds the library's launch granularity is issued as several launches of the same kernel over
     # consecutive pieces (include/sdsp_hip.h: sdsp_hip_set_launch_piece_bytes); the library says how many
     # (sdsp_hip_fft_plan_launches), and for a single-kernel path the roofline is per launch: bytes and duration both divided
@@ -439,7 +496,7 @@ def measure(name, sd, torch, dev, args, dist, steps, warmup):
             "algorithmic_bytes_per_launch": units * unit_bytes / launches,
         },
     }
-    del keep, step
+    del keep, step, out, restart
     torch.cuda.empty_cache()
     return res
 
@@ -466,7 +523,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    args.world = world
+    args.world, args.rank = world, rank
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.gpus > 1 and world == 1:
         sys.exit("bench.py --gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
     if not torch.cuda.is_available():
@@ -482,15 +541,20 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=dev)
 
-    head = measure(args.workload, sd, torch, dev, args, dist, args.steps, args.warmup)
+    def dump(fname, budget):
+        return (fname, budget) if args.dump_outputs else None
+
+    head = measure(args.workload, sd, torch, dev, args, dist, args.steps, args.warmup, dump(args.workload, DUMP_HEAD_BYTES))
 
     # the other single-GPU BASELINE configs, same K / W, appended to the same line (N = 1, default workload only)
     others = []
+    keys = {"fft1m": "cfg3_fft1m", "iir": "cfg4_iir_f32", "iir64": "cfg4_iir_f64", "iir_mix": "cfg4_iir_mix",
+            "iir_lp": "cfg4_iir_lp", "fft4096": "cfg5_shard"}
     if world == 1 and args.workload == "fft4096" and not args.no_other_configs and not args.batch_per_gpu and args.variant < 0:
         plan = [("fft1m", 0), ("iir", 0), ("iir64", 0), ("iir_mix", 0), ("iir_lp", 0), ("fft4096", 262144)]
         for name, batch in plan:
             args.batch_per_gpu = batch
-            r = measure(name, sd, torch, dev, args, dist, args.steps, args.warmup)
+            r = measure(name, sd, torch, dev, args, dist, args.steps, args.warmup, dump(keys[name], DUMP_OTHER_BYTES))
             r["steps"], r["warmup"] = args.steps, args.warmup
             others.append((name, r))
         args.batch_per_gpu = 0
@@ -510,7 +574,7 @@ def main():
                                      # the register-pass families (2048- / 1024-point tiles): the reference's own test size and a small one
                                      ("fft", 64, 2, "f32"), ("fft", 1024, 2, "f32"), ("fft", 1024, 4, "f32"), ("fft", 64, 2, "f64"), ("fft", 1024, 2, "f64")):
             args.n, args.radix, args.precision = n, radix, prec
-            r = measure(name, sd, torch, dev, args, dist, args.steps, args.warmup)
+            r = measure(name, sd, torch, dev, args, dist, args.steps, args.warmup, dump(f"extra_{name}_n{n}_r{radix}_{prec}", DUMP_OTHER_BYTES))
             extras.append({"what": f"{name} n={n} radix={radix}" + (" f64" if prec == "f64" else ""), **compact(r)})
         args.n, args.radix, args.precision = keep_n, keep_radix, keep_prec
 
@@ -523,8 +587,6 @@ def main():
         }
         # the compact copy of every other BASELINE config, inside the object the driver's record keeps whole
         if others:
-            keys = {"fft1m": "cfg3_fft1m", "iir": "cfg4_iir_f32", "iir64": "cfg4_iir_f64", "iir_mix": "cfg4_iir_mix",
-                    "iir_lp": "cfg4_iir_lp", "fft4096": "cfg5_shard"}
             out["roofline"]["configs"] = {keys[name]: compact(r) for name, r in others}
         # the extra workloads (--workload fft / fir) are not BASELINE configs: no CPU leg for them
         if world == 1 and not args.no_cpu_baseline and args.workload not in ("fft", "fir", "conv", "rfft"):

@@ -14,6 +14,7 @@ Two back ends, both double precision on the host CPU:
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import subprocess
 from pathlib import Path
@@ -27,6 +28,12 @@ MAX_SECTIONS = 32
 
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
+
+
+def digest(a) -> str:
+    """sha256 of a complex array's exact bytes (little-endian complex128, C order): a bit-for-bit fingerprint that stands
+    in for stored outputs too large to keep under tests/golden/"""
+    return hashlib.sha256(np.ascontiguousarray(a, dtype="<c16").tobytes()).hexdigest()
 
 
 def build(ref: bool = True) -> None:

@@ -7,6 +7,7 @@ TEST INFRASTRUCTURE ONLY.  Run in the build container, where /root/reference exi
 
 Writes data only (inputs + the reference's outputs):
   tests/golden/fft_golden.npz      inputs/outputs of sdsp::fft_radix2 / fft_radix4 (fft.h:258-360)
+  tests/golden/fft_golden_f64.json the same on full double-precision random inputs, as sha256 digests
   tests/golden/iir_golden.npz      outputs/coefficients/state of sdsp::casc_2o_iir* (casc_2o_iir.h)
   tests/golden/impulse_response/   the 9 Octave CSV fixtures the reference's own tests read
                                    (test_data/impulse_response/*.csv, testIIR.cpp:34) -- data files
@@ -14,6 +15,7 @@ The input recipes restate the reference's test inputs (testFFT.cpp / testIIR.cpp
 """
 from __future__ import annotations
 
+import json
 import shutil
 import sys
 from pathlib import Path
@@ -22,11 +24,12 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-from oracle import Reference  # noqa: E402
+from oracle import Reference, digest  # noqa: E402
 
 GOLD = ROOT / "tests" / "golden"
 REF_CSV = Path("/root/reference/test_data/impulse_response")
 SEED = 0x5D5B
+F64_SEED = 7  # the inputs of tests/test_oracle_fft.py::test_oracle_live_against_reference_build
 
 
 def f32_representable(rng, shape):
@@ -87,6 +90,21 @@ def gen_fft(ref: Reference) -> dict:
         g[f"swap{N}_base2"] = ref.swap_lookup(N, 2)
         g[f"swap{N}_base4"] = ref.swap_lookup(N, 4)
     g["swap128_base2"] = ref.swap_lookup(128, 2)
+    return g
+
+
+def gen_fft_f64(ref: Reference) -> dict:
+    """full double-precision random inputs (not fp32-representable, default_rng(F64_SEED)), two transforms at every size
+    the shim instantiates: digests of the inputs and of the reference's outputs.  The test regenerates the inputs from the
+    seed; the outputs (~1 MB of incompressible doubles) are kept only as digests."""
+    g: dict = {}
+    rng = np.random.default_rng(F64_SEED)
+    for N in Reference.SIZES:
+        x = rng.standard_normal((2, N)) + 1j * rng.standard_normal((2, N))
+        g[f"n{N}__in"] = digest(x)
+        for r in ((2, 4) if ref.is_power_of_4(N) else (2,)):
+            for rev in (False, True):
+                g[f"n{N}__r{r}_{'rev' if rev else 'fwd'}"] = digest(ref.fft(x, r, rev))
     return g
 
 
@@ -180,6 +198,7 @@ def main():
     ref = Reference()
     GOLD.mkdir(parents=True, exist_ok=True)
     np.savez_compressed(GOLD / "fft_golden.npz", **gen_fft(ref))
+    (GOLD / "fft_golden_f64.json").write_text(json.dumps(gen_fft_f64(ref), indent=1) + "\n")
     np.savez_compressed(GOLD / "iir_golden.npz", **gen_iir(ref))
     dst = GOLD / "impulse_response"
     dst.mkdir(exist_ok=True)

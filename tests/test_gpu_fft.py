@@ -1050,3 +1050,27 @@ def test_bench_under_torch_distributed_run_on_one_gpu(sd, torch_cuda):
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["scaling"] == "weak"
     assert out["config"]["batch_per_gpu"] == 65536 and out["roofline"]["launches_per_step"] == 2
     assert 0.5 < out["roofline"]["frac"] < 0.9, out["roofline"]
+
+
+def test_bench_dump_outputs_repeat_and_hold_the_last_step(sd, torch_cuda, tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same arrays, and they are what the last timed step
+    left in the buffer -- W + K = 4 alternating steps from the seeded input bring it back to that input (two round trips)"""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    torch = torch_cuda
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", "fft", "--n", "1024", "--radix", "2", "--batch-per-gpu", "1024",
+               "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout)["steps"] == 3
+        assert sorted(p.name for p in (tmp_path / run).iterdir()) == ["fft.npy"]
+        dumps.append(np.load(tmp_path / run / "fft.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1024, 1024, 2)
+    assert np.array_equal(dumps[0], dumps[1])
+    g = torch.Generator(device="cuda:0").manual_seed(0x5D5B + 4)  # bench.make_fft's seed on device 0
+    x0 = torch.randn((1024, 1024, 2), generator=g, device="cuda:0").cpu().numpy()
+    assert np.abs(dumps[0] - x0).max() / np.abs(x0).max() < 1e-5
