@@ -341,17 +341,39 @@ int ensure_workspace(sdsp_hip_fft_plan *p)
 // sdsp_hip_fft_exec at the start of a call (the per-launch abort flag beside the tickets is re-zeroed for every launch)
 void *fft1m_sticky(const sdsp_hip_fft_plan *p) { return reinterpret_cast<char *>(p->sync) + p->sticky_off; }
 
-// chunk sizes of the multi-pass schedules (shared by exec and the launch count)
-uint64_t fft1m_chunk(const sdsp_hip_fft_plan *p) { return std::max<uint64_t>(1, std::min<uint64_t>(32, p->ws_batch)); }
-uint64_t fft2p_chunk(const sdsp_hip_fft_plan *p) // an intermediate of at most 256 MiB per chunk
+// ------------------------------------------------------------------------------------------------------------------
+// The optional thread-twiddle tables.  Each predicate reads the plan's shape only (n, radix, precision, real_mode, allow_mix):
+// plan creation uploads a table where its predicate holds, and select_kernel / select_conv test the same predicate where a kernel
+// reads the table, so a plan holds a table iff some variant of its exec or convolve can run a kernel that reads it.
+// tuned N = 4096 kernels of fft4096.hip, either radix, and their fused convolution
+bool uses_twt4096(const sdsp_hip_fft_plan *p) { return p->precision == SDSP_HIP_F32 && !p->real_mode && p->n == 4096; }
+// register-pass families (fft_reg.hip, fft_reg64.hip) and fft_wave.hip's N = 1024 kernels; not the f32 N = 4096 radix-4 complex plan
+// (fft4096.hip's kernels, or the coverage kernel)
+bool uses_twt_reg(const sdsp_hip_fft_plan *p)
 {
-    const uint64_t cap = 1ull << 28; // the Infinity Cache: 37 % at 256 MiB, 35 % at 128 / 192, 33 - 34 % at 288 MiB and beyond (profiles/r03_fft2p_chunk_lab.txt)
-    return std::max<uint64_t>(1, std::min<uint64_t>(p->ws_batch, cap / ((uint64_t)p->n * esize(p->precision))));
+    if (p->precision == SDSP_HIP_F64)
+        return fft_reg64_supports(p->n, p->radix);
+    return fft_reg_supports(p->n, p->radix) && !(uses_twt4096(p) && p->radix == 4);
 }
+// registers-resident kernels (fft_big.hip, fft_big64.hip): the transform, its fused convolution, the REAL forms
+bool uses_twt_big(const sdsp_hip_fft_plan *p)
+{
+    if (p->precision == SDSP_HIP_F64)
+        return p->real_mode ? fft_big64_real_supports(p->n, p->radix) : fft_big64_supports(p->n, p->radix);
+    return p->real_mode ? fft_big_real_supports(p->n, p->radix) : fft_big_conv_supports(p->n, p->radix);
+}
+// fft_wave.hip's N = 256 / 512 / 2048 kernels (real-input plans: n <= 512)
+bool uses_twt_wave(const sdsp_hip_fft_plan *p)
+{
+    return p->precision == SDSP_HIP_F32 && fft_wave2_supports(p->n, p->radix) && (!p->real_mode || p->n <= 512);
+}
+// fft_mix.hip: the sub-transforms' table and the leading stage's twiddles
+bool uses_mix(const sdsp_hip_fft_plan *p) { return p->precision == SDSP_HIP_F32 && !p->real_mode && p->allow_mix && fft_mix_supports(p->n); }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The ONE dispatch table: which kernel serves (plan, variant).  sdsp_hip_fft_exec, sdsp_hip_fft_plan_get_info and
-// sdsp_hip_fft_plan_launches all go through select_kernel(), so what the plan reports is what runs, by construction.
+// The ONE dispatch table: which kernel serves (plan, variant), with which launcher and which table.  sdsp_hip_fft_exec,
+// sdsp_hip_fft_plan_get_info and sdsp_hip_fft_plan_launches go through select_kernel(), sdsp_hip_fft_convolve through
+// select_conv() beside it, so what the plan reports is what runs, by construction.
 enum fft_kernel_id {
     K_NOOP = 0,
     K_FFT4096_R4,    // fft4096.hip: the headline kernel (cfg 2 / 5)
@@ -376,6 +398,9 @@ enum fft_kernel_id {
     K_UNSUPPORTED,   // no kernel serves this (plan, variant)
 };
 
+using reg_launcher = int (*)(const fft_reg_args &, void *);
+using plan_table = void *sdsp_hip_fft_plan::*;
+
 struct fft_kernel_sel {
     fft_kernel_id id;
     const char *name;  // as rocprofv3 prints the dominant kernel(s)
@@ -383,53 +408,59 @@ struct fft_kernel_sel {
     int stage_radix;   // butterflies that run: 2, 4, or SDSP_HIP_STAGES_2_THEN_4
     bool workspace;    // needs the plan-owned workspace
     bool pieces;       // one launch per batch, issued in launch pieces (sdsp_hip_set_launch_piece_bytes)
+    reg_launcher launch = nullptr; // kernels launched with fft_reg_args (launch_reg)
+    plan_table table = nullptr;    // the optional table the kernel reads (its `tw`)
+    bool nontemporal = true;       // fft_reg_args.nontemporal
+    bool conv = false;             // select_conv: one launch computes the whole convolution ...
+    int variant = 0;               // ... or else the variant of the three-launch composition's forward transform
 };
 
 fft_kernel_sel select_kernel(const sdsp_hip_fft_plan *p, int variant)
 {
+    using P = sdsp_hip_fft_plan;
     const bool f32 = p->precision == SDSP_HIP_F32;
     // launch pieces: kernels with many short workgroups (N <= 8192); see fft_exec_pieces
     const bool pc = (p->path == PATH_FFT4096 || p->path == PATH_REG || p->path == PATH_TILE) && p->n <= 8192;
     if (p->path == PATH_NOOP)
         return { K_NOOP, "none", 0, p->radix, false, false };
     if (p->path == PATH_FFT4096 && variant < fft4096_num_variants())
-        return { K_FFT4096_R4, "sdsp_fft4096_r4_f32", 1, 4, false, pc };
+        return { K_FFT4096_R4, "sdsp_fft4096_r4_f32", 1, 4, false, pc, nullptr, &P::twt };
     if (p->path == PATH_REG && f32 && variant == 0 && p->n == 4096 && p->radix == 2 && !p->real_mode)
-        return { K_FFT4096_R2, "sdsp_fft4096_r2_f32", 1, 2, false, pc };
+        return { K_FFT4096_R2, "sdsp_fft4096_r2_f32", 1, 2, false, pc, nullptr, &P::twt };
     // N = 8192 / 16384 f32, either stage type: one leading radix-2 / radix-4 stage + the tuned N = 4096 radix-4 machinery
-    const bool mix_size = p->path == PATH_REG && f32 && !p->real_mode && p->tw_lead;
+    const bool mix_size = p->path == PATH_REG && uses_mix(p);
     const int mix_variant = big_is_default(p->n, p->radix) ? 1 : 0;
     if (mix_size && variant == mix_variant)
-        return { K_MIX, "sdsp_fft_mix_f32", 1, p->n == 8192 ? SDSP_HIP_STAGES_2_THEN_4 : 4, false, pc };
+        return { K_MIX, "sdsp_fft_mix_f32", 1, p->n == 8192 ? SDSP_HIP_STAGES_2_THEN_4 : 4, false, pc, nullptr, &P::twt_mix };
     // N = 32768 (variant 0) and N = 8192 / 16384 (variant 0 or 1, see big_is_default), f32: registers-resident kernel
     if ((p->path == PATH_REG || p->path == PATH_FOUR_STEP) && f32 && variant == (mix_size ? 1 - mix_variant : 0) && !p->real_mode &&
         fft_big_supports(p->n, p->radix))
-        return { K_BIG, "sdsp_fft_big_kernel", 1, big_r4_form(p->n, p->radix) ? 4 : 2, false, pc };
+        return { K_BIG, "sdsp_fft_big_kernel", 1, big_r4_form(p->n, p->radix) ? 4 : 2, false, pc, launch_fft_big_f32, &P::twt_big };
     // real-input plans of n_real = 4096 .. 65536: split / merge inside the registers-resident kernel; variants 1 / 2 keep
     // the register-pass family's MODE 1 / 2
-    if (p->path == PATH_REG && f32 && variant == 0 && p->real_mode && p->twt_big && fft_big_real_supports(p->n, p->radix))
-        return { K_BIG_REAL, "sdsp_fft_big_kernel", 1, big_r4_form(p->n, p->radix) ? 4 : 2, false, pc };
+    if (p->path == PATH_REG && f32 && variant == 0 && p->real_mode && uses_twt_big(p))
+        return { K_BIG_REAL, "sdsp_fft_big_kernel", 1, big_r4_form(p->n, p->radix) ? 4 : 2, false, pc, launch_fft_big_f32, &P::twt_big };
     // double precision, N = 4096 / 8192 / 16384: the registers-resident kernel in double (fft_big64.hip) -- radix-2 stages, or, for
     // radix-4 plans of N = 4096 / 16384, genuine radix-4 stages (its R4 form).
     // The default of all three sizes: 73.4 / 74.5 / 59.5 % of HBM peak against 67.5 % (N = 4096, fft_reg64.hip), 51.4 % (N = 8192:
     // the whole tile in LDS) and 24.2 % (N = 16384: three streaming passes) in one call (tools/sweep_sizes64.py, round 3);
     // what served a size before is its variant 1
-    const bool big64 = !f32 && !p->real_mode && p->twt_big && fft_big64_supports(p->n, p->radix);
+    const bool big64 = !f32 && !p->real_mode && uses_twt_big(p);
     if (big64 && variant == big64_variant(p->n))
-        return { K_BIG64, "sdsp_fft_big_f64_kernel", 1, p->radix == 4 ? 4 : 2, false, pc && p->n <= 4096 };
+        return { K_BIG64, "sdsp_fft_big_f64_kernel", 1, p->radix == 4 ? 4 : 2, false, pc && p->n <= 4096, launch_fft_big_f64, &P::twt_big };
     // real-input plans in double of n_real = 8192 / 16384 / 32768 (radix 2): split / merge around the same transform (its REAL form);
     // variant 1 keeps the register-pass family's MODE 1 / 2 (n_real <= 16384)
-    const bool big64_real = !f32 && p->real_mode && p->twt_big && fft_big64_real_supports(p->n, p->radix);
+    const bool big64_real = !f32 && p->real_mode && uses_twt_big(p);
     if (big64_real && variant == 0)
-        return { K_BIG64_REAL, "sdsp_fft_big_f64_real_kernel", 1, 2, false, pc && p->n <= 4096 };
+        return { K_BIG64_REAL, "sdsp_fft_big_f64_real_kernel", 1, 2, false, pc && p->n <= 4096, launch_fft_big_f64, &P::twt_big };
     if (p->path == PATH_REG && !f32 && fft_reg64_supports(p->n, p->radix)) {
         if ((big64 && big64_variant(p->n) == 0) || big64_real) // the kernel that was the default becomes variant 1
             variant = variant == 1 ? 0 : variant;
         const bool wave64 = !p->real_mode && fft_wave_supports(p->n, p->radix);
         if (variant == 1 && wave64) // N = 1024 alternate: same bits; measured 71.4-72.1 % against 71.7-72.6 %: no gain in double
-            return { K_WAVE64, "sdsp_fft1024_wave", 1, p->radix, false, pc };
+            return { K_WAVE64, "sdsp_fft1024_wave", 1, p->radix, false, pc, launch_fft_wave_f64, &P::twt_reg };
         if (variant == 0)
-            return { K_REG64, "sdsp_fft_reg_f64_kernel", 1, p->radix, false, pc };
+            return { K_REG64, "sdsp_fft_reg_f64_kernel", 1, p->radix, false, pc, launch_fft_reg_f64, &P::twt_reg };
     }
     if (p->path == PATH_REG && f32 && variant < 3) {
         // Complex plans: the register-pass family (fft_reg.hip) at every N <= 2048 since its tiles are 2048 points (eight 128-thread
@@ -440,11 +471,12 @@ fft_kernel_sel select_kernel(const sdsp_hip_fft_plan *p, int variant)
         // leads at n_real = 512 (74.7 against 71.8 %; radix 4: 75.5 / 71.0) and 2048 (70.5 / 67.2), the one-wave kernel keeps n_real = 1024
         // (70.8 / 69.8) -- tools/rfft_probe.py, one call each; n_real = 4096 .. 65536 radix 2 were taken by K_BIG_REAL above
         const int wave_variant = (p->real_mode && p->n == 512) ? 0 : 2;
+        const bool nt = variant != 1 || uses_mix(p); // variant 1: default cache policy (N < 8192)
         if (variant == wave_variant && fft_wave_supports(p->n, p->radix) && (!p->real_mode || p->radix == 2))
-            return { K_WAVE1024, "sdsp_fft1024_wave", 1, p->radix, false, pc };
-        if (variant == wave_variant && p->twt_wave && (p->real_mode ? p->n <= 512 : p->n != 512))
-            return { K_WAVE2, "sdsp_fft_wave_f32", 1, p->radix, false, pc };
-        return { K_REG32, "sdsp_fft_reg_kernel", 1, p->radix, false, pc };
+            return { K_WAVE1024, "sdsp_fft1024_wave", 1, p->radix, false, pc, launch_fft_wave_f32, &P::twt_reg, nt };
+        if (variant == wave_variant && uses_twt_wave(p) && (p->real_mode || p->n != 512))
+            return { K_WAVE2, "sdsp_fft_wave_f32", 1, p->radix, false, pc, launch_fft_wave2_f32, &P::twt_wave, nt };
+        return { K_REG32, "sdsp_fft_reg_kernel", 1, p->radix, false, pc, launch_fft_reg_f32, &P::twt_reg, nt };
     }
     if (p->real_mode)
         return { K_UNSUPPORTED, "none", 0, p->radix, false, false };
@@ -479,23 +511,248 @@ fft_kernel_sel select_kernel(const sdsp_hip_fft_plan *p, int variant)
     return { K_FOUR_STEP, "sdsp_fft_tile_kernel", 2, p->radix, true, false };
 }
 
+// The convolution y = IFFT(FFT(x) .* h) of a forward complex plan (sdsp_hip_fft_convolve) with kernel variant `variant`: ONE fused
+// launch (`conv`: both transforms and the multiply; launch_reg passes real_mode 3 and h in tw2), or else the three-launch composition --
+// the forward transform of `variant` (the result's), the multiply (riding on its pass 2 where that is K_2PASS / K_2PASS_FUSED: four
+// passes over HBM instead of five), the partner plan's reverse transform.  Either form runs in launch pieces where the plan is a
+// single-pass one of N <= 8192.
+fft_kernel_sel select_conv(const sdsp_hip_fft_plan *p, int variant)
+{
+    using P = sdsp_hip_fft_plan;
+    const bool f32 = p->precision == SDSP_HIP_F32, reg = p->path == PATH_REG, big = reg || p->path == PATH_FOUR_STEP;
+    const bool pc = (p->path == PATH_FFT4096 || reg || p->path == PATH_TILE) && p->n <= 8192;
+    auto fused = [&](fft_kernel_id id, const char *name, reg_launcher launch, plan_table table) {
+        return fft_kernel_sel{ id, name, 1, p->radix, false, pc, launch, table, true, true };
+    };
+    if (p->path == PATH_FFT4096 && variant == 0)
+        return fused(K_FFT4096_R4, "sdsp_fft4096_conv_f32", nullptr, &P::twt);
+    // N = 2048 .. 32768 radix-2 stages, N = 16384 radix-4 stages: both transforms and the multiply in the registers-resident kernel
+    // (fft_big.hip)
+    if (big && f32 && variant == 0 && uses_twt_big(p))
+        return fused(K_BIG, "sdsp_fft_big_kernel", launch_fft_big_f32, &P::twt_big);
+    // variant 0: the fused kernel of the size; variant 2: the register-pass family's fused MODE 3 where a one-wave kernel is the
+    // default (A/B and cross-check); any other variant: three launches
+    if (reg && f32 && variant == 0 && fft_wave_supports(p->n, p->radix)) // N = 1024: both transforms in one wave's registers
+        return fused(K_WAVE1024, "sdsp_fft1024_wave", launch_fft_wave_f32, &P::twt_reg);
+    // N = 256 / 512 radix 2 (N = 2048 radix 2 was taken by the fft_big.hip form above: 65-69 % against 52 %)
+    if (reg && f32 && variant == 0 && uses_twt_wave(p))
+        return fused(K_WAVE2, "sdsp_fft_wave_f32", launch_fft_wave2_f32, &P::twt_wave);
+    if (reg && f32 && (variant == 0 || variant == 2))
+        return fused(K_REG32, "sdsp_fft_reg_kernel", launch_fft_reg_f32, &P::twt_reg);
+    // double, N = 4096 / 8192 / 16384 radix-2 plans: fft_big64.hip's convolution form; variant 2: what served N <= 8192 before (the
+    // register-pass family's fused MODE 3)
+    if (big && !f32 && variant == 0 && uses_twt_big(p) && fft_big64_conv_supports(p->n, p->radix))
+        return fused(K_BIG64, "sdsp_fft_big_f64_kernel", launch_fft_big_f64, &P::twt_big);
+    if (reg && !f32 && (variant == 0 || variant == 2)) // f64, N = 16 .. 8192
+        return fused(K_REG64, "sdsp_fft_reg_f64_kernel", launch_fft_reg_f64, &P::twt_reg);
+    // PATH_FFT4096 with variant != 0 selects the three launches for cross-checking: its transforms run variant 0.  N = 2^20 f32 takes
+    // the generic persistent kernel (its variant 2) for the forward half, which can carry the multiply
+    int v = p->path == PATH_FFT4096 ? 0 : variant;
+    if (p->path == PATH_FFT1M && v == 0 && select_kernel(p, 2).id == K_2PASS_FUSED)
+        v = 2;
+    fft_kernel_sel s = select_kernel(p, v);
+    s.pieces = pc;
+    s.variant = v;
+    return s;
+}
+
+// a kernel is never handed a null table: a predicate that disagrees with what plan creation uploaded is a host error
+int check_table(const sdsp_hip_fft_plan *p, const fft_kernel_sel &sel)
+{
+    if (sel.table && !(p->*sel.table))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, std::string(sel.name) + ": the plan holds no table for this kernel");
+    return SDSP_HIP_OK;
+}
+
+// every kernel launched with fft_reg_args: the transforms, and with `h` the fused convolutions (real_mode 3, h in tw2)
+int launch_reg(const sdsp_hip_fft_plan *p, const fft_kernel_sel &sel, void *data, uint64_t batch, hipStream_t stream,
+               const void *h = nullptr)
+{
+    const bool f64 = p->precision == SDSP_HIP_F64;
+    fft_reg_args a;
+    a.data = data;
+    a.tw = p->*sel.table;
+    a.n = p->n;
+    a.radix = p->radix;
+    a.batch = batch;
+    a.scale = f64 ? 1.0f : (float)(1.0 / p->n); // the f64 kernels scale by scale_d
+    a.scale_d = f64 ? 1.0 / p->n : 1.0;
+    a.reverse = p->direction == SDSP_HIP_REVERSE;
+    a.nontemporal = sel.nontemporal;
+    a.real_mode = h ? 3 : p->real_mode;
+    a.tw2 = h ? h : p->real_mode ? p->tw2 : nullptr; // real-input plans: W_2n (a complex four-step plan's tw2 is W_n2)
+    return sel.launch(a, stream);
+}
+
+// transforms one step of a multi-pass schedule covers -- a chunk of two launches, one persistent launch, one workspace slice
+// (shared by exec and the launch count)
+uint64_t fft_step_units(const sdsp_hip_fft_plan *p, fft_kernel_id id)
+{
+    switch (id) {
+    case K_FFT1M_CHUNKED: return std::max<uint64_t>(1, std::min<uint64_t>(32, p->ws_batch));
+    case K_FFT1M_FUSED: return p->sync_count;
+    case K_2PASS: { // an intermediate of at most 256 MiB per chunk
+        const uint64_t cap = 1ull << 28; // the Infinity Cache: 37 % at 256 MiB, 35 % at 128 / 192, 33 - 34 % at 288 MiB and beyond (profiles/r03_fft2p_chunk_lab.txt)
+        return std::max<uint64_t>(1, std::min<uint64_t>(p->ws_batch, cap / ((uint64_t)p->n * esize(p->precision))));
+    }
+    case K_2PASS_FUSED: return p->path == PATH_FFT1M ? p->sync_count : p->sync_count * p->f2_unit; // N = 2^20: unit = one transform
+    default: return p->ws_batch; // K_MID, K_FOUR_STEP
+    }
+}
+
+int fft_exec_device(sdsp_hip_fft_plan *p, void *data, uint64_t batch, hipStream_t stream, int variant, const void *hmul = nullptr);
+
+// one step of the multi-pass kernel `id` over `nb` transforms at `d`
+int fft_exec_step(sdsp_hip_fft_plan *p, fft_kernel_id id, char *d, uint64_t nb, hipStream_t stream, const void *hmul)
+{
+    const int rev = p->direction == SDSP_HIP_REVERSE;
+    const float scale = (float)(1.0 / p->n);
+    switch (id) {
+    case K_FFT1M_CHUNKED: { // two launches per chunk of <= 32 transforms (round 1's schedule; also what plans with a small workspace run)
+        fft1m_args a;
+        a.data = d;
+        a.workspace = p->workspace;
+        a.tw_n = p->tw;
+        a.tw_1024 = p->tw1;
+        a.count = nb;
+        a.scale = scale;
+        a.reverse = rev;
+        if (int rc = launch_fft1m_pass(a, 1, stream))
+            return rc;
+        return launch_fft1m_pass(a, 2, stream);
+    }
+    case K_FFT1M_FUSED: { // ONE persistent launch (fft1m_kernels.h): eight ticket queues, per queue a ring of three intermediates,
+                          // pass 2 of a queue's transform one ticket step behind its pass 1
+        fft1m_fused_args a;
+        a.data = d;
+        a.workspace = p->workspace;
+        a.tw_1024 = p->tw1;
+        a.sync = p->sync;
+        a.sticky = fft1m_sticky(p);
+        a.spin_limit = p->wait_limit;
+        a.count = nb;
+        // a ring of 4 with pass 2 two steps behind measured 42.0-42.2 %, 3 / one step 41.4-41.6 % (profiles/r02_fft1m_lab.md)
+        a.ring = p->ws_batch >= 4 * kFft1mQueues ? 4 : (uint32_t)kFft1mRing;
+        a.lag = a.ring - 2;
+        a.queues = (uint32_t)kFft1mQueues;
+        a.scale = scale;
+        a.reverse = rev;
+        return launch_fft1m_fused(a, stream);
+    }
+    case K_2PASS_FUSED: { // the two-pass sizes in one persistent launch per kFused2pUnitsPerLaunch units
+        const bool m1 = p->path == PATH_FFT1M; // unit = one transform, the counters of the dedicated kernel
+        fft_2pass_fused_args a;
+        a.data = d;
+        a.workspace = p->workspace;
+        a.tw_1024 = m1 ? p->tw1 : p->tw1024; // N = 2^20: n1 = 1024, so W_n1 is that table
+        a.sync = p->sync;
+        a.sticky = fft1m_sticky(p);
+        a.spin_limit = p->wait_limit;
+        a.count = nb;
+        a.n = p->n;
+        a.unit = m1 ? 1 : p->f2_unit;
+        a.ring = m1 ? 4 : p->f2_ring;
+        a.lag = m1 ? 2 : p->f2_lag;
+        a.queues = m1 ? (uint32_t)kFft1mQueues : p->f2_queues;
+        a.scale = scale;
+        a.scale_d = 1.0 / p->n;
+        a.reverse = rev;
+        a.hmul = hmul;
+        return launch_fft_2pass_fused(p->precision, a, stream);
+    }
+    case K_2PASS: { // N = 2^16 .. 2^19, f32: two passes over HBM (fft_2pass.hip), in chunks whose intermediate is at most 256 MiB
+        fft_2pass_args a;
+        a.data = d;
+        a.workspace = p->workspace;
+        a.tw_1024 = p->tw1024;
+        a.n = p->n;
+        a.count = nb;
+        a.scale = scale;
+        a.scale_d = 1.0 / p->n;
+        a.reverse = rev;
+        a.hmul = hmul;
+        return launch_fft_2pass(p->precision, a, stream);
+    }
+    case K_MID: { // three streaming passes, N = 16 x N2 with the rows on a tuned single-pass kernel: f32 N = 2^21 .. 2^23, f64
+                  // N = 2^14 .. 2^21, and variant 1 of the f32 sizes above
+        const uint32_t n2 = p->n / 16;
+        if (int rc = launch_fft_mid_cols(p->precision, d, p->workspace, p->tw1024, n2, nb, rev, stream))
+            return rc;
+        if (int rc = fft_exec_device(p->mid_rows, p->workspace, nb * 16, stream, p->mid_rows->variant))
+            return rc;
+        return launch_fft_mid_untwist(p->precision, p->workspace, d, n2, nb, stream);
+    }
+    default: break; // K_FOUR_STEP
+    }
+    // four-step: N = n1 x n2 viewed as a row-major [n1][n2] matrix (index n = n2_count*i1 + i2).
+    //   pass 1: length-n1 transforms down the columns, times W_N^(i2*k1), data -> workspace
+    //   pass 2: length-n2 transforms along the rows, written transposed, workspace -> data
+    const uint64_t N = (uint64_t)p->n1 * p->n2;
+    fft_tile_args a{};
+    a.in = d;
+    a.out = p->workspace;
+    a.tw = p->tw1;
+    a.tw_big = p->tw;
+    a.n = p->n1;
+    a.log2n = sdsp_hip_log2(p->n1);
+    a.cols = p->cols1;
+    a.pitch = p->pitch1;
+    a.tiles_per_group = p->n2 / p->cols1;
+    a.total_cols = nb * p->n2;
+    a.group_stride = N;
+    a.in_tile_step = a.out_tile_step = p->cols1;
+    a.in_si = a.out_sk = p->n2;
+    a.in_sc = a.out_sc = 1;
+    a.in_c_fast = a.out_c_fast = 1;
+    a.reverse = rev;
+    a.apply_scale = 0;
+    a.scale = 1.0f;
+    a.scale_d = 1.0;
+    if (int rc = launch_fft_tile(p->precision, p->radix, a, nb * a.tiles_per_group, stream))
+        return rc;
+
+    fft_tile_args c{};
+    c.in = p->workspace;
+    c.out = d;
+    c.tw = p->tw2;
+    c.tw_big = nullptr;
+    c.n = p->n2;
+    c.log2n = sdsp_hip_log2(p->n2);
+    c.cols = p->cols2;
+    c.pitch = p->pitch2;
+    c.tiles_per_group = p->n1 / p->cols2;
+    c.total_cols = nb * p->n1;
+    c.group_stride = N;
+    c.in_tile_step = (uint64_t)p->cols2 * p->n2;
+    c.out_tile_step = p->cols2;
+    c.in_si = 1;
+    c.in_sc = p->n2;
+    c.in_c_fast = 0;
+    c.out_sk = p->n1;
+    c.out_sc = 1;
+    c.out_c_fast = 1;
+    c.reverse = rev;
+    c.apply_scale = rev;
+    c.scale = (float)(1.0 / (double)N);
+    c.scale_d = 1.0 / (double)N;
+    return launch_fft_tile(p->precision, p->radix, c, nb * c.tiles_per_group, stream);
+}
+
 // `variant`: the kernel variant to run (normally the plan's; the convolution path overrides it without touching the plan)
 // hmul (the two-pass kernels, forward plans): every output leaves multiplied by hmul[k] -- the fused convolution's forward half
-int fft_exec_device(sdsp_hip_fft_plan *p, void *data, uint64_t batch, hipStream_t stream, int variant, const void *hmul = nullptr)
+int fft_exec_device(sdsp_hip_fft_plan *p, void *data, uint64_t batch, hipStream_t stream, int variant, const void *hmul)
 {
     if (batch == 0 || p->path == PATH_NOOP)
         return SDSP_HIP_OK;
     const bool rev = p->direction == SDSP_HIP_REVERSE;
     const fft_kernel_sel sel = select_kernel(p, variant);
-    if (sel.workspace)
-        if (int rc = ensure_workspace(p))
-            return rc;
-
-    switch (sel.id) {
-    case K_NOOP:
-        return SDSP_HIP_OK;
-    case K_UNSUPPORTED:
+    if (sel.id == K_UNSUPPORTED)
         return fail(SDSP_HIP_ERR_UNSUPPORTED, "real-input plans have no alternative kernel variant");
+    if (int rc = check_table(p, sel))
+        return rc;
+    if (sel.launch)
+        return launch_reg(p, sel, data, batch, stream);
+    switch (sel.id) {
     case K_FFT4096_R4:
     case K_FFT4096_R2: {
         fft4096_args a;
@@ -516,75 +773,6 @@ int fft_exec_device(sdsp_hip_fft_plan *p, void *data, uint64_t batch, hipStream_
         a.scale = (float)(1.0 / p->n);
         a.reverse = rev;
         return launch_fft_mix_f32(a, stream);
-    }
-    case K_BIG:
-    case K_BIG_REAL: {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_big;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = (float)(1.0 / p->n);
-        a.reverse = rev;
-        a.nontemporal = 1;
-        if (sel.id == K_BIG_REAL) {
-            a.real_mode = p->real_mode;
-            a.tw2 = p->tw2;
-        }
-        return launch_fft_big_f32(a, stream);
-    }
-    case K_BIG64:
-    case K_BIG64_REAL: {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_big;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = 1.0f;
-        a.scale_d = 1.0 / p->n;
-        a.reverse = rev;
-        if (sel.id == K_BIG64_REAL) {
-            a.real_mode = p->real_mode;
-            a.tw2 = p->tw2;
-        }
-        a.nontemporal = 1;
-        return launch_fft_big_f64(a, stream);
-    }
-    case K_REG64:
-    case K_WAVE64: {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_reg;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = 1.0f;
-        a.scale_d = 1.0 / p->n;
-        a.reverse = rev;
-        a.nontemporal = 1;
-        a.real_mode = p->real_mode;
-        a.tw2 = p->tw2;
-        return sel.id == K_WAVE64 ? launch_fft_wave_f64(a, stream) : launch_fft_reg_f64(a, stream);
-    }
-    case K_WAVE1024:
-    case K_WAVE2:
-    case K_REG32: {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = sel.id == K_WAVE2 ? p->twt_wave : p->twt_reg;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = (float)(1.0 / p->n);
-        a.reverse = rev;
-        a.nontemporal = variant != 1 || (p->tw_lead && !p->real_mode); // variant 1: default cache policy (N < 8192)
-        a.real_mode = p->real_mode;
-        a.tw2 = p->tw2;
-        if (sel.id == K_WAVE1024)
-            return launch_fft_wave_f32(a, stream);
-        return sel.id == K_WAVE2 ? launch_fft_wave2_f32(a, stream) : launch_fft_reg_f32(a, stream);
     }
     case K_TILE: {
         fft_tile_args a{};
@@ -613,179 +801,12 @@ int fft_exec_device(sdsp_hip_fft_plan *p, void *data, uint64_t batch, hipStream_
     default:
         break; // the multi-pass kernels follow
     }
-
-    if (sel.id == K_FFT1M_CHUNKED || sel.id == K_FFT1M_FUSED) {
-        const uint64_t N = 1ull << 20;
-        const float scale = (float)(1.0 / (double)N);
-        if (sel.id == K_FFT1M_CHUNKED) {
-            // two launches per chunk of <= 32 transforms (round 1's schedule; also what plans with a small workspace run)
-            const uint64_t chunk = fft1m_chunk(p);
-            for (uint64_t done = 0; done < batch; done += chunk) {
-                fft1m_args a;
-                a.data = reinterpret_cast<char *>(data) + done * N * 8;
-                a.workspace = p->workspace;
-                a.tw_n = p->tw;
-                a.tw_1024 = p->tw1;
-                a.count = std::min<uint64_t>(chunk, batch - done);
-                a.scale = scale;
-                a.reverse = rev;
-                if (int rc = launch_fft1m_pass(a, 1, stream))
-                    return rc;
-                if (int rc = launch_fft1m_pass(a, 2, stream))
-                    return rc;
-            }
-            return SDSP_HIP_OK;
-        }
-        // default: ONE persistent launch (fft1m_kernels.h): eight ticket queues, per queue a ring of three intermediates,
-        // pass 2 of a queue's transform one ticket step behind its pass 1
-        for (uint64_t done = 0; done < batch; done += p->sync_count) {
-            fft1m_fused_args a;
-            a.data = reinterpret_cast<char *>(data) + done * N * 8;
-            a.workspace = p->workspace;
-            a.tw_1024 = p->tw1;
-            a.sync = p->sync;
-            a.sticky = fft1m_sticky(p);
-            a.spin_limit = p->wait_limit;
-            a.count = std::min<uint64_t>(p->sync_count, batch - done);
-            // a ring of 4 with pass 2 two steps behind measured 42.0-42.2 %, 3 / one step 41.4-41.6 % (profiles/r02_fft1m_lab.md)
-            a.ring = p->ws_batch >= 4 * kFft1mQueues ? 4 : (uint32_t)kFft1mRing;
-            a.lag = a.ring - 2;
-            a.queues = (uint32_t)kFft1mQueues;
-            a.scale = scale;
-            a.reverse = rev;
-            if (int rc = launch_fft1m_fused(a, stream))
-                return rc;
-        }
-        return SDSP_HIP_OK;
-    }
-
-    // the two-pass sizes in one persistent launch per kFused2pUnitsPerLaunch units
-    if (sel.id == K_2PASS_FUSED) {
-        const bool m1 = p->path == PATH_FFT1M; // unit = one transform, the counters of the dedicated kernel
-        const uint64_t per_launch = m1 ? p->sync_count : p->sync_count * p->f2_unit;
-        for (uint64_t done = 0; done < batch; done += per_launch) {
-            fft_2pass_fused_args a;
-            a.data = reinterpret_cast<char *>(data) + done * p->n * esize(p->precision);
-            a.workspace = p->workspace;
-            a.tw_1024 = p->path == PATH_FFT1M ? p->tw1 : p->tw1024; // N = 2^20: n1 = 1024, so W_n1 is that table
-            a.sync = p->sync;
-            a.sticky = reinterpret_cast<char *>(p->sync) + p->sticky_off;
-            a.spin_limit = p->wait_limit;
-            a.count = std::min<uint64_t>(per_launch, batch - done);
-            a.n = p->n;
-            a.unit = m1 ? 1 : p->f2_unit;
-            a.ring = m1 ? 4 : p->f2_ring;
-            a.lag = m1 ? 2 : p->f2_lag;
-            a.queues = m1 ? (uint32_t)kFft1mQueues : p->f2_queues;
-            a.scale = (float)(1.0 / p->n);
-            a.scale_d = 1.0 / p->n;
-            a.reverse = rev;
-            a.hmul = hmul;
-            if (int rc = launch_fft_2pass_fused(p->precision, a, stream))
-                return rc;
-        }
-        return SDSP_HIP_OK;
-    }
-    // N = 2^16 .. 2^19, f32: two passes over HBM (fft_2pass.hip), in chunks whose intermediate is at most 256 MiB
-    if (sel.id == K_2PASS) {
-        const uint64_t chunk = fft2p_chunk(p);
-        for (uint64_t done = 0; done < batch; done += chunk) {
-            fft_2pass_args a;
-            a.data = reinterpret_cast<char *>(data) + done * p->n * esize(p->precision);
-            a.workspace = p->workspace;
-            a.tw_1024 = p->tw1024;
-            a.n = p->n;
-            a.count = std::min<uint64_t>(chunk, batch - done);
-            a.scale = (float)(1.0 / p->n);
-            a.scale_d = 1.0 / p->n;
-            a.reverse = rev;
-            a.hmul = hmul;
-            if (int rc = launch_fft_2pass(p->precision, a, stream))
-                return rc;
-        }
-        return SDSP_HIP_OK;
-    }
-
-    // three streaming passes, N = 16 x N2 with the rows on a tuned single-pass kernel: f32 N = 2^21 .. 2^23, f64
-    // N = 2^14 .. 2^21, and variant 1 of the f32 sizes above
-    if (sel.id == K_MID) {
-        const uint32_t n2 = p->n / 16;
-        uint64_t done = 0;
-        while (done < batch) {
-            const uint64_t nb = std::min<uint64_t>(p->ws_batch, batch - done);
-            char *d = reinterpret_cast<char *>(data) + done * p->n * esize(p->precision);
-            if (int rc = launch_fft_mid_cols(p->precision, d, p->workspace, p->tw1024, n2, nb, rev, stream))
-                return rc;
-            if (int rc = fft_exec_device(p->mid_rows, p->workspace, nb * 16, stream, p->mid_rows->variant))
-                return rc;
-            if (int rc = launch_fft_mid_untwist(p->precision, p->workspace, d, n2, nb, stream))
-                return rc;
-            done += nb;
-        }
-        return SDSP_HIP_OK;
-    }
-
-    // four-step: N = n1 x n2 viewed as a row-major [n1][n2] matrix (index n = n2_count*i1 + i2).
-    //   pass 1: length-n1 transforms down the columns, times W_N^(i2*k1), data -> workspace
-    //   pass 2: length-n2 transforms along the rows, written transposed, workspace -> data
-    const uint64_t N = (uint64_t)p->n1 * p->n2;
-    uint64_t done = 0;
-    while (done < batch) {
-        const uint64_t nb = std::min<uint64_t>(p->ws_batch, batch - done);
-        char *d = reinterpret_cast<char *>(data) + done * N * esize(p->precision);
-        fft_tile_args a{};
-        a.in = d;
-        a.out = p->workspace;
-        a.tw = p->tw1;
-        a.tw_big = p->tw;
-        a.n = p->n1;
-        a.log2n = sdsp_hip_log2(p->n1);
-        a.cols = p->cols1;
-        a.pitch = p->pitch1;
-        a.tiles_per_group = p->n2 / p->cols1;
-        a.total_cols = nb * p->n2;
-        a.group_stride = N;
-        a.in_tile_step = a.out_tile_step = p->cols1;
-        a.in_si = a.out_sk = p->n2;
-        a.in_sc = a.out_sc = 1;
-        a.in_c_fast = a.out_c_fast = 1;
-        a.reverse = rev;
-        a.apply_scale = 0;
-        a.scale = 1.0f;
-        a.scale_d = 1.0;
-        int rc = launch_fft_tile(p->precision, p->radix, a, nb * a.tiles_per_group, stream);
-        if (rc)
+    if (int rc = ensure_workspace(p))
+        return rc;
+    const uint64_t step = fft_step_units(p, sel.id), row_bytes = (uint64_t)p->n * esize(p->precision);
+    for (uint64_t done = 0; done < batch; done += step)
+        if (int rc = fft_exec_step(p, sel.id, static_cast<char *>(data) + done * row_bytes, std::min(step, batch - done), stream, hmul))
             return rc;
-
-        fft_tile_args c{};
-        c.in = p->workspace;
-        c.out = d;
-        c.tw = p->tw2;
-        c.tw_big = nullptr;
-        c.n = p->n2;
-        c.log2n = sdsp_hip_log2(p->n2);
-        c.cols = p->cols2;
-        c.pitch = p->pitch2;
-        c.tiles_per_group = p->n1 / p->cols2;
-        c.total_cols = nb * p->n1;
-        c.group_stride = N;
-        c.in_tile_step = (uint64_t)p->cols2 * p->n2;
-        c.out_tile_step = p->cols2;
-        c.in_si = 1;
-        c.in_sc = p->n2;
-        c.in_c_fast = 0;
-        c.out_sk = p->n1;
-        c.out_sc = 1;
-        c.out_c_fast = 1;
-        c.reverse = rev;
-        c.apply_scale = rev;
-        c.scale = (float)(1.0 / (double)N);
-        c.scale_d = 1.0 / (double)N;
-        rc = launch_fft_tile(p->precision, p->radix, c, nb * c.tiles_per_group, stream);
-        if (rc)
-            return rc;
-        done += nb;
-    }
     return SDSP_HIP_OK;
 }
 
@@ -824,15 +845,16 @@ uint64_t fft_launch_count(const sdsp_hip_fft_plan *p, uint64_t batch, int varian
     switch (sel.id) {
     case K_NOOP:
     case K_UNSUPPORTED: return 0;
-    case K_FFT1M_CHUNKED: return 2 * ceil_div(batch, fft1m_chunk(p));
-    case K_FFT1M_FUSED: return ceil_div(batch, p->sync_count);
-    case K_2PASS: return 2 * ceil_div(batch, fft2p_chunk(p));
-    case K_2PASS_FUSED: return ceil_div(batch, p->path == PATH_FFT1M ? p->sync_count : p->sync_count * p->f2_unit);
-    case K_FOUR_STEP: return 2 * ceil_div(batch, p->ws_batch);
+    case K_FFT1M_FUSED:
+    case K_2PASS_FUSED: return ceil_div(batch, fft_step_units(p, sel.id));
+    case K_FFT1M_CHUNKED:
+    case K_2PASS:
+    case K_FOUR_STEP: return 2 * ceil_div(batch, fft_step_units(p, sel.id));
     case K_MID: {
+        const uint64_t step = fft_step_units(p, K_MID);
         uint64_t n = 0;
-        for (uint64_t done = 0; done < batch; done += p->ws_batch)
-            n += 2 + fft_launch_count(p->mid_rows, std::min<uint64_t>(p->ws_batch, batch - done) * 16, p->mid_rows->variant, false);
+        for (uint64_t done = 0; done < batch; done += step)
+            n += 2 + fft_launch_count(p->mid_rows, std::min(step, batch - done) * 16, p->mid_rows->variant, false);
         return n;
     }
     default: return in_pieces ? ceil_div(batch, fft_piece(p, sel, batch)) : 1;
@@ -912,8 +934,9 @@ int sdsp_hip_device_synchronize(int device)
 
 // ------------------------------------------------------------------ FFT plans
 
-int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int direction, int precision,
-                             uint64_t max_batch, int device)
+// real_mode 0: a complex plan; 1 / 2: the real-input plan of n_real = 2 n (forward / inverse), decided here as the plan it is
+static int fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int direction, int precision, uint64_t max_batch,
+                           int device, int real_mode)
 {
     if (!out)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
@@ -954,6 +977,7 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int
     p->precision = precision;
     p->device = device;
     p->max_batch = max_batch ? max_batch : 1;
+    p->real_mode = real_mode;
     // An explicit radix is the stage type that runs (radix 2: radix-2 butterflies only; radix 4: radix-4 only).  AUTO asks
     // for the fastest kernel: at N = 8192 = 2 * 4^6 that is the radix-4 machinery behind ONE radix-2 stage.
     p->allow_mix = (radix_auto && n == 8192) || radix == 4;
@@ -961,8 +985,30 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int
     int rc = SDSP_HIP_OK;
     std::vector<double> w;
     const uint32_t lds_cap_n = (uint32_t)(fft_tile_max_lds_bytes() / esize(precision));
+    if (n > 1) {
+        make_twiddles(n, direction, w);
+        rc = upload_twiddles(w, precision, &p->tw);
+        p->twiddle_bytes = (uint64_t)n * esize(precision);
+    }
+    // the optional thread-twiddle tables: where some variant of this plan's exec or convolve runs a kernel that reads them
+    if (!rc && uses_twt4096(p))
+        rc = upload_thread_twiddles_4096(w, radix, &p->twt);
+    if (!rc && uses_twt_reg(p))
+        rc = upload_thread_twiddles_reg(w, n, radix, precision, &p->twt_reg);
+    if (!rc && uses_twt_big(p))
+        rc = radix == 4 ? upload_thread_twiddles_big_r4(w, n, precision, &p->twt_big) : upload_thread_twiddles_big(w, n, precision, &p->twt_big);
+    if (!rc && uses_twt_wave(p))
+        rc = upload_thread_twiddles_wave(w, n, radix, &p->twt_wave);
+    if (!rc && uses_mix(p))
+        rc = upload_thread_twiddles_mix(w, n, &p->twt_mix, &p->tw_lead);
     if (n == 1) {
         p->path = PATH_NOOP;
+    } else if (real_mode) { // every size on the split / merge kernels (n = 4096 f32 too: the tuned complex kernels have no split stage)
+        p->path = PATH_REG;
+        make_twiddles(2 * n, direction, w);
+        if (!rc)
+            rc = upload_twiddles(w, precision, &p->tw2); // W_2n
+        p->twiddle_bytes += 2ull * n * esize(precision);
     } else if (n <= lds_cap_n) {
         if (n == 4096 && radix == 4 && precision == SDSP_HIP_F32)
             p->path = PATH_FFT4096;
@@ -972,22 +1018,6 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int
             p->path = PATH_REG;
         else
             p->path = PATH_TILE;
-        make_twiddles(n, direction, w);
-        rc = upload_twiddles(w, precision, &p->tw);
-        p->twiddle_bytes = (uint64_t)n * esize(precision);
-        if (!rc && n == 4096 && precision == SDSP_HIP_F32)
-            rc = upload_thread_twiddles_4096(w, radix, &p->twt);
-        if (!rc && ((precision == SDSP_HIP_F32 && fft_reg_supports(n, radix)) ||
-                    (precision == SDSP_HIP_F64 && fft_reg64_supports(n, radix))))
-            rc = upload_thread_twiddles_reg(w, n, radix, precision, &p->twt_reg);
-        if (!rc && precision == SDSP_HIP_F32 && (fft_big_supports(n, radix) || fft_big_conv_supports(n, radix)))
-            rc = big_r4_form(n, radix) ? upload_thread_twiddles_big_r4(w, n, SDSP_HIP_F32, &p->twt_big) : upload_thread_twiddles_big(w, n, SDSP_HIP_F32, &p->twt_big);
-        if (!rc && precision == SDSP_HIP_F64 && fft_big64_supports(n, radix))
-            rc = radix == 4 ? upload_thread_twiddles_big_r4(w, n, SDSP_HIP_F64, &p->twt_big) : upload_thread_twiddles_big(w, n, SDSP_HIP_F64, &p->twt_big);
-        if (!rc && precision == SDSP_HIP_F32 && fft_wave2_supports(n, radix))
-            rc = upload_thread_twiddles_wave(w, n, radix, &p->twt_wave);
-        if (!rc && precision == SDSP_HIP_F32 && fft_mix_supports(n) && p->allow_mix)
-            rc = upload_thread_twiddles_mix(w, n, &p->twt_mix, &p->tw_lead);
         pick_tile(precision, n, std::max<uint32_t>(1, 1024 / n), &p->cols, &p->pitch);
         if (p->cols > 16)
             pick_tile(precision, n, 16, &p->cols, &p->pitch);
@@ -1004,12 +1034,6 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int
             p->n1 = 1u << (2 * ((d + 1) / 2));
         }
         p->n2 = n / p->n1;
-        make_twiddles(n, direction, w);
-        rc = upload_twiddles(w, precision, &p->tw);
-        if (!rc && precision == SDSP_HIP_F32 && fft_big_supports(n, radix))
-            rc = upload_thread_twiddles_big(w, n, SDSP_HIP_F32, &p->twt_big);
-        if (!rc && precision == SDSP_HIP_F64 && fft_big64_supports(n, radix))
-            rc = radix == 4 ? upload_thread_twiddles_big_r4(w, n, SDSP_HIP_F64, &p->twt_big) : upload_thread_twiddles_big(w, n, SDSP_HIP_F64, &p->twt_big);
         if (!rc) {
             make_twiddles(p->n1, direction, w);
             rc = upload_twiddles(w, precision, &p->tw1);
@@ -1018,7 +1042,7 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int
             make_twiddles(p->n2, direction, w);
             rc = upload_twiddles(w, precision, &p->tw2);
         }
-        p->twiddle_bytes = ((uint64_t)n + p->n1 + p->n2) * esize(precision);
+        p->twiddle_bytes += ((uint64_t)p->n1 + p->n2) * esize(precision);
         pick_tile(precision, p->n1, 16, &p->cols1, &p->pitch1);
         pick_tile(precision, p->n2, 16, &p->cols2, &p->pitch2);
         // the tuned 2^20 path keeps 24 intermediates for the persistent kernel (8 queues x 3) / 32 for variant 1's chunks
@@ -1085,6 +1109,12 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int
     return SDSP_HIP_OK;
 }
 
+int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int direction, int precision,
+                             uint64_t max_batch, int device)
+{
+    return fft_plan_create(out, n, radix, direction, precision, max_batch, device, 0);
+}
+
 int sdsp_hip_rfft_plan_create_p(sdsp_hip_fft_plan **out, uint32_t n_real, int radix, int direction, int precision,
                                 uint64_t max_batch, int device)
 {
@@ -1104,28 +1134,7 @@ int sdsp_hip_rfft_plan_create_p(sdsp_hip_fft_plan **out, uint32_t n_real, int ra
                           (precision == SDSP_HIP_F64 && fft_big64_real_supports(n, radix));    // fft_big64.hip, REAL
     if (!big_real && (precision == SDSP_HIP_F32 ? !fft_reg_supports(n, radix) : !fft_reg64_supports(n, radix)))
         return fail(SDSP_HIP_ERR_UNSUPPORTED, "real-input plans cover n_real = 32 .. 32768 (f32; radix 2: .. 65536) / 32 .. 16384 (f64; radix 2: .. 32768)");
-    sdsp_hip_fft_plan *p = nullptr;
-    if (int rc = sdsp_hip_fft_plan_create(&p, n, radix, direction, precision, max_batch, device))
-        return rc;
-    p->path = PATH_REG; // also at n = 4096 f32 (the tuned complex kernels have no split stage)
-    p->real_mode = direction == SDSP_HIP_FORWARD ? 1 : 2;
-    std::vector<double> w;
-    if (big_real && !p->twt_big) { // (every complex plan these kernels serve has the table already)
-        make_twiddles(n, direction, w);
-        if (int rc = (precision == SDSP_HIP_F32 && big_r4_form(n, radix)) ? upload_thread_twiddles_big_r4(w, n, SDSP_HIP_F32, &p->twt_big)
-                                                                          : upload_thread_twiddles_big(w, n, precision, &p->twt_big)) {
-            sdsp_hip_fft_plan_destroy(p);
-            return rc;
-        }
-    }
-    make_twiddles(n_real, direction, w);
-    if (int rc = upload_twiddles(w, precision, &p->tw2)) {
-        sdsp_hip_fft_plan_destroy(p);
-        return rc;
-    }
-    p->twiddle_bytes += (uint64_t)n_real * esize(precision);
-    *out = p;
-    return SDSP_HIP_OK;
+    return fft_plan_create(out, n, radix, direction, precision, max_batch, device, direction == SDSP_HIP_FORWARD ? 1 : 2);
 }
 
 int sdsp_hip_rfft_plan_create(sdsp_hip_fft_plan **out, uint32_t n_real, int radix, int direction, uint64_t max_batch,
@@ -1246,8 +1255,6 @@ int sdsp_hip_fft_exec_sharded(sdsp_hip_fft_plan *const *plans, int n_plans, void
     return SDSP_HIP_OK;
 }
 
-static int convolve_device(sdsp_hip_fft_plan *p, void *data, const void *h, uint64_t batch, void *stream);
-
 int sdsp_hip_fft_convolve(sdsp_hip_fft_plan *p, void *data, const void *h, uint64_t batch, void *stream)
 {
     if (!p)
@@ -1262,117 +1269,41 @@ int sdsp_hip_fft_convolve(sdsp_hip_fft_plan *p, void *data, const void *h, uint6
         return fail(SDSP_HIP_ERR_UNSUPPORTED, "convolve needs a complex plan (real-input plans are not supported)");
     if (int rc = use_device(p->device))
         return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // this call's launches report into clean sticky abort words (the persistent two-pass kernels; forward and reverse half)
     if (p->sync)
-        HIP_TRY(hipMemsetAsync(fft1m_sticky(p), 0, sizeof(unsigned), reinterpret_cast<hipStream_t>(stream)));
+        HIP_TRY(hipMemsetAsync(fft1m_sticky(p), 0, sizeof(unsigned), s));
     if (p->partner && p->partner->sync)
-        HIP_TRY(hipMemsetAsync(fft1m_sticky(p->partner), 0, sizeof(unsigned), reinterpret_cast<hipStream_t>(stream)));
-    // launch pieces as in sdsp_hip_fft_exec (N <= 8192, single-launch kernels); the three-launch composition runs piece by piece
-    const bool single = (p->path == PATH_FFT4096 || p->path == PATH_REG || p->path == PATH_TILE) && p->n <= 8192;
-    const uint64_t row_bytes = (uint64_t)p->n * esize(p->precision);
-    const uint64_t piece = single ? piece_units(batch, row_bytes, p->n < 16 ? 4096 : 256) : batch;
-    for (uint64_t done = 0; done < batch; done += piece)
-        if (int rc = convolve_device(p, static_cast<char *>(data) + done * row_bytes, h, std::min(piece, batch - done), stream))
+        HIP_TRY(hipMemsetAsync(fft1m_sticky(p->partner), 0, sizeof(unsigned), s));
+    const fft_kernel_sel sel = select_conv(p, p->variant);
+    if (sel.conv) {
+        if (int rc = check_table(p, sel))
             return rc;
-    return SDSP_HIP_OK;
-}
-
-static int convolve_device(sdsp_hip_fft_plan *p, void *data, const void *h, uint64_t batch, void *stream)
-{
-    if (p->path == PATH_FFT4096 && p->variant == 0)
-        return launch_fft4096_conv_f32(data, p->twt, h, batch, stream);
-    // N = 8192 / 16384 / 32768 radix-2 stages, N = 16384 radix-4 stages: both transforms and the multiply in the
-    // registers-resident kernel (fft_big.hip)
-    if ((p->path == PATH_REG || p->path == PATH_FOUR_STEP) && p->precision == SDSP_HIP_F32 && p->variant == 0 && !p->real_mode &&
-        p->twt_big && fft_big_conv_supports(p->n, p->radix)) {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_big;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = (float)(1.0 / p->n);
-        a.reverse = 0;
-        a.nontemporal = 1;
-        a.real_mode = 3;
-        a.tw2 = h;
-        return launch_fft_big_f32(a, stream);
-    }
-    // variant 0: the fused kernel of the size; variant 2: the register-pass family's fused MODE 3 where a one-wave kernel
-    // is the default (A/B and cross-check); any other variant: three launches
-    if (p->path == PATH_REG && p->precision == SDSP_HIP_F32 && (p->variant == 0 || p->variant == 2) && !p->real_mode) {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_reg;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = (float)(1.0 / p->n);
-        a.reverse = 0;
-        a.nontemporal = 1;
-        a.real_mode = 3; // fused convolution: one kernel, h travels in tw2
-        a.tw2 = h;
-        if (p->variant == 0 && fft_wave_supports(p->n, p->radix)) // N = 1024: both transforms in one wave's registers (fft_wave.hip)
-            return launch_fft_wave_f32(a, stream);
-        if (p->variant == 0 && p->twt_wave) { // N = 256 / 512 radix 2 (N = 2048 radix 2 was taken by the fft_big.hip form above: 65-69 % against 52 %)
-            a.tw = p->twt_wave;
-            return launch_fft_wave2_f32(a, stream);
-        }
-        return launch_fft_reg_f32(a, stream);
-    }
-    // double, N = 4096 / 8192 / 16384 radix-2 plans: both transforms and the multiply in the registers-resident kernel (fft_big64.hip);
-    // variant 2: what served N <= 8192 before (the register-pass family's fused MODE 3), any other variant: three launches
-    if ((p->path == PATH_REG || p->path == PATH_FOUR_STEP) && p->precision == SDSP_HIP_F64 && p->variant == 0 && !p->real_mode && p->twt_big &&
-        fft_big64_conv_supports(p->n, p->radix)) {
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_big;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = 1.0f;
-        a.scale_d = 1.0 / p->n;
-        a.reverse = 0;
-        a.nontemporal = 1;
-        a.real_mode = 3;
-        a.tw2 = h;
-        return launch_fft_big_f64(a, stream);
-    }
-    if (p->path == PATH_REG && p->precision == SDSP_HIP_F64 && (p->variant == 0 || p->variant == 2) && !p->real_mode) { // f64, N = 16 .. 8192
-        fft_reg_args a;
-        a.data = data;
-        a.tw = p->twt_reg;
-        a.n = p->n;
-        a.radix = p->radix;
-        a.batch = batch;
-        a.scale = 1.0f;
-        a.scale_d = 1.0 / p->n;
-        a.reverse = 0;
-        a.nontemporal = 1;
-        a.real_mode = 3;
-        a.tw2 = h;
-        return launch_fft_reg_f64(a, stream);
-    }
-    if (!p->partner) {
-        if (int rc = sdsp_hip_fft_plan_create(&p->partner, p->n, p->radix, SDSP_HIP_REVERSE, p->precision,
-                                              p->max_batch, p->device))
+    } else if (!p->partner) { // the reverse half of the three launches
+        if (int rc = sdsp_hip_fft_plan_create(&p->partner, p->n, p->radix, SDSP_HIP_REVERSE, p->precision, p->max_batch, p->device))
             return rc;
         p->partner->wait_limit = p->wait_limit;
     }
-    // PATH_FFT4096 with variant != 0 selects this three-launch path for cross-checking: its transforms run variant 0
-    int v = p->path == PATH_FFT4096 ? 0 : p->variant;
-    // the two-pass sizes: the forward transform's pass 2 multiplies by h on its way out (fft_2pass.hip, HM) -- four passes over HBM
-    // instead of five.  N = 2^20 f32 takes the generic persistent kernel (its variant 2) for that half
-    if (p->path == PATH_FFT1M && v == 0 && select_kernel(p, 2).id == K_2PASS_FUSED)
-        v = 2;
-    const fft_kernel_id fwd_id = select_kernel(p, v).id;
-    const bool fused_mul = fwd_id == K_2PASS || fwd_id == K_2PASS_FUSED;
-    int rc = fft_exec_device(p, data, batch, reinterpret_cast<hipStream_t>(stream), v, fused_mul ? h : nullptr);
-    if (!rc && !fused_mul)
-        rc = launch_pointwise_mul(p->precision, data, h, p->n, batch, stream);
-    if (!rc)
-        rc = fft_exec_device(p->partner, data, batch, reinterpret_cast<hipStream_t>(stream), p->partner->variant);
-    return rc;
+    const bool fused_mul = sel.id == K_2PASS || sel.id == K_2PASS_FUSED; // the forward transform's pass 2 multiplies by h
+    const uint64_t row_bytes = (uint64_t)p->n * esize(p->precision);
+    const uint64_t piece = fft_piece(p, sel, batch);
+    for (uint64_t done = 0; done < batch; done += piece) {
+        char *d = static_cast<char *>(data) + done * row_bytes;
+        const uint64_t nb = std::min(piece, batch - done);
+        int rc;
+        if (sel.conv) {
+            rc = sel.launch ? launch_reg(p, sel, d, nb, s, h) : launch_fft4096_conv_f32(d, p->twt, h, nb, stream);
+        } else {
+            rc = fft_exec_device(p, d, nb, s, sel.variant, fused_mul ? h : nullptr);
+            if (!rc && !fused_mul)
+                rc = launch_pointwise_mul(p->precision, d, h, p->n, nb, stream);
+            if (!rc)
+                rc = fft_exec_device(p->partner, d, nb, s, p->partner->variant);
+        }
+        if (rc)
+            return rc;
+    }
+    return SDSP_HIP_OK;
 }
 
 int sdsp_hip_fft_plan_get_info(const sdsp_hip_fft_plan *p, sdsp_hip_fft_plan_info *info)
