@@ -131,6 +131,21 @@ public:
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     const std::array<double, n_taps> &coeff() const { return m_coeff; }
+    // what the plan computes with: method (SDSP_HIP_FIR_DIRECT / _FFT), fft_n, hop, dominant kernel
+    sdsp_hip_fir_plan_info info()
+    {
+        ensure_plan();
+        sdsp_hip_fir_plan_info i{};
+        detail::check(sdsp_hip_fir_plan_get_info(m_plan, &i));
+        return i;
+    }
+
+protected:
+    // the FFT-domain plan of fft_fir_bank (fft_n = 0: auto; workspace_bytes = 0: default budget)
+    fir_bank(std::uint64_t channels, int device, std::uint32_t fft_n, std::uint64_t workspace_bytes)
+        : m_channels(channels), m_device(device), m_fft(true), m_fft_n(fft_n), m_workspace_bytes(workspace_bytes)
+    {
+    }
 
 private:
     static constexpr size_t hist = n_taps > 1 ? n_taps - 1 : 1;
@@ -149,7 +164,12 @@ private:
     }
     void ensure_plan()
     {
-        if (!m_plan)
+        if (m_plan)
+            return;
+        if (m_fft)
+            detail::check(sdsp_hip_fir_fft_plan_create(&m_plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(),
+                                                       detail::precision_of<real_t>::value, m_fft_n, m_workspace_bytes, m_device));
+        else
             detail::check(sdsp_hip_fir_plan_create(&m_plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(),
                                                    detail::precision_of<real_t>::value, m_device));
     }
@@ -173,6 +193,22 @@ private:
     filter_type m_f_type{ filter_type::none };
     sdsp_hip_fir_plan *m_plan{ nullptr };
     void *m_state{ nullptr };
+    bool m_fft{ false };
+    std::uint32_t m_fft_n{ 0 };
+    std::uint64_t m_workspace_bytes{ 0 };
+};
+
+// ---- the same bank in the frequency domain (overlap-save, sdsp_hip_fir_fft_plan_create): long filters, up to 16384 taps in
+// float and 8192 in double.  Same surface, state layout and streaming as fir_bank; results agree within rounding, not bit for bit.
+template <size_t n_taps, typename real_t = float> class fft_fir_bank : public fir_bank<n_taps, real_t> {
+    static_assert(n_taps <= (std::is_same<real_t, double>::value ? SDSP_HIP_FIR_FFT_MAX_TAPS_F64 : SDSP_HIP_FIR_FFT_MAX_TAPS),
+                  "too many taps for the FFT-domain FIR plan");
+
+public:
+    explicit fft_fir_bank(std::uint64_t channels, int device = 0, std::uint32_t fft_n = 0, std::uint64_t workspace_bytes = 0)
+        : fir_bank<n_taps, real_t>(channels, device, fft_n, workspace_bytes)
+    {
+    }
 };
 } // namespace sdsp
 

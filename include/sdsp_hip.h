@@ -70,6 +70,12 @@ typedef enum {
 #define SDSP_HIP_RADIX_AUTO 0
 #define SDSP_HIP_STAGES_2_THEN_4 24 /* plan info: radix-2 stage(s) in front of radix-4 stages (mixed radix) */
 #define SDSP_HIP_FIR_MAX_TAPS 4096
+/* FFT-domain (overlap-save) FIR plans: f32 up to 16384 taps, f64 up to 8192 (fft_n <= 32768 / 16384 keeps the convolution one
+ * fused kernel) */
+#define SDSP_HIP_FIR_FFT_MAX_TAPS 16384
+#define SDSP_HIP_FIR_FFT_MAX_TAPS_F64 8192
+#define SDSP_HIP_FIR_DIRECT 0
+#define SDSP_HIP_FIR_FFT 1
 
 typedef struct sdsp_hip_fft_plan sdsp_hip_fft_plan;
 typedef struct sdsp_hip_iir_plan sdsp_hip_iir_plan;
@@ -343,7 +349,44 @@ int sdsp_hip_fir_process(sdsp_hip_fir_plan *plan, void *data, uint64_t channels,
 int sdsp_hip_fir_process_host(sdsp_hip_fir_plan *plan, void *host_data, uint64_t channels,
                               uint64_t samples, uint64_t stride, void *host_state);
 int sdsp_hip_fir_state_bytes(const sdsp_hip_fir_plan *plan, uint64_t channels, uint64_t *bytes);
+/* direct plans: kernel variants of sdsp_fir_kernel (same values); FFT plans: the variant of the inner convolution
+ * (sdsp_hip_fft_convolve's numbering on a forward radix-2 plan of size fft_n: 0 = the fused kernel, 1 = the three-launch
+ * composition -- an independent cross-check, within the same tolerance).  Whatever the variant needs is allocated here. */
 int sdsp_hip_fir_plan_set_variant(sdsp_hip_fir_plan *plan, int variant);
+
+/*
+ * FFT-domain FIR plans (overlap-save) for long filters: the same filter as a direct plan of the same h,
+ * computed per frame of N = fft_n inputs as IFFT(FFT(frame) .* H) with H = FFT(h zero-padded to N), computed in double at
+ * creation and rounded once to the plan precision.  Hop L = N - taps + 1 outputs per frame; N >= 2 (taps - 1).  Two frames
+ * of one channel share one complex transform (real / imaginary part).  Rounding differs from the direct form (the error is
+ * normwise per frame pair, ~1e-7 in f32, ~1e-15 in f64), so block-by-block calls match one long call within that
+ * tolerance, not bit for bit.
+ * sdsp_hip_fir_process / _process_host / _state_bytes / _plan_set_variant / _plan_destroy take these plans with the same
+ * arguments, stride and state layout as direct plans: a stream may move between a direct and an FFT plan of the same h from one
+ * block to the next.  A process call runs in slices of the plan's workspace (frame gather -> convolution -> scatter in place,
+ * then the new history); it allocates nothing and can be stream-captured.  One process call per plan in flight: the slices
+ * share the plan's workspace, so two calls on the SAME plan must not overlap (use one plan per stream).
+ */
+/* auto FFT size for `taps` (power of two, N >= 2(taps-1), within the fused-convolution range of the precision) */
+int sdsp_hip_fir_fft_size(uint32_t taps, int precision, uint32_t *fft_n);
+/* fft_n = 0: auto; workspace_bytes = 0: default budget (rounded down to whole transforms, at least one).
+ * Errors: taps == 0 or above the precision's maximum, fft_n not a power of two or below 2 (taps - 1):
+ * SDSP_HIP_ERR_INVALID_SIZE; fft_n outside the fused convolution (f32 16 .. 32768, f64 16 .. 16384): SDSP_HIP_ERR_UNSUPPORTED;
+ * a bad precision or a null pointer: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_fir_fft_plan_create(sdsp_hip_fir_plan **plan, uint32_t taps, const double *h, int precision,
+                                 uint32_t fft_n, uint64_t workspace_bytes, int device);
+typedef struct {
+    uint32_t taps;
+    int precision;
+    int device;
+    int method;               /* SDSP_HIP_FIR_DIRECT / SDSP_HIP_FIR_FFT */
+    uint32_t fft_n, hop;      /* 0 for direct plans */
+    uint64_t workspace_bytes; /* FFT plans: frame pairs + staged history + carry */
+    char kernel[64];          /* dominant kernel: "sdsp_fir_kernel" or the convolution's */
+} sdsp_hip_fir_plan_info;
+int sdsp_hip_fir_plan_get_info(const sdsp_hip_fir_plan *plan, sdsp_hip_fir_plan_info *info);
+/* kernel launches one sdsp_hip_fir_process(plan, ., channels, samples, ...) with a state buffer issues (memsets not counted) */
+int sdsp_hip_fir_plan_launches(const sdsp_hip_fir_plan *plan, uint64_t channels, uint64_t samples, uint64_t *launches);
 
 #ifdef __cplusplus
 }

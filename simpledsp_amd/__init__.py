@@ -5,11 +5,12 @@ this package is its Python host mirror.  Importing does not touch the GPU; any c
 the library or without a HIP device raises (there is no CPU path here).
 """
 from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP, IIR_HP, IIR_BP, FILTER_NONE,
-                   FILTER_LOW_PASS, FILTER_HIGH_PASS, FILTER_BAND_PASS, FILTER_BAND_STOP, SdspHipError, load)
+                   FILTER_LOW_PASS, FILTER_HIGH_PASS, FILTER_BAND_PASS, FILTER_BAND_STOP, FIR_DIRECT, FIR_FFT, SdspHipError,
+                   load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
 from .iir import casc_2o_iir, casc_2o_iir_lp, casc_2o_iir_hp, casc_2o_iir_bp
-from .fir import fir_filter
+from .fir import fir_filter, fft_fir_filter, fir_fft_size
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

@@ -39,6 +39,16 @@ class PlanInfo(C.Structure):
     ]
 
 
+class FirPlanInfo(C.Structure):
+    _fields_ = [
+        ("taps", C.c_uint32), ("precision", C.c_int), ("device", C.c_int), ("method", C.c_int),
+        ("fft_n", C.c_uint32), ("hop", C.c_uint32), ("workspace_bytes", C.c_uint64), ("kernel", C.c_char * 64),
+    ]
+
+
+FIR_DIRECT, FIR_FFT = 0, 1
+
+
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -94,6 +104,10 @@ SIGNATURES = {
     "sdsp_hip_fir_process_host": (_i, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "sdsp_hip_fir_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_fir_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_fir_fft_size": (_i, [_u32, _i, C.POINTER(_u32)]),
+    "sdsp_hip_fir_fft_plan_create": (_i, [_pp, _u32, _vp, _i, _u32, _u64, _i]),
+    "sdsp_hip_fir_plan_get_info": (_i, [_vp, C.POINTER(FirPlanInfo)]),
+    "sdsp_hip_fir_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
 }
 
 _lib = None

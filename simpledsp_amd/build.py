@@ -43,6 +43,7 @@ SOURCES = {
     "fft_2pass.hip": ["-fno-slp-vectorize"],
     "iir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "fir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps: multiply then add, like the oracle
+    "fir_fft.hip": [],
 }
 
 

@@ -309,6 +309,14 @@ struct sdsp_hip_fir_plan {
     uint32_t taps = 0;
     int precision = 0, device = 0, variant = 0;
     void *h_dev = nullptr;
+    // FFT-domain plans (sdsp_hip_fir_fft_plan_create, fir_fft.hip)
+    int method = SDSP_HIP_FIR_DIRECT;
+    uint32_t fft_n = 0, hop = 0;
+    sdsp_hip_fft_plan *conv = nullptr; // forward radix-2 plan of size fft_n; its variant is the plan's
+    void *H = nullptr;                 // FFT(h zero-padded to fft_n), plan precision, fft_n complex
+    void *ws = nullptr;                // ws_units x fft_n complex (frame pairs), then ws_units x (taps-1) staged history
+    void *carry = nullptr;             // 2 x (taps-1): the straddling channel's inputs, ping-pong between slices
+    uint64_t ws_units = 0, workspace_bytes = 0;
 };
 
 namespace
@@ -1641,9 +1649,284 @@ int sdsp_hip_fir_plan_destroy(sdsp_hip_fir_plan *p)
 {
     if (!p)
         return SDSP_HIP_OK;
-    if (p->h_dev && use_device(p->device) == SDSP_HIP_OK)
+    if (use_device(p->device) == SDSP_HIP_OK) {
         (void)hipFree(p->h_dev);
+        (void)hipFree(p->H);
+        (void)hipFree(p->ws);
+        (void)hipFree(p->carry);
+    }
+    if (p->conv)
+        sdsp_hip_fft_plan_destroy(p->conv);
     delete p;
+    return SDSP_HIP_OK;
+}
+
+// ------------------------------------------------------------------ FFT-domain FIR plans (overlap-save)
+
+namespace
+{
+// frame pairs + staged history of one slice.  Measured (tools/bench_fir_fft.py): 16 / 32 / 64 / 128 / 256 /
+// 512 MiB, f32 1024 taps 98.8 / 74.5 / 56.6 / 49.9 / 47.9 / 49.0 ms, f64 1024 taps 109 / 70.1 / 49.1 / 44.9 / 41.8 / 41.4 ms: fewer,
+// longer slices win; keeping a slice inside the Infinity Cache (<= 128 MiB) does not
+constexpr uint64_t kFirFftDefaultBudget = 256ull << 20;
+// auto fft_n: the smallest power of two >= 4 taps, but not above 4096 unless 2 (taps - 1) needs it.  Measured on 4096-sample rows
+// (DESIGN.md section 5.9): 1024 taps N = 2048 / 4096 / 8192 / 16384: 53.0 / 49.9 / 85.1 / 189 ms; 4096 taps N = 8192 / 16384 / 32768:
+// 93.7 / 200 / 445 ms -- the fused convolution slows down above N = 4096 and short rows pay for the padding of a large frame
+constexpr uint32_t kFirFftAutoRatio = 4, kFirFftAutoCap = 4096;
+
+uint32_t fir_fft_max_taps(int precision) { return precision == SDSP_HIP_F64 ? SDSP_HIP_FIR_FFT_MAX_TAPS_F64 : SDSP_HIP_FIR_FFT_MAX_TAPS; }
+// the fused convolution's range on radix-2 plans (sdsp_hip_fft_convolve)
+uint32_t fir_fft_max_n(int precision) { return precision == SDSP_HIP_F64 ? 16384u : 32768u; }
+constexpr uint32_t kFirFftMinN = 16;
+
+// what the plan's inner convolution needs for its current variant, allocated now so that process never allocates: the
+// three-launch composition's reverse partner and the multi-pass workspaces
+int fir_fft_prepare_conv(sdsp_hip_fir_plan *p)
+{
+    sdsp_hip_fft_plan *c = p->conv;
+    const fft_kernel_sel sel = select_conv(c, c->variant);
+    if (sel.conv)
+        return SDSP_HIP_OK;
+    if (!c->partner) {
+        if (int rc = sdsp_hip_fft_plan_create(&c->partner, c->n, c->radix, SDSP_HIP_REVERSE, c->precision, c->max_batch, c->device))
+            return rc;
+        c->partner->wait_limit = c->wait_limit;
+    }
+    if (select_kernel(c, sel.variant).workspace)
+        if (int rc = ensure_workspace(c))
+            return rc;
+    if (select_kernel(c->partner, c->partner->variant).workspace)
+        if (int rc = ensure_workspace(c->partner))
+            return rc;
+    return SDSP_HIP_OK;
+}
+
+// kernel launches of sdsp_hip_fft_convolve(c, ., ., batch) -- the same loop
+uint64_t conv_launch_count(const sdsp_hip_fft_plan *c, uint64_t batch)
+{
+    const fft_kernel_sel sel = select_conv(c, c->variant);
+    const bool fused_mul = sel.id == K_2PASS || sel.id == K_2PASS_FUSED;
+    const uint64_t piece = fft_piece(c, sel, batch);
+    uint64_t n = 0;
+    for (uint64_t done = 0; done < batch; done += piece) {
+        const uint64_t nb = std::min(piece, batch - done);
+        if (sel.conv)
+            n += 1;
+        else
+            n += fft_launch_count(c, nb, sel.variant, false) + (fused_mul ? 0 : 1) +
+                 (c->partner ? fft_launch_count(c->partner, nb, c->partner->variant, false) : 0);
+    }
+    return n;
+}
+
+// the stream's frame grid: F frames, P pairs per channel
+void fir_fft_grid(const sdsp_hip_fir_plan *p, uint64_t samples, uint64_t *frames, uint64_t *pairs)
+{
+    *frames = (samples + p->hop - 1) / p->hop;
+    *pairs = (*frames + 1) / 2;
+}
+
+// H = FFT(h zero-padded to n) in double (iterative radix 2 on the library's own twiddle row), natural order
+std::vector<double> fir_fft_response(const double *h, uint32_t taps, uint32_t n)
+{
+    std::vector<double> x(2 * static_cast<size_t>(n), 0.0), w(2 * static_cast<size_t>(n));
+    for (uint32_t i = 0; i < taps; i++)
+        x[2 * i] = h[i];
+    sdsp_hip_calc_twiddles(n, SDSP_HIP_FORWARD, w.data());
+    const uint32_t lg = sdsp_hip_log2(n);
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t r = 0;
+        for (uint32_t b = 0; b < lg; b++)
+            r |= ((i >> b) & 1u) << (lg - 1 - b);
+        if (r > i) {
+            std::swap(x[2 * i], x[2 * r]);
+            std::swap(x[2 * i + 1], x[2 * r + 1]);
+        }
+    }
+    for (uint32_t len = 2; len <= n; len <<= 1) {
+        const uint32_t half = len / 2, step = n / len;
+        for (uint32_t s0 = 0; s0 < n; s0 += len)
+            for (uint32_t j = 0; j < half; j++) {
+                const double wr = w[2 * (j * step)], wi = w[2 * (j * step) + 1];
+                double *a = &x[2 * (s0 + j)], *b = &x[2 * (s0 + j + half)];
+                const double tr = b[0] * wr - b[1] * wi, ti = b[0] * wi + b[1] * wr;
+                b[0] = a[0] - tr;
+                b[1] = a[1] - ti;
+                a[0] += tr;
+                a[1] += ti;
+            }
+    }
+    return x;
+}
+
+int fir_fft_process(sdsp_hip_fir_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride, void *state, void *stream)
+{
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint32_t t1 = p->taps - 1;
+    uint64_t frames = 0, pairs = 0;
+    fir_fft_grid(p, samples, &frames, &pairs);
+    if (channels > ~0ull / pairs)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * pairs;
+    char *tails = static_cast<char *>(p->ws) + p->ws_units * p->fft_n * 2 * rs;
+    fir_os_args a{};
+    a.data = data;
+    a.state = t1 ? state : nullptr;
+    a.ws = p->ws;
+    a.tails = a.state ? tails : nullptr;
+    a.stride = stride;
+    a.samples = samples;
+    a.frames = frames;
+    a.pairs = pairs;
+    a.n = p->fft_n;
+    a.hop = p->hop;
+    a.taps_m1 = t1;
+    uint64_t k = 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units, k++) {
+        a.g0 = g0;
+        a.units = std::min(p->ws_units, total - g0);
+        a.carry_in = static_cast<char *>(p->carry) + ((k + 1) & 1) * t1 * rs;
+        a.carry_out = static_cast<char *>(p->carry) + (k & 1) * t1 * rs;
+        if (int rc = launch_fir_os(p->precision, a, FIR_OS_FRAME, stream))
+            return rc;
+        if (int rc = sdsp_hip_fft_convolve(p->conv, p->ws, p->H, a.units, stream))
+            return rc;
+        if (int rc = launch_fir_os(p->precision, a, FIR_OS_SCATTER, stream))
+            return rc;
+        if (a.state)
+            if (int rc = launch_fir_os(p->precision, a, FIR_OS_STATE, stream))
+                return rc;
+    }
+    return SDSP_HIP_OK;
+}
+} // namespace
+
+int sdsp_hip_fir_fft_size(uint32_t taps, int precision, uint32_t *fft_n)
+{
+    if (!fft_n)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "fft_n is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (taps == 0 || taps > fir_fft_max_taps(precision))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_FIR_FFT_MAX_TAPS] (f64: SDSP_HIP_FIR_FFT_MAX_TAPS_F64)");
+    const uint64_t want = std::max<uint64_t>(2ull * (taps - 1), std::min<uint64_t>(static_cast<uint64_t>(kFirFftAutoRatio) * taps, kFirFftAutoCap));
+    uint32_t n = kFirFftMinN;
+    while (n < want && n < fir_fft_max_n(precision))
+        n <<= 1;
+    *fft_n = n; // >= 2 (taps - 1): the clamp only binds where 2 x max taps = max n
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fir_fft_plan_create(sdsp_hip_fir_plan **out, uint32_t taps, const double *h, int precision, uint32_t fft_n,
+                                 uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "coefficient pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (taps == 0 || taps > fir_fft_max_taps(precision))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_FIR_FFT_MAX_TAPS] (f64: SDSP_HIP_FIR_FFT_MAX_TAPS_F64)");
+    if (fft_n == 0) {
+        if (int rc = sdsp_hip_fir_fft_size(taps, precision, &fft_n))
+            return rc;
+    } else {
+        if (!sdsp_hip_is_power_of_2(fft_n) || fft_n < 2ull * (taps - 1))
+            return fail(SDSP_HIP_ERR_INVALID_SIZE, "fft_n must be a power of 2 and >= 2 (taps - 1)");
+        if (fft_n < kFirFftMinN || fft_n > fir_fft_max_n(precision))
+            return fail(SDSP_HIP_ERR_UNSUPPORTED, "fft_n must be in the fused convolution's range (f32 16 .. 32768, f64 16 .. 16384)");
+    }
+    if (int rc = use_device(device))
+        return rc;
+    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t unit_bytes = 2ull * fft_n * rs + static_cast<uint64_t>(taps - 1) * rs; // one frame pair + its staged history
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kFirFftDefaultBudget;
+    auto *p = new sdsp_hip_fir_plan();
+    p->taps = taps;
+    p->precision = precision;
+    p->device = device;
+    p->method = SDSP_HIP_FIR_FFT;
+    p->fft_n = fft_n;
+    p->hop = fft_n - taps + 1;
+    p->ws_units = std::max<uint64_t>(1, budget / unit_bytes);
+    p->workspace_bytes = p->ws_units * unit_bytes + 2ull * (taps - 1) * rs;
+    int rc = sdsp_hip_fft_plan_create(&p->conv, fft_n, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device);
+    if (!rc && !select_conv(p->conv, 0).conv)
+        rc = fail(SDSP_HIP_ERR_UNSUPPORTED, "no fused convolution for this fft_n");
+    if (!rc) {
+        hipError_t e = hipMalloc(&p->ws, p->ws_units * unit_bytes);
+        if (e == hipSuccess)
+            e = hipMalloc(&p->carry, std::max<size_t>(1, 2ull * (taps - 1) * rs));
+        if (e == hipSuccess)
+            e = hipMalloc(&p->h_dev, taps * rs);
+        if (e == hipSuccess)
+            e = hipMalloc(&p->H, 2ull * fft_n * rs);
+        if (e == hipSuccess) {
+            // coefficients and response rounded once to the plan precision (the twiddle-table convention)
+            const std::vector<double> resp = fir_fft_response(h, taps, fft_n);
+            if (precision == SDSP_HIP_F64) {
+                e = hipMemcpy(p->h_dev, h, taps * rs, hipMemcpyHostToDevice);
+                if (e == hipSuccess)
+                    e = hipMemcpy(p->H, resp.data(), resp.size() * rs, hipMemcpyHostToDevice);
+            } else {
+                const std::vector<float> hf(h, h + taps), rf(resp.begin(), resp.end());
+                e = hipMemcpy(p->h_dev, hf.data(), taps * rs, hipMemcpyHostToDevice);
+                if (e == hipSuccess)
+                    e = hipMemcpy(p->H, rf.data(), rf.size() * rs, hipMemcpyHostToDevice);
+            }
+        }
+        if (e != hipSuccess)
+            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "fir fft plan: out of device memory") : hip_fail(e, "fir fft plan");
+    }
+    if (rc) {
+        sdsp_hip_fir_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fir_plan_get_info(const sdsp_hip_fir_plan *p, sdsp_hip_fir_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->taps = p->taps;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->method = p->method;
+    info->fft_n = p->fft_n;
+    info->hop = p->hop;
+    info->workspace_bytes = p->workspace_bytes;
+    const char *name = p->method == SDSP_HIP_FIR_FFT ? select_conv(p->conv, p->conv->variant).name : "sdsp_fir_kernel";
+    std::strncpy(info->kernel, name, sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fir_plan_launches(const sdsp_hip_fir_plan *p, uint64_t channels, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (p->method != SDSP_HIP_FIR_FFT) {
+        *launches = 1;
+        return SDSP_HIP_OK;
+    }
+    uint64_t frames = 0, pairs = 0;
+    fir_fft_grid(p, samples, &frames, &pairs);
+    const uint64_t total = channels * pairs;
+    uint64_t n = 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t g1 = std::min(total, g0 + p->ws_units);
+        n += 2 + conv_launch_count(p->conv, g1 - g0);
+        if (p->taps > 1 && g1 / pairs > g0 / pairs) // a channel ends in this slice: the state launch
+            n += 1;
+    }
+    *launches = n;
     return SDSP_HIP_OK;
 }
 
@@ -1660,7 +1943,12 @@ int sdsp_hip_fir_plan_set_variant(sdsp_hip_fir_plan *p, int variant)
     if (!p || variant < 0)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
     p->variant = variant;
-    return SDSP_HIP_OK;
+    if (p->method != SDSP_HIP_FIR_FFT)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    p->conv->variant = variant;
+    return fir_fft_prepare_conv(p);
 }
 
 int sdsp_hip_fir_process(sdsp_hip_fir_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride,
@@ -1676,6 +1964,8 @@ int sdsp_hip_fir_process(sdsp_hip_fir_plan *p, void *data, uint64_t channels, ui
         return fail(SDSP_HIP_ERR_INVALID_ARG, "stride must be >= samples");
     if (int rc = use_device(p->device))
         return rc;
+    if (p->method == SDSP_HIP_FIR_FFT)
+        return fir_fft_process(p, data, channels, samples, stride, state, stream);
     fir_args a{};
     a.data = data;
     a.state = p->taps > 1 ? state : nullptr;

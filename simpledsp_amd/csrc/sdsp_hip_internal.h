@@ -220,4 +220,18 @@ struct fir_args {
     uint32_t taps;
 };
 int launch_fir(int precision, const fir_args &a, int variant, void *stream);
+
+// FFT-domain FIR plans (overlap-save, fir_fft.hip): the launches of one slice around the convolution
+enum { FIR_OS_FRAME = 0, FIR_OS_SCATTER = 1, FIR_OS_STATE = 2 };
+struct fir_os_args {
+    void *data;
+    void *state;          // nullable; channels x (taps-1), newest first
+    void *ws;             // units x n complex (frame pairs)
+    void *tails;          // staged new history: (taps-1) per channel whose last unit is in the slice; null without state
+    const void *carry_in; // the previous slice's carry (the straddling channel's taps-1 inputs), ...
+    void *carry_out;      // ... and this slice's
+    uint64_t stride, samples, frames, pairs, g0, units;
+    uint32_t n, hop, taps_m1;
+};
+int launch_fir_os(int precision, const fir_os_args &a, int step, void *stream);
 } // namespace sdsp_hip

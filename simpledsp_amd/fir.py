@@ -78,13 +78,31 @@ class fir_filter:
             self._lib.sdsp_hip_fir_plan_destroy(self._plan)
             self._plan = None
 
+    def _create_plan(self, out):
+        L.check(self._lib.sdsp_hip_fir_plan_create(out, self.n_taps, self.m_coeff.ctypes.data, self.precision, self.device))
+
     def _ensure_plan(self):
         if self._plan is None:
             h = C.c_void_p()
-            L.check(self._lib.sdsp_hip_fir_plan_create(C.byref(h), self.n_taps, self.m_coeff.ctypes.data, self.precision,
-                                                       self.device))
+            self._create_plan(C.byref(h))
             self._plan = h
             L.check(self._lib.sdsp_hip_fir_plan_set_variant(h, self._variant))
+
+    def info(self) -> dict:
+        """the plan's sdsp_hip_fir_plan_info as a dict (creates the plan)"""
+        self._ensure_plan()
+        i = L.FirPlanInfo()
+        L.check(self._lib.sdsp_hip_fir_plan_get_info(self._plan, C.byref(i)))
+        d = {name: getattr(i, name) for name, _ in i._fields_}
+        d["kernel"] = i.kernel.decode()
+        return d
+
+    def launches(self, samples: int) -> int:
+        """kernel launches one process() call of `samples` samples per channel issues"""
+        self._ensure_plan()
+        n = C.c_uint64(0)
+        L.check(self._lib.sdsp_hip_fir_plan_launches(self._plan, self.channels, samples, C.byref(n)))
+        return n.value
 
     def process(self, data, samples: int | None = None, offset: int = 0):
         """data: contiguous device tensor (channels, stride); filters data[:, offset:offset+samples] of every
@@ -114,3 +132,25 @@ class fir_filter:
             self._drop_plan()
         except Exception:
             pass
+
+
+class fft_fir_filter(fir_filter):
+    """The same bank computed in the frequency domain (overlap-save through the fused fast convolution): for long filters,
+    up to 16384 taps in f32 and 8192 in f64.  fft_n = 0 picks the FFT size, workspace_bytes = 0 the default slice budget.
+    Same design setters, state layout and process() as fir_filter; results agree within rounding, not bit for bit."""
+
+    def __init__(self, n_taps: int, channels: int = 1, precision: int = L.F32, device: int = 0, fft_n: int = 0,
+                 workspace_bytes: int = 0):
+        super().__init__(n_taps, channels, precision, device)
+        self.fft_n, self.workspace_bytes = fft_n, workspace_bytes
+
+    def _create_plan(self, out):
+        L.check(self._lib.sdsp_hip_fir_fft_plan_create(out, self.n_taps, self.m_coeff.ctypes.data, self.precision,
+                                                       self.fft_n, self.workspace_bytes, self.device))
+
+
+def fir_fft_size(n_taps: int, precision: int = L.F32) -> int:
+    """the FFT size an fft_fir_filter with fft_n = 0 uses (sdsp_hip_fir_fft_size)"""
+    n = C.c_uint32(0)
+    L.check(L.load().sdsp_hip_fir_fft_size(n_taps, precision, C.byref(n)))
+    return n.value
