@@ -388,6 +388,67 @@ int sdsp_hip_fir_plan_get_info(const sdsp_hip_fir_plan *plan, sdsp_hip_fir_plan_
 /* kernel launches one sdsp_hip_fir_process(plan, ., channels, samples, ...) with a state buffer issues (memsets not counted) */
 int sdsp_hip_fir_plan_launches(const sdsp_hip_fir_plan *plan, uint64_t channels, uint64_t samples, uint64_t *launches);
 
+/* ------------------------------------------------------------------ polyphase FIR resampler banks */
+
+/*
+ * Rate change by U / D (up factor U, down factor D, g = gcd(U, D), q = D / g) with a T-tap filter h, for `channels` independent
+ * streams, out of place.  Output m of a call, x = the history followed by the block:
+ *     y[m] = sum over k < T with (m D - k) = 0 (mod U) of h[k] x[(m D - k) / U],   m in [0, S U / D)
+ * -- the causal part of scipy.signal.upfirdn(h, x, U, D); outputs of a phase without taps (T < U) are 0.  No reference counterpart:
+ * pinned to scipy, like the FIR bank.
+ *   - samples S must be a multiple of q; every call yields exactly S U / D outputs and starts at phase 0, so block-by-block calls
+ *     equal one long call bit for bit.
+ *   - history: H = floor((T - 1) / U) inputs per channel, state[c H + j] = x_c[n-1-j] (j = 0 the newest), plan precision; read at
+ *     entry, written at exit; NULL = zero history, final history dropped.  With U = 1 this is the direct FIR plan's layout.
+ *   - each output sums exactly its own taps in ascending k: a plain multiply, then one multiply and one add per tap in f64, one
+ *     fmaf in f32 -- the values of zero-stuff -> sdsp_hip_fir_process of the same precision -> every D-th sample (signed zeros
+ *     aside).  No phase is padded with zero taps.
+ * Limits: 1 <= T <= SDSP_HIP_FIR_MAX_TAPS, 1 <= U, D <= SDSP_HIP_RESAMPLE_MAX_FACTOR.
+ */
+#define SDSP_HIP_RESAMPLE_MAX_FACTOR 1024
+typedef struct sdsp_hip_resample_plan sdsp_hip_resample_plan;
+/* anti-aliasing / anti-imaging low-pass for the ratio: Hamming-windowed sinc, cutoff 1 / (2 max(U, D)) of the intermediate rate
+ * (U times the input rate), pass-band gain U (what interpolation by U loses) -- sdsp_hip_fir_design(taps, LOW_PASS, 1 / max(U, D),
+ * 2, 0, U) == U * scipy.signal.firwin(taps, 1 / max(U, D)).  U = D = 1 (no rate change): SDSP_HIP_ERR_INVALID_ARG; taps or a factor
+ * out of range: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_resample_design(uint32_t taps, uint32_t up, uint32_t down, double *h);
+/* outputs one call of `samples` inputs per channel yields (S U / D); host only, no device needed.  samples not a multiple of q, or a
+ * factor out of range: SDSP_HIP_ERR_INVALID_SIZE; out NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_resample_out_samples(uint32_t up, uint32_t down, uint64_t samples, uint64_t *out);
+/* h: taps doubles (host), rounded to the plan precision and kept on the device.  Errors: taps, up or down out of range:
+ * SDSP_HIP_ERR_INVALID_SIZE; a null pointer or a precision other than F32 / F64: SDSP_HIP_ERR_INVALID_ARG; no device:
+ * SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_resample_plan_create(sdsp_hip_resample_plan **plan, uint32_t taps, const double *h, uint32_t up, uint32_t down,
+                                  int precision, int device);
+int sdsp_hip_resample_plan_destroy(sdsp_hip_resample_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples), never written.  out: DEVICE pointer, channel c = out[c out_stride
+ * .. + S U / D); nothing past those rows is touched.  state: DEVICE pointer or NULL (layout above).  Asynchronous on `stream`,
+ * allocates nothing (stream-capturable); one call per plan in flight.
+ * Errors: samples % q != 0: SDSP_HIP_ERR_INVALID_SIZE; null in / out, in_stride < samples or out_stride < S U / D with more
+ * than one channel, overlapping in and out ranges: SDSP_HIP_ERR_INVALID_ARG.  channels == 0 or samples == 0: nothing to do.
+ * Measured (1 MI355X, 1M channels x 4032 samples f32, 64 taps, D = 4): DESIGN.md section 5.10.
+ */
+int sdsp_hip_resample_process(sdsp_hip_resample_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_resample_process_host(sdsp_hip_resample_plan *plan, const void *host_in, uint64_t in_stride, void *host_out,
+                                   uint64_t out_stride, uint64_t channels, uint64_t samples, void *host_state);
+/* bytes of a state buffer for `channels` channels: H channels element size (0 when H = 0) */
+int sdsp_hip_resample_state_bytes(const sdsp_hip_resample_plan *plan, uint64_t channels, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = default (sdsp_resample_dec_kernel for U = 1 and D in {1, 2, 4, 8, 16},
+ * sdsp_resample_poly_kernel otherwise); 1 = sdsp_resample_plain_kernel, one output per thread from global memory (the
+ * cross-check); 2 = sdsp_resample_poly_kernel for every ratio. */
+int sdsp_hip_resample_plan_set_variant(sdsp_hip_resample_plan *plan, int variant);
+typedef struct {
+    uint32_t taps, up, down;
+    uint32_t hist;   /* H = floor((taps - 1) / up) */
+    int precision;
+    int device;
+    char kernel[64]; /* the kernel the plan's variant runs on a long contiguous row */
+} sdsp_hip_resample_plan_info;
+int sdsp_hip_resample_plan_get_info(const sdsp_hip_resample_plan *plan, sdsp_hip_resample_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, revers
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
 from .iir import casc_2o_iir, casc_2o_iir_lp, casc_2o_iir_hp, casc_2o_iir_bp
 from .fir import fir_filter, fft_fir_filter, fir_fft_size
+from .resample import fir_resampler
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

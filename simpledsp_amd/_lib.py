@@ -49,6 +49,16 @@ class FirPlanInfo(C.Structure):
 FIR_DIRECT, FIR_FFT = 0, 1
 
 
+class ResamplePlanInfo(C.Structure):
+    _fields_ = [
+        ("taps", C.c_uint32), ("up", C.c_uint32), ("down", C.c_uint32), ("hist", C.c_uint32), ("precision", C.c_int),
+        ("device", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
+RESAMPLE_MAX_FACTOR = 1024
+
+
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -108,6 +118,15 @@ SIGNATURES = {
     "sdsp_hip_fir_fft_plan_create": (_i, [_pp, _u32, _vp, _i, _u32, _u64, _i]),
     "sdsp_hip_fir_plan_get_info": (_i, [_vp, C.POINTER(FirPlanInfo)]),
     "sdsp_hip_fir_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_resample_design": (_i, [_u32, _u32, _u32, _vp]),
+    "sdsp_hip_resample_out_samples": (_i, [_u32, _u32, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_resample_plan_create": (_i, [_pp, _u32, _vp, _u32, _u32, _i, _i]),
+    "sdsp_hip_resample_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_resample_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_resample_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_resample_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_resample_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_resample_plan_get_info": (_i, [_vp, C.POINTER(ResamplePlanInfo)]),
 }
 
 _lib = None

@@ -44,6 +44,7 @@ SOURCES = {
     "iir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "fir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps: multiply then add, like the oracle
     "fir_fft.hip": [],
+    "fir_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64: multiply then add per tap, as fir.hip
 }
 
 

@@ -319,6 +319,12 @@ struct sdsp_hip_fir_plan {
     uint64_t ws_units = 0, workspace_bytes = 0;
 };
 
+struct sdsp_hip_resample_plan {
+    uint32_t taps = 0, up = 1, down = 1, q = 1, hist = 0; // q = down / gcd(up, down), hist = floor((taps - 1) / up)
+    int precision = 0, device = 0, variant = 0;
+    void *h_dev = nullptr;
+};
+
 namespace
 {
 // largest power-of-two column count whose padded tile fits the LDS budget
@@ -2014,6 +2020,188 @@ int sdsp_hip_fir_process_host(sdsp_hip_fir_plan *p, void *host_data, uint64_t ch
             rc = hip_fail(e, "fir host read-back");
     }
     (void)hipFree(d);
+    (void)hipFree(s);
+    return rc;
+}
+
+// ------------------------------------------------------------------ polyphase FIR resampler banks (fir_resample.hip)
+
+int sdsp_hip_resample_plan_create(sdsp_hip_resample_plan **out, uint32_t taps, const double *h, uint32_t up, uint32_t down,
+                                  int precision, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (taps == 0 || taps > SDSP_HIP_FIR_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_FIR_MAX_TAPS]");
+    if (up == 0 || down == 0 || up > SDSP_HIP_RESAMPLE_MAX_FACTOR || down > SDSP_HIP_RESAMPLE_MAX_FACTOR)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "up and down must be in [1, SDSP_HIP_RESAMPLE_MAX_FACTOR]");
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "coefficient pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_resample_plan();
+    uint32_t g = up, b = down;
+    while (b) {
+        const uint32_t t = g % b;
+        g = b;
+        b = t;
+    }
+    p->taps = taps;
+    p->up = up;
+    p->down = down;
+    p->q = down / g;
+    p->hist = (taps - 1) / up;
+    p->precision = precision;
+    p->device = device;
+    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    std::vector<float> hf(h, h + taps);
+    hipError_t e = hipMalloc(&p->h_dev, taps * rs);
+    if (e == hipSuccess)
+        e = hipMemcpy(p->h_dev, precision == SDSP_HIP_F64 ? static_cast<const void *>(h) : hf.data(), taps * rs, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p->h_dev);
+        delete p;
+        return hip_fail(e, "resample coefficients");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_resample_plan_destroy(sdsp_hip_resample_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->h_dev);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_resample_state_bytes(const sdsp_hip_resample_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_resample_plan_set_variant(sdsp_hip_resample_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 2)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0, 1 or 2");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_resample_plan_get_info(const sdsp_hip_resample_plan *p, sdsp_hip_resample_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->taps = p->taps;
+    info->up = p->up;
+    info->down = p->down;
+    info->hist = p->hist;
+    info->precision = p->precision;
+    info->device = p->device;
+    resample_args a{};
+    a.taps = p->taps;
+    a.up = p->up;
+    a.down = p->down;
+    a.channels = 1;
+    a.samples = 4096ull * p->q;
+    std::strncpy(info->kernel, resample_kernel_for(p->precision, a, p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_resample_process(sdsp_hip_resample_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, void *state, void *stream)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    uint64_t outs = 0;
+    if (int rc = sdsp_hip_resample_out_samples(p->up, p->down, samples, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < outs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= samples * up / down");
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + samples) * rs, o1 = o0 + ((channels - 1) * out_stride + outs) * rs;
+    if (i0 < o1 && o0 < i1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the resampler runs out of place)");
+    if (int rc = use_device(p->device))
+        return rc;
+    resample_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = p->hist ? state : nullptr;
+    a.h = p->h_dev;
+    a.channels = channels;
+    a.samples = samples;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.taps = p->taps;
+    a.up = p->up;
+    a.down = p->down;
+    return launch_resample(p->precision, a, p->variant, stream);
+}
+
+int sdsp_hip_resample_process_host(sdsp_hip_resample_plan *p, const void *host_in, uint64_t in_stride, void *host_out,
+                                   uint64_t out_stride, uint64_t channels, uint64_t samples, void *host_state)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    uint64_t outs = 0;
+    if (int rc = sdsp_hip_resample_out_samples(p->up, p->down, samples, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!host_in || !host_out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < outs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= samples * up / down");
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
+    const size_t out_bytes = ((channels - 1) * out_stride + outs) * rs;
+    uint64_t state_bytes = 0;
+    sdsp_hip_resample_state_bytes(p, channels, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    void *di = nullptr, *dout = nullptr, *s = nullptr;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&di, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&dout, out_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) // rows of out past S U / D keep what the caller had there
+        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && with_state) {
+        e = hipMalloc(&s, state_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+        rc = hip_fail(e, "resample host staging");
+    if (!rc)
+        rc = sdsp_hip_resample_process(p, di, in_stride, dout, out_stride, channels, samples, s, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_state)
+            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "resample host read-back");
+    }
+    (void)hipFree(di);
+    (void)hipFree(dout);
     (void)hipFree(s);
     return rc;
 }

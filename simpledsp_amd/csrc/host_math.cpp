@@ -347,4 +347,32 @@ int sdsp_hip_iir_preload(uint32_t m, int filter_type, const double *a, const dou
 {
     return preload(m, filter_type, a, b, gain, value, mem);
 }
+int sdsp_hip_resample_design(uint32_t taps, uint32_t up, uint32_t down, double *h)
+{
+    if (up == 0 || down == 0 || up > SDSP_HIP_RESAMPLE_MAX_FACTOR || down > SDSP_HIP_RESAMPLE_MAX_FACTOR)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "up and down must be in [1, SDSP_HIP_RESAMPLE_MAX_FACTOR]");
+    if (up == 1 && down == 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "up = down = 1 changes no rate: there is no band to protect");
+    const uint32_t r = up > down ? up : down;
+    return design_fir(taps, SDSP_HIP_FILTER_LOW_PASS, 1.0 / r, 2.0, 0.0, static_cast<double>(up), h);
+}
+int sdsp_hip_resample_out_samples(uint32_t up, uint32_t down, uint64_t samples, uint64_t *out)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *out = 0;
+    if (up == 0 || down == 0 || up > SDSP_HIP_RESAMPLE_MAX_FACTOR || down > SDSP_HIP_RESAMPLE_MAX_FACTOR)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "up and down must be in [1, SDSP_HIP_RESAMPLE_MAX_FACTOR]");
+    uint32_t a = up, b = down;
+    while (b) {
+        const uint32_t t = a % b;
+        a = b;
+        b = t;
+    }
+    const uint32_t q = down / a;
+    if (samples % q)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be a multiple of down / gcd(up, down)");
+    *out = samples / q * (up / a);
+    return SDSP_HIP_OK;
+}
 }

@@ -234,4 +234,17 @@ struct fir_os_args {
     uint32_t n, hop, taps_m1;
 };
 int launch_fir_os(int precision, const fir_os_args &a, int step, void *stream);
+
+// polyphase FIR resampler banks (fir_resample.hip): up by `up`, filter, down by `down`, out of place
+struct resample_args {
+    const void *in;
+    void *out;
+    void *state;   // nullable; channels x floor((taps-1)/up), newest first
+    const void *h; // device, plan precision, `taps` values
+    uint64_t channels, samples, in_stride, out_stride; // samples: a multiple of down / gcd(up, down)
+    uint32_t taps, up, down;
+};
+int launch_resample(int precision, const resample_args &a, int variant, void *stream);
+// the kernel launch_resample runs for this shape and variant (the same selection function)
+const char *resample_kernel_for(int precision, const resample_args &a, int variant);
 } // namespace sdsp_hip
