@@ -449,6 +449,78 @@ typedef struct {
 } sdsp_hip_resample_plan_info;
 int sdsp_hip_resample_plan_get_info(const sdsp_hip_resample_plan *plan, sdsp_hip_resample_plan_info *info);
 
+/* ------------------------------------------------------------------ STFT banks */
+
+/*
+ * Short-time Fourier transform of `channels` independent real streams.  N = n_fft (a power of two in the
+ * radix-2 real-input range: f32 32 .. 65536, f64 32 .. 32768), 1 <= hop <= N, hist = N - hop, bins = N / 2 + 1.  A call takes
+ * S samples per channel, S a multiple of hop, and writes exactly F = S / hop frames.  With x = the channel's history followed by
+ * the block (the block starts at index hist), frame j of the call is
+ *     out[c out_stride + j bins + k] = sum over n < N of fl(x[j hop + n] w[n]) e^(-2 pi i k n / N),   0 <= k <= N / 2
+ * -- the np.fft.rfft sign, no scaling; torch.stft(concat(history, block), N, hop, window = w, center = False) in frame-major order.
+ * A fresh stream (NULL or zeroed state) is the stream with hist zeros in front of it.
+ *   - history: state[c hist + j] = x_c[-1 - j] (newest first), plan precision; read at entry, written at exit; NULL = zero history,
+ *     final history dropped (the FIR and resampler layout).  hop = N: hist = 0, no state.
+ *   - block-by-block calls equal one long call bit for bit, for any split into multiples of hop (blocks shorter than hist included).
+ *   - the window: N host doubles, rounded once to the plan precision at creation; every windowed sample is one rounding of x w.
+ *   - output kinds: COMPLEX = interleaved complex of the plan precision; POWER = re re + im im in the plan precision (two products
+ *     and a sum, no FMA contraction); MAGNITUDE = sqrt of the power.  Bins 0 and N / 2 have zero imaginary parts.
+ *   - strides count elements (a complex bin is one element).  `in` is never written; nothing past each channel's F bins outputs is.
+ * A call runs in slices of the plan's workspace: windowed frames -> the library's forward real-input transform (unchanged) -> the
+ * output rows, then one launch for the new history.
+ */
+#define SDSP_HIP_STFT_COMPLEX 0
+#define SDSP_HIP_STFT_POWER 1
+#define SDSP_HIP_STFT_MAGNITUDE 2
+#define SDSP_HIP_WINDOW_RECT 0
+#define SDSP_HIP_WINDOW_HANN 1
+#define SDSP_HIP_WINDOW_HAMMING 2
+#define SDSP_HIP_WINDOW_BLACKMAN 3
+typedef struct sdsp_hip_stft_plan sdsp_hip_stft_plan;
+/* periodic window of n points (scipy.signal.get_window(name, n), fftbins = True), host only: RECT 1; HANN 0.5 - 0.5 cos(2 pi k / n);
+ * HAMMING 0.54 - 0.46 cos(2 pi k / n); BLACKMAN 0.42 - 0.5 cos(2 pi k / n) + 0.08 cos(4 pi k / n).  Unknown kind or w NULL:
+ * SDSP_HIP_ERR_INVALID_ARG; n = 0: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_stft_window(int kind, uint32_t n, double *w);
+/* frames one call of `samples` per channel writes (samples / hop); host only.  hop = 0 or samples % hop != 0:
+ * SDSP_HIP_ERR_INVALID_SIZE; frames NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_stft_frames(uint32_t hop, uint64_t samples, uint64_t *frames);
+/* window: n_fft host doubles.  workspace_bytes: the slice budget (0 = the default); a slice holds at least
+ * one frame.  Errors: n_fft not a power of two, hop = 0 or hop > n_fft: SDSP_HIP_ERR_INVALID_SIZE; n_fft outside the real-input
+ * range of the precision: SDSP_HIP_ERR_UNSUPPORTED; a null pointer, a precision other than F32 / F64 or an unknown output kind:
+ * SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_stft_plan_create(sdsp_hip_stft_plan **plan, uint32_t n_fft, uint32_t hop, const double *window, int output,
+                              int precision, uint64_t workspace_bytes, int device);
+int sdsp_hip_stft_plan_destroy(sdsp_hip_stft_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples).  out: DEVICE pointer, channel c = out[c out_stride .. + F bins)
+ * elements.  state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one call per plan
+ * in flight.  Errors: samples % hop != 0: SDSP_HIP_ERR_INVALID_SIZE; null in / out, in_stride < samples or out_stride < F bins
+ * with more than one channel, overlapping in and out ranges: SDSP_HIP_ERR_INVALID_ARG.  channels == 0 or samples == 0: nothing
+ * to do.  Measured (1 MI355X, 1024 channels x 2^18 samples f32, N = 1024, hop = 256): power 4.25 ms against 8.60 ms for
+ * unfold x window -> rfft -> unpack -> |X|^2 (2.02x) and 10.6 ms for torch.stft (2.50x); complex 4.64 ms (1.16x / 1.62x).
+ * DESIGN.md section 5.11.
+ */
+int sdsp_hip_stft_process(sdsp_hip_stft_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                          uint64_t channels, uint64_t samples, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_stft_process_host(sdsp_hip_stft_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                               uint64_t channels, uint64_t samples, void *host_state);
+/* bytes of a state buffer for `channels` channels: hist channels element size (0 when hop = n_fft) */
+int sdsp_hip_stft_state_bytes(const sdsp_hip_stft_plan *plan, uint64_t channels, uint64_t *bytes);
+/* the kernel variant of the inner real-input plan (sdsp_hip_fft_plan_set_variant of an rfft plan of n_real = n_fft, radix 2);
+ * SDSP_HIP_ERR_UNSUPPORTED where that plan has no such variant */
+int sdsp_hip_stft_plan_set_variant(sdsp_hip_stft_plan *plan, int variant);
+/* kernel launches of one process call of `samples` per channel with a state buffer (frame, transform and emit launches per slice,
+ * plus the state launch when hist > 0) */
+int sdsp_hip_stft_plan_launches(const sdsp_hip_stft_plan *plan, uint64_t channels, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t n_fft, hop, bins, hist;
+    int output, precision, device;
+    uint64_t workspace_bytes;
+    char kernel[64]; /* the inner transform's kernel */
+} sdsp_hip_stft_plan_info;
+int sdsp_hip_stft_plan_get_info(const sdsp_hip_stft_plan *plan, sdsp_hip_stft_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

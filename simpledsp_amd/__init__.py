@@ -12,6 +12,7 @@ from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, revers
 from .iir import casc_2o_iir, casc_2o_iir_lp, casc_2o_iir_hp, casc_2o_iir_bp
 from .fir import fir_filter, fft_fir_filter, fir_fft_size
 from .resample import fir_resampler
+from .stft import stft_bank, stft_window
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

@@ -59,6 +59,17 @@ class ResamplePlanInfo(C.Structure):
 RESAMPLE_MAX_FACTOR = 1024
 
 
+class StftPlanInfo(C.Structure):
+    _fields_ = [
+        ("n_fft", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32), ("output", C.c_int),
+        ("precision", C.c_int), ("device", C.c_int), ("workspace_bytes", C.c_uint64), ("kernel", C.c_char * 64),
+    ]
+
+
+STFT_COMPLEX, STFT_POWER, STFT_MAGNITUDE = 0, 1, 2
+WINDOW_RECT, WINDOW_HANN, WINDOW_HAMMING, WINDOW_BLACKMAN = 0, 1, 2, 3
+
+
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -127,6 +138,16 @@ SIGNATURES = {
     "sdsp_hip_resample_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_resample_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_resample_plan_get_info": (_i, [_vp, C.POINTER(ResamplePlanInfo)]),
+    "sdsp_hip_stft_window": (_i, [_i, _u32, _vp]),
+    "sdsp_hip_stft_frames": (_i, [_u32, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_stft_plan_create": (_i, [_pp, _u32, _u32, _vp, _i, _i, _u64, _i]),
+    "sdsp_hip_stft_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_stft_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_stft_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_stft_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_stft_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_stft_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_stft_plan_get_info": (_i, [_vp, C.POINTER(StftPlanInfo)]),
 }
 
 _lib = None

@@ -45,6 +45,7 @@ SOURCES = {
     "fir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps: multiply then add, like the oracle
     "fir_fft.hip": [],
     "fir_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64: multiply then add per tap, as fir.hip
+    "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
 }
 
 

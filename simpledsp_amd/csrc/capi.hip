@@ -325,6 +325,15 @@ struct sdsp_hip_resample_plan {
     void *h_dev = nullptr;
 };
 
+struct sdsp_hip_stft_plan {
+    uint32_t n = 0, hop = 0, hist = 0, bins = 0; // hist = n - hop, bins = n / 2 + 1
+    int output = 0, precision = 0, device = 0;
+    sdsp_hip_fft_plan *inner = nullptr; // forward real-input plan of n_real = n, radix 2; its variant is the plan's
+    void *window = nullptr;             // n values, plan precision
+    void *ws = nullptr;                 // ws_units x n reals: the slice's frames, transformed in place
+    uint64_t ws_units = 0, workspace_bytes = 0;
+};
+
 namespace
 {
 // largest power-of-two column count whose padded tile fits the LDS budget
@@ -2199,6 +2208,276 @@ int sdsp_hip_resample_process_host(sdsp_hip_resample_plan *p, const void *host_i
             e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             rc = hip_fail(e, "resample host read-back");
+    }
+    (void)hipFree(di);
+    (void)hipFree(dout);
+    (void)hipFree(s);
+    return rc;
+}
+
+// ------------------------------------------------------------------ STFT banks (stft.hip)
+
+namespace
+{
+// windowed frames of one slice (transformed in place).  Measured (tools/bench_stft.py), f32 N = 1024,
+// hop = 256, complex, 1 GiB in: 16 / 64 / 128 / 256 / 512 / 1024 MiB 7.73 / 4.87 / 4.73 / 4.64 / 4.62 / 4.64 ms -- flat from 256 MiB on
+constexpr uint64_t kStftDefaultBudget = 256ull << 20;
+
+uint32_t stft_max_n(int precision) { return precision == SDSP_HIP_F64 ? 32768u : 65536u; }
+
+int stft_run(sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+             uint64_t samples, void *state, hipStream_t stream)
+{
+    const uint64_t frames = samples / p->hop;
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames per channel for one call");
+    if (channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * frames;
+    stft_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = p->hist ? state : nullptr;
+    a.window = p->window;
+    a.ws = p->ws;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.channels = channels;
+    a.samples = samples;
+    a.frames = static_cast<uint32_t>(frames);
+    a.n = p->n;
+    a.hop = p->hop;
+    a.hist = p->hist;
+    a.output = p->output;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        a.g0 = g0;
+        a.units = static_cast<uint32_t>(std::min(p->ws_units, total - g0));
+        if (int rc = launch_stft(p->precision, a, STFT_FRAME, stream))
+            return rc;
+        if (int rc = fft_exec_pieces(p->inner, p->ws, a.units, stream, p->inner->variant))
+            return rc;
+        if (int rc = launch_stft(p->precision, a, STFT_EMIT, stream))
+            return rc;
+    }
+    return launch_stft(p->precision, a, STFT_STATE, stream); // after every frame launch: they may read the old history
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int stft_check(const sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride,
+               uint64_t channels, uint64_t samples, uint64_t *frames)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (int rc = sdsp_hip_stft_frames(p->hop, samples, frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < *frames * p->bins))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= frames * bins");
+    return SDSP_HIP_OK;
+}
+
+uint64_t stft_out_esize(const sdsp_hip_stft_plan *p)
+{
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    return p->output == SDSP_HIP_STFT_COMPLEX ? 2 * rs : rs;
+}
+} // namespace
+
+int sdsp_hip_stft_plan_create(sdsp_hip_stft_plan **out, uint32_t n_fft, uint32_t hop, const double *window, int output,
+                              int precision, uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (!sdsp_hip_is_power_of_2(n_fft))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
+    if (hop == 0 || hop > n_fft)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
+    if (!window)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (output != SDSP_HIP_STFT_COMPLEX && output != SDSP_HIP_STFT_POWER && output != SDSP_HIP_STFT_MAGNITUDE)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "output must be SDSP_HIP_STFT_COMPLEX, _POWER or _MAGNITUDE");
+    if (n_fft < 32 || n_fft > stft_max_n(precision))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    if (int rc = use_device(device))
+        return rc;
+    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t unit_bytes = static_cast<uint64_t>(n_fft) * rs;
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kStftDefaultBudget;
+    auto *p = new sdsp_hip_stft_plan();
+    p->n = n_fft;
+    p->hop = hop;
+    p->hist = n_fft - hop;
+    p->bins = n_fft / 2 + 1;
+    p->output = output;
+    p->precision = precision;
+    p->device = device;
+    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->workspace_bytes = p->ws_units * unit_bytes;
+    int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device, 1);
+    if (!rc) {
+        hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
+        if (e == hipSuccess)
+            e = hipMalloc(&p->window, n_fft * rs);
+        if (e == hipSuccess) { // rounded once to the plan precision
+            if (precision == SDSP_HIP_F64) {
+                e = hipMemcpy(p->window, window, n_fft * rs, hipMemcpyHostToDevice);
+            } else {
+                const std::vector<float> wf(window, window + n_fft);
+                e = hipMemcpy(p->window, wf.data(), n_fft * rs, hipMemcpyHostToDevice);
+            }
+        }
+        if (e != hipSuccess)
+            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "stft plan: out of device memory") : hip_fail(e, "stft plan");
+    }
+    if (rc) {
+        sdsp_hip_stft_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_stft_plan_destroy(sdsp_hip_stft_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->ws);
+        (void)hipFree(p->window);
+    }
+    if (p->inner)
+        sdsp_hip_fft_plan_destroy(p->inner);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_stft_state_bytes(const sdsp_hip_stft_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_stft_plan_set_variant(sdsp_hip_stft_plan *p, int variant)
+{
+    if (!p || variant < 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
+    // rejected here rather than at the next process call: a variant without a kernel, or whose kernel needs a table this size's
+    // plan does not upload
+    const fft_kernel_sel sel = select_kernel(p->inner, variant);
+    if (sel.id == K_UNSUPPORTED)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the inner real-input plan has no such kernel variant");
+    if (int rc = check_table(p->inner, sel))
+        return rc;
+    p->inner->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_stft_plan_get_info(const sdsp_hip_stft_plan *p, sdsp_hip_stft_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->n_fft = p->n;
+    info->hop = p->hop;
+    info->bins = p->bins;
+    info->hist = p->hist;
+    info->output = p->output;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->workspace_bytes = p->workspace_bytes;
+    std::strncpy(info->kernel, select_kernel(p->inner, p->inner->variant).name, sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_stft_plan_launches(const sdsp_hip_stft_plan *p, uint64_t channels, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_stft_frames(p->hop, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t total = channels * frames;
+    uint64_t n = 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t units = std::min(p->ws_units, total - g0);
+        n += 2 + fft_launch_count(p->inner, units, p->inner->variant);
+    }
+    *launches = n + (p->hist ? 1 : 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_stft_process(sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                          uint64_t samples, void *state, void *stream)
+{
+    uint64_t frames = 0;
+    if (int rc = stft_check(p, in, in_stride, out, out_stride, channels, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + samples) * rs;
+    const uintptr_t o1 = o0 + ((channels - 1) * out_stride + frames * p->bins) * stft_out_esize(p);
+    if (i0 < o1 && o0 < i1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the STFT runs out of place)");
+    if (i0 % rs || o0 % stft_out_esize(p) || reinterpret_cast<uintptr_t>(state) % rs)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return stft_run(p, in, in_stride, out, out_stride, channels, samples, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_stft_process_host(sdsp_hip_stft_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                               uint64_t channels, uint64_t samples, void *host_state)
+{
+    uint64_t frames = 0;
+    if (int rc = stft_check(p, host_in, in_stride, host_out, out_stride, channels, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
+    const size_t out_bytes = ((channels - 1) * out_stride + frames * p->bins) * stft_out_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_stft_state_bytes(p, channels, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    void *di = nullptr, *dout = nullptr, *s = nullptr;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&di, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&dout, out_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) // rows of out past F bins keep what the caller had there
+        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && with_state) {
+        e = hipMalloc(&s, state_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+        rc = hip_fail(e, "stft host staging");
+    if (!rc)
+        rc = stft_run(p, di, in_stride, dout, out_stride, channels, samples, s, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_state)
+            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "stft host read-back");
     }
     (void)hipFree(di);
     (void)hipFree(dout);

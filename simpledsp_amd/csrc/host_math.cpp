@@ -375,4 +375,37 @@ int sdsp_hip_resample_out_samples(uint32_t up, uint32_t down, uint64_t samples, 
     *out = samples / q * (up / a);
     return SDSP_HIP_OK;
 }
+int sdsp_hip_stft_window(int kind, uint32_t n, double *w)
+{
+    if (!w)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    if (kind < SDSP_HIP_WINDOW_RECT || kind > SDSP_HIP_WINDOW_BLACKMAN)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window kind must be SDSP_HIP_WINDOW_RECT / HANN / HAMMING / BLACKMAN");
+    if (n == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "a window needs at least one point");
+    // periodic (scipy fftbins = True): the first n points of the symmetric window of n + 1
+    const double two_pi = 2 * M_PI;
+    for (uint32_t k = 0; k < n; k++) {
+        const double c1 = std::cos(two_pi * k / n);
+        switch (kind) {
+        case SDSP_HIP_WINDOW_RECT: w[k] = 1.0; break;
+        case SDSP_HIP_WINDOW_HANN: w[k] = 0.5 - 0.5 * c1; break;
+        case SDSP_HIP_WINDOW_HAMMING: w[k] = 0.54 - 0.46 * c1; break;
+        default: w[k] = 0.42 - 0.5 * c1 + 0.08 * std::cos(2.0 * two_pi * k / n); break;
+        }
+    }
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_stft_frames(uint32_t hop, uint64_t samples, uint64_t *frames)
+{
+    if (!frames)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *frames = 0;
+    if (hop == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be >= 1");
+    if (samples % hop)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be a multiple of hop");
+    *frames = samples / hop;
+    return SDSP_HIP_OK;
+}
 }

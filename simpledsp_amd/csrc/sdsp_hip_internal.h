@@ -247,4 +247,18 @@ struct resample_args {
 int launch_resample(int precision, const resample_args &a, int variant, void *stream);
 // the kernel launch_resample runs for this shape and variant (the same selection function)
 const char *resample_kernel_for(int precision, const resample_args &a, int variant);
+// STFT banks (stft.hip): the launches of one slice around the plan's real-input transform, and the state launch
+enum { STFT_FRAME = 0, STFT_EMIT = 1, STFT_STATE = 2 };
+struct stft_args {
+    const void *in;
+    void *out;
+    void *state;        // nullable; channels x hist, newest first
+    const void *window; // device, plan precision, n values
+    void *ws;           // units x n reals (windowed frames, then their packed half spectra)
+    uint64_t in_stride, out_stride, channels, samples;
+    uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, frame) numbering
+    uint32_t units, frames, n, hop, hist;
+    int output;         // SDSP_HIP_STFT_*
+};
+int launch_stft(int precision, const stft_args &a, int step, void *stream);
 } // namespace sdsp_hip
