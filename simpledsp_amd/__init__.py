@@ -13,6 +13,7 @@ from .iir import casc_2o_iir, casc_2o_iir_lp, casc_2o_iir_hp, casc_2o_iir_bp
 from .fir import fir_filter, fft_fir_filter, fir_fft_size
 from .resample import fir_resampler
 from .stft import stft_bank, stft_window
+from .istft import istft_bank, synthesis_window as istft_synthesis_window
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

@@ -70,6 +70,17 @@ STFT_COMPLEX, STFT_POWER, STFT_MAGNITUDE = 0, 1, 2
 WINDOW_RECT, WINDOW_HANN, WINDOW_HAMMING, WINDOW_BLACKMAN = 0, 1, 2, 3
 
 
+class IstftPlanInfo(C.Structure):
+    _fields_ = [
+        ("n_fft", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32), ("norm", C.c_int),
+        ("precision", C.c_int), ("device", C.c_int), ("workspace_bytes", C.c_uint64), ("kernel", C.c_char * 64),
+        ("env_min", C.c_double), ("env_max", C.c_double),
+    ]
+
+
+ISTFT_NORMALIZED, ISTFT_RAW = 0, 1
+
+
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -148,6 +159,15 @@ SIGNATURES = {
     "sdsp_hip_stft_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_stft_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_stft_plan_get_info": (_i, [_vp, C.POINTER(StftPlanInfo)]),
+    "sdsp_hip_istft_synthesis_window": (_i, [_u32, _u32, _vp, _i, _vp]),
+    "sdsp_hip_istft_plan_create": (_i, [_pp, _u32, _u32, _vp, _i, _i, _u64, _i]),
+    "sdsp_hip_istft_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_istft_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_istft_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_istft_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_istft_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_istft_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_istft_plan_get_info": (_i, [_vp, C.POINTER(IstftPlanInfo)]),
 }
 
 _lib = None

@@ -334,6 +334,16 @@ struct sdsp_hip_stft_plan {
     uint64_t ws_units = 0, workspace_bytes = 0;
 };
 
+struct sdsp_hip_istft_plan {
+    uint32_t n = 0, hop = 0, hist = 0, bins = 0; // hist = n - hop, bins = n / 2 + 1
+    int norm = 0, precision = 0, device = 0;
+    sdsp_hip_fft_plan *inner = nullptr; // reverse real-input plan of n_real = n, radix 2; its variant is the plan's
+    void *g = nullptr;                  // the synthesis window: n values, plan precision
+    void *ws = nullptr;                 // ws_units x n reals: the slice's packed spectra, transformed in place
+    uint64_t ws_units = 0, workspace_bytes = 0;
+    double env_min = 0, env_max = 0;
+};
+
 namespace
 {
 // largest power-of-two column count whose padded tile fits the LDS budget
@@ -2478,6 +2488,269 @@ int sdsp_hip_stft_process_host(sdsp_hip_stft_plan *p, const void *host_in, uint6
             e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             rc = hip_fail(e, "stft host read-back");
+    }
+    (void)hipFree(di);
+    (void)hipFree(dout);
+    (void)hipFree(s);
+    return rc;
+}
+
+// ------------------------------------------------------------------ inverse STFT banks (istft.hip)
+
+namespace
+{
+// packed spectra of one slice (transformed in place): the STFT bank's budget, whose workspace round trip per frame is the same
+// 4 N rs (DESIGN.md section 5.12 has the sweep)
+constexpr uint64_t kIstftDefaultBudget = 256ull << 20;
+
+int istft_run(sdsp_hip_istft_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+              uint64_t frames, void *state, hipStream_t stream)
+{
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames per channel for one call");
+    if (channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * frames;
+    istft_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = p->hist ? state : nullptr;
+    a.g = p->g;
+    a.ws = p->ws;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.channels = channels;
+    a.frames = static_cast<uint32_t>(frames);
+    a.n = p->n;
+    a.hop = p->hop;
+    a.hist = p->hist;
+    // before every overlap-add launch: those write the new pending sums where the old ones were
+    if (int rc = launch_istft(p->precision, a, ISTFT_SEED, stream))
+        return rc;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        a.g0 = g0;
+        a.units = static_cast<uint32_t>(std::min(p->ws_units, total - g0));
+        if (int rc = launch_istft(p->precision, a, ISTFT_PACK, stream))
+            return rc;
+        if (int rc = fft_exec_pieces(p->inner, p->ws, a.units, stream, p->inner->variant))
+            return rc;
+        if (int rc = launch_istft(p->precision, a, ISTFT_OLA, stream))
+            return rc;
+    }
+    return SDSP_HIP_OK;
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int istft_check(const sdsp_hip_istft_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride,
+                uint64_t channels, uint64_t frames)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (frames > ~0ull / p->n)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    if (channels > 1 && (in_stride < frames * p->bins || out_stride < frames * p->hop))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= frames * bins and out_stride >= frames * hop");
+    return SDSP_HIP_OK;
+}
+} // namespace
+
+int sdsp_hip_istft_plan_create(sdsp_hip_istft_plan **out, uint32_t n_fft, uint32_t hop, const double *window, int norm, int precision,
+                               uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (!sdsp_hip_is_power_of_2(n_fft))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
+    if (hop == 0 || hop > n_fft)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
+    if (!window)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (n_fft < 32 || n_fft > stft_max_n(precision))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    std::vector<double> g(n_fft);
+    double env_min = 0, env_max = 0;
+    if (int rc = istft_synthesis(n_fft, hop, window, norm, g.data(), &env_min, &env_max))
+        return rc;
+    if (int rc = use_device(device))
+        return rc;
+    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t unit_bytes = static_cast<uint64_t>(n_fft) * rs;
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kIstftDefaultBudget;
+    auto *p = new sdsp_hip_istft_plan();
+    p->n = n_fft;
+    p->hop = hop;
+    p->hist = n_fft - hop;
+    p->bins = n_fft / 2 + 1;
+    p->norm = norm;
+    p->precision = precision;
+    p->device = device;
+    p->env_min = env_min;
+    p->env_max = env_max;
+    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->workspace_bytes = p->ws_units * unit_bytes;
+    int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_REVERSE, precision, p->ws_units, device, 2);
+    if (!rc) {
+        hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
+        if (e == hipSuccess)
+            e = hipMalloc(&p->g, n_fft * rs);
+        if (e == hipSuccess) { // rounded once to the plan precision
+            if (precision == SDSP_HIP_F64) {
+                e = hipMemcpy(p->g, g.data(), n_fft * rs, hipMemcpyHostToDevice);
+            } else {
+                const std::vector<float> gf(g.begin(), g.end());
+                e = hipMemcpy(p->g, gf.data(), n_fft * rs, hipMemcpyHostToDevice);
+            }
+        }
+        if (e != hipSuccess)
+            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "istft plan: out of device memory") : hip_fail(e, "istft plan");
+    }
+    if (rc) {
+        sdsp_hip_istft_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_istft_plan_destroy(sdsp_hip_istft_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->ws);
+        (void)hipFree(p->g);
+    }
+    if (p->inner)
+        sdsp_hip_fft_plan_destroy(p->inner);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_istft_state_bytes(const sdsp_hip_istft_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_istft_plan_set_variant(sdsp_hip_istft_plan *p, int variant)
+{
+    if (!p || variant < 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
+    const fft_kernel_sel sel = select_kernel(p->inner, variant);
+    if (sel.id == K_UNSUPPORTED)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the inner real-input plan has no such kernel variant");
+    if (int rc = check_table(p->inner, sel))
+        return rc;
+    p->inner->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_istft_plan_get_info(const sdsp_hip_istft_plan *p, sdsp_hip_istft_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->n_fft = p->n;
+    info->hop = p->hop;
+    info->bins = p->bins;
+    info->hist = p->hist;
+    info->norm = p->norm;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->workspace_bytes = p->workspace_bytes;
+    std::strncpy(info->kernel, select_kernel(p->inner, p->inner->variant).name, sizeof(info->kernel) - 1);
+    info->env_min = p->env_min;
+    info->env_max = p->env_max;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_istft_plan_launches(const sdsp_hip_istft_plan *p, uint64_t channels, uint64_t frames, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    if (channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * frames;
+    uint64_t n = p->hist ? 1 : 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t units = std::min(p->ws_units, total - g0);
+        n += 2 + fft_launch_count(p->inner, units, p->inner->variant);
+    }
+    *launches = n;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_istft_process(sdsp_hip_istft_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                           uint64_t frames, void *state, void *stream)
+{
+    if (int rc = istft_check(p, in, in_stride, out, out_stride, channels, frames))
+        return rc;
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + frames * p->bins) * 2 * rs;
+    const uintptr_t o1 = o0 + ((channels - 1) * out_stride + frames * p->hop) * rs;
+    if (i0 < o1 && o0 < i1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the inverse STFT runs out of place)");
+    if (i0 % (2 * rs) || o0 % rs || reinterpret_cast<uintptr_t>(state) % rs)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return istft_run(p, in, in_stride, out, out_stride, channels, frames, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_istft_process_host(sdsp_hip_istft_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                                uint64_t channels, uint64_t frames, void *host_state)
+{
+    if (int rc = istft_check(p, host_in, in_stride, host_out, out_stride, channels, frames))
+        return rc;
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t in_bytes = ((channels - 1) * in_stride + frames * p->bins) * 2 * rs;
+    const size_t out_bytes = ((channels - 1) * out_stride + frames * p->hop) * rs;
+    uint64_t state_bytes = 0;
+    sdsp_hip_istft_state_bytes(p, channels, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    void *di = nullptr, *dout = nullptr, *s = nullptr;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&di, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&dout, out_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) // rows of out past F hop keep what the caller had there
+        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && with_state) {
+        e = hipMalloc(&s, state_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+        rc = hip_fail(e, "istft host staging");
+    if (!rc)
+        rc = istft_run(p, di, in_stride, dout, out_stride, channels, frames, s, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_state)
+            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "istft host read-back");
     }
     (void)hipFree(di);
     (void)hipFree(dout);

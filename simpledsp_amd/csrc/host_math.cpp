@@ -3,6 +3,7 @@
 // filter preload.  Double precision, runs once per plan / per filter.
 #include "sdsp_hip_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstring>
@@ -261,6 +262,37 @@ int preload(uint32_t m, int filter_type, const double *a, const double *b, doubl
     }
     return SDSP_HIP_OK;
 }
+// inverse STFT synthesis window: env[r] = sum over ascending k of w[r + k hop]^2, in double
+int istft_synthesis(uint32_t n, uint32_t hop, const double *w, int norm, double *g, double *env_min, double *env_max)
+{
+    if (!sdsp_hip_is_power_of_2(n))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
+    if (hop == 0 || hop > n)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
+    if (!w || !g)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window or output pointer is null");
+    if (norm != SDSP_HIP_ISTFT_NORMALIZED && norm != SDSP_HIP_ISTFT_RAW)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "norm must be SDSP_HIP_ISTFT_NORMALIZED or SDSP_HIP_ISTFT_RAW");
+    std::vector<double> env(hop, 0.0);
+    for (uint32_t i = 0; i < n; i++) // i ascending: each env[r] sums its k in ascending order
+        env[i % hop] += w[i] * w[i];
+    double lo = env[0], hi = env[0];
+    for (uint32_t r = 1; r < hop; r++) {
+        lo = std::min(lo, env[r]);
+        hi = std::max(hi, env[r]);
+    }
+    if (env_min)
+        *env_min = lo;
+    if (env_max)
+        *env_max = hi;
+    if (norm == SDSP_HIP_ISTFT_NORMALIZED && !(lo > 1e-10 * hi))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the window breaks the NOLA condition at this hop (min of the squared-window overlap-add "
+                                              "<= 1e-10 x its max): overlap-add cannot be normalised; use a shorter hop, another "
+                                              "window or SDSP_HIP_ISTFT_RAW");
+    for (uint32_t i = 0; i < n; i++)
+        g[i] = norm == SDSP_HIP_ISTFT_RAW ? w[i] : w[i] / env[i % hop];
+    return SDSP_HIP_OK;
+}
 } // namespace sdsp_hip
 
 using namespace sdsp_hip;
@@ -407,5 +439,9 @@ int sdsp_hip_stft_frames(uint32_t hop, uint64_t samples, uint64_t *frames)
         return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be a multiple of hop");
     *frames = samples / hop;
     return SDSP_HIP_OK;
+}
+int sdsp_hip_istft_synthesis_window(uint32_t n_fft, uint32_t hop, const double *window, int norm, double *g)
+{
+    return istft_synthesis(n_fft, hop, window, norm, g, nullptr, nullptr);
 }
 }

@@ -261,4 +261,20 @@ struct stft_args {
     int output;         // SDSP_HIP_STFT_*
 };
 int launch_stft(int precision, const stft_args &a, int step, void *stream);
+// inverse STFT banks (istft.hip): the launch that consumes the old pending sums, and the launches of one
+// slice around the plan's reverse real-input transform
+enum { ISTFT_SEED = 0, ISTFT_PACK = 1, ISTFT_OLA = 2 };
+struct istft_args {
+    const void *in;     // complex bins, plan precision
+    void *out;
+    void *state;        // nullable; channels x hist, time order
+    const void *g;      // device, plan precision, n values: the synthesis window
+    void *ws;           // units x n reals (packed half spectra, then their frames)
+    uint64_t in_stride, out_stride, channels;
+    uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, frame) numbering
+    uint32_t units, frames, n, hop, hist;
+};
+int launch_istft(int precision, const istft_args &a, int step, void *stream);
+// host_math.cpp: the synthesis window (n doubles) and the range of env[r] = sum_k w[r + k hop]^2; NOLA is checked for NORMALIZED
+int istft_synthesis(uint32_t n, uint32_t hop, const double *w, int norm, double *g, double *env_min, double *env_max);
 } // namespace sdsp_hip
