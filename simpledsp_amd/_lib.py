@@ -81,6 +81,17 @@ class IstftPlanInfo(C.Structure):
 ISTFT_NORMALIZED, ISTFT_RAW = 0, 1
 
 
+class FiltfiltPlanInfo(C.Structure):
+    _fields_ = [
+        ("sections", C.c_uint32), ("padlen", C.c_uint32), ("kind", C.c_int), ("padtype", C.c_int), ("precision", C.c_int),
+        ("device", C.c_int), ("variant", C.c_int), ("workspace_bytes", C.c_uint64), ("slice_channels", C.c_uint64),
+        ("kernel", C.c_char * 64),
+    ]
+
+
+PAD_NONE, PAD_ODD, PAD_EVEN, PAD_CONSTANT = 0, 1, 2, 3
+
+
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -168,6 +179,16 @@ SIGNATURES = {
     "sdsp_hip_istft_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_istft_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_istft_plan_get_info": (_i, [_vp, C.POINTER(IstftPlanInfo)]),
+    "sdsp_hip_iir_steady_state": (_i, [_u32, _i, _vp, _vp, _d, _vp]),
+    "sdsp_hip_filtfilt_default_padlen": (_i, [_u32, _i, _vp, _vp, C.POINTER(_u32)]),
+    "sdsp_hip_filtfilt_plan_create": (_i, [_pp, _u32, _i, _vp, _vp, _d, _i, _i, C.c_int64, _u64, _i]),
+    "sdsp_hip_filtfilt_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_filtfilt_process": (_i, [_vp, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_filtfilt_process_host": (_i, [_vp, _vp, _u64, _u64, _u64]),
+    "sdsp_hip_filtfilt_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_filtfilt_plan_kernel": (_i, [_vp, _vp, _u64, _u64, _u64, C.c_char_p, _sz]),
+    "sdsp_hip_filtfilt_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_filtfilt_plan_get_info": (_i, [_vp, C.POINTER(FiltfiltPlanInfo)]),
 }
 
 _lib = None

@@ -42,6 +42,7 @@ SOURCES = {
     "fft_mid.hip": ["-fno-slp-vectorize"],
     "fft_2pass.hip": ["-fno-slp-vectorize"],
     "iir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    "iir_filtfilt.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # iir.hip's recurrence (iir_step.h), bit for bit
     "fir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps: multiply then add, like the oracle
     "fir_fft.hip": [],
     "fir_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64: multiply then add per tap, as fir.hip

@@ -344,6 +344,17 @@ struct sdsp_hip_istft_plan {
     double env_min = 0, env_max = 0;
 };
 
+struct sdsp_hip_filtfilt_plan {
+    uint32_t sections = 0, padlen = 0;
+    int kind = 0, precision = 0, device = 0, padtype = 0, variant = 0;
+    double gain = 1.0;
+    double a1[SDSP_HIP_MAX_SECTIONS] = {}, a2[SDSP_HIP_MAX_SECTIONS] = {};
+    double b1[SDSP_HIP_MAX_SECTIONS] = {}, b2[SDSP_HIP_MAX_SECTIONS] = {};
+    double ss[SDSP_HIP_MAX_SECTIONS + 1] = {}; // steady state per level
+    void *ws = nullptr;                        // slice_channels x padlen samples (null when padlen = 0)
+    uint64_t slice_channels = 0, workspace_bytes = 0;
+};
+
 namespace
 {
 // largest power-of-two column count whose padded tile fits the LDS budget
@@ -2755,6 +2766,237 @@ int sdsp_hip_istft_process_host(sdsp_hip_istft_plan *p, const void *host_in, uin
     (void)hipFree(di);
     (void)hipFree(dout);
     (void)hipFree(s);
+    return rc;
+}
+
+// ------------------------------------------------------------------ forward-backward filtering (iir_filtfilt.hip)
+
+namespace
+{
+// the default slice budget: 256 MiB of right-edge samples, raised for long edges toward the 2^17 channels per slice that fill the
+// chip (256 CUs x 8 resident waves x 64 channels), but never above 1 GiB whatever the edge (DESIGN.md section 5.13 has the sweep)
+constexpr uint64_t kFiltfiltDefaultBudget = 256ull << 20;
+constexpr uint64_t kFiltfiltMaxDefaultBudget = 1ull << 30;
+constexpr uint64_t kFiltfiltFillSlice = 1ull << 17;
+
+filtfilt_args filtfilt_make_args(const sdsp_hip_filtfilt_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride)
+{
+    filtfilt_args a{};
+    a.data = data;
+    a.ws = p->ws;
+    a.channels = channels;
+    a.samples = samples;
+    a.stride = stride;
+    a.sections = p->sections;
+    a.padlen = p->padlen;
+    a.kind = p->kind;
+    a.padtype = p->padtype;
+    a.gain = p->gain;
+    for (uint32_t j = 0; j < p->sections; j++) {
+        a.a1[j] = p->a1[j];
+        a.a2[j] = p->a2[j];
+        a.b1[j] = p->b1[j];
+        a.b2[j] = p->b2[j];
+    }
+    for (uint32_t j = 0; j <= p->sections; j++)
+        a.ss[j] = p->ss[j];
+    return a;
+}
+
+int filtfilt_run(sdsp_hip_filtfilt_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride, hipStream_t stream)
+{
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    for (uint64_t c0 = 0; c0 < channels; c0 += p->slice_channels) {
+        const uint64_t n = std::min(p->slice_channels, channels - c0);
+        const filtfilt_args a = filtfilt_make_args(p, static_cast<char *>(data) + c0 * stride * rs, n, samples, stride);
+        if (int rc = launch_filtfilt(p->precision, a, p->variant, stream))
+            return rc;
+    }
+    return SDSP_HIP_OK;
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int filtfilt_check(const sdsp_hip_filtfilt_plan *p, const void *data, uint64_t channels, uint64_t samples, uint64_t stride)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples <= p->padlen)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be larger than padlen (the edge extension mirrors padlen samples)");
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (!data)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "data is null");
+    if (stride < samples && channels > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "stride must be >= samples");
+    return SDSP_HIP_OK;
+}
+} // namespace
+
+int sdsp_hip_filtfilt_plan_create(sdsp_hip_filtfilt_plan **out, uint32_t sections, int kind, const double *a, const double *b,
+                                  double gain, int precision, int padtype, int64_t padlen, uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    double ss[SDSP_HIP_MAX_SECTIONS + 1];
+    if (int rc = iir_steady_state(sections, kind, a, b, gain, ss))
+        return rc;
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64 && precision != SDSP_HIP_F32_F64STATE)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32, SDSP_HIP_F64 or SDSP_HIP_F32_F64STATE");
+    if (padtype < SDSP_HIP_PAD_NONE || padtype > SDSP_HIP_PAD_CONSTANT)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "padtype must be SDSP_HIP_PAD_NONE / ODD / EVEN / CONSTANT");
+    uint32_t pad = 0;
+    if (padtype != SDSP_HIP_PAD_NONE) {
+        if (padlen >= (1ll << 31))
+            return fail(SDSP_HIP_ERR_INVALID_SIZE, "padlen must be below 2^31");
+        if (padlen < 0) {
+            if (int rc = filtfilt_default_padlen(sections, kind, a, b, &pad))
+                return rc;
+        } else {
+            pad = static_cast<uint32_t>(padlen);
+        }
+    }
+    if (int rc = use_device(device))
+        return rc;
+    const uint64_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    auto *p = new sdsp_hip_filtfilt_plan();
+    p->sections = sections;
+    p->padlen = pad;
+    p->kind = kind;
+    p->precision = precision;
+    p->device = device;
+    p->padtype = padtype;
+    p->gain = gain;
+    for (uint32_t j = 0; j < sections; j++) {
+        p->a1[j] = a[3 * j + 1];
+        p->a2[j] = a[3 * j + 2];
+        if (b) {
+            p->b1[j] = b[3 * j + 1];
+            p->b2[j] = b[3 * j + 2];
+        }
+    }
+    std::memcpy(p->ss, ss, sizeof(double) * (sections + 1));
+    if (pad == 0) { // nothing to keep between the passes: one launch covers every channel
+        p->slice_channels = 1ull << 40;
+    } else {
+        const uint64_t per_channel = pad * rs;
+        const uint64_t fill = kFiltfiltFillSlice * per_channel;
+        const uint64_t budget =
+            workspace_bytes ? workspace_bytes : std::min(std::max(kFiltfiltDefaultBudget, fill), kFiltfiltMaxDefaultBudget);
+        p->slice_channels = std::min<uint64_t>(std::max<uint64_t>(64, budget / per_channel / 64 * 64), 1ull << 36);
+        p->workspace_bytes = p->slice_channels * per_channel;
+        hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
+        if (e != hipSuccess) {
+            p->ws = nullptr;
+            const int rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "filtfilt plan: out of device memory")
+                                                    : hip_fail(e, "filtfilt plan");
+            sdsp_hip_filtfilt_plan_destroy(p);
+            return rc;
+        }
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_filtfilt_plan_destroy(sdsp_hip_filtfilt_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (p->ws && use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->ws);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_filtfilt_plan_set_variant(sdsp_hip_filtfilt_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 (fused) or 1 (direct)");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_filtfilt_plan_launches(const sdsp_hip_filtfilt_plan *p, uint64_t channels, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    if (samples <= p->padlen)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be larger than padlen");
+    *launches = (channels + p->slice_channels - 1) / p->slice_channels;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_filtfilt_plan_kernel(const sdsp_hip_filtfilt_plan *p, const void *data, uint64_t channels, uint64_t samples,
+                                  uint64_t stride, char *name, size_t name_bytes)
+{
+    if (!p || !name || name_bytes == 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    // the first slice's shape: the one the launcher selects for first (later slices start stride * slice_channels further on)
+    const filtfilt_args a = filtfilt_make_args(p, const_cast<void *>(data), std::min(channels, p->slice_channels), samples, stride);
+    std::strncpy(name, filtfilt_kernel_for(p->precision, a, p->variant), name_bytes - 1);
+    name[name_bytes - 1] = 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_filtfilt_plan_get_info(const sdsp_hip_filtfilt_plan *p, sdsp_hip_filtfilt_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->sections = p->sections;
+    info->padlen = p->padlen;
+    info->kind = p->kind;
+    info->padtype = p->padtype;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->variant = p->variant;
+    info->workspace_bytes = p->workspace_bytes;
+    info->slice_channels = p->slice_channels;
+    // the kernel of a long run of 16-byte aligned rows (address 0 stands for any aligned pointer)
+    const filtfilt_args a = filtfilt_make_args(p, nullptr, 2, p->padlen + 1, 64);
+    std::strncpy(info->kernel, filtfilt_kernel_for(p->precision, a, p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_filtfilt_process(sdsp_hip_filtfilt_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride, void *stream)
+{
+    if (int rc = filtfilt_check(p, data, channels, samples, stride))
+        return rc;
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(data) % rs)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "data must be aligned to its element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return filtfilt_run(p, data, channels, samples, stride, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_filtfilt_process_host(sdsp_hip_filtfilt_plan *p, void *host_data, uint64_t channels, uint64_t samples, uint64_t stride)
+{
+    if (int rc = filtfilt_check(p, host_data, channels, samples, stride))
+        return rc;
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t bytes = ((channels - 1) * stride + samples) * rs;
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMemcpy(d, host_data, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        rc = hip_fail(e, "filtfilt host staging");
+    if (!rc)
+        rc = filtfilt_run(p, d, channels, samples, stride, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_data, d, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "filtfilt host read-back");
+    }
+    (void)hipFree(d);
     return rc;
 }
 }

@@ -262,6 +262,69 @@ int preload(uint32_t m, int filter_type, const double *a, const double *b, doubl
     }
     return SDSP_HIP_OK;
 }
+// forward-backward filtering: the steady state of a cascade per unit input and scipy's default edge
+namespace
+{
+int check_cascade(uint32_t m, int kind, const double *a, const double *b)
+{
+    if (m == 0 || m % 2 != 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "M must be even!");
+    if (m > SDSP_HIP_MAX_SECTIONS)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "at most SDSP_HIP_MAX_SECTIONS (16) sections are compiled in");
+    if (kind < SDSP_HIP_IIR_GENERIC || kind > SDSP_HIP_IIR_BP)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "unknown IIR kind");
+    if (!a || (kind == SDSP_HIP_IIR_GENERIC && !b))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "coefficient pointer is null");
+    return SDSP_HIP_OK;
+}
+
+// b1 / b2 of section j as the kind's process body uses them: the folded numerators 1+2+1, 1-2+1, 1+0-1
+void numerator(int kind, const double *b, uint32_t j, double *b1, double *b2)
+{
+    switch (kind) {
+    case SDSP_HIP_IIR_LP: *b1 = 2.0, *b2 = 1.0; break;
+    case SDSP_HIP_IIR_HP: *b1 = -2.0, *b2 = 1.0; break;
+    case SDSP_HIP_IIR_BP: *b1 = 0.0, *b2 = -1.0; break;
+    default: *b1 = b[3 * j + 1], *b2 = b[3 * j + 2]; break;
+    }
+}
+} // namespace
+
+int iir_steady_state(uint32_t m, int kind, const double *a, const double *b, double gain, double *s)
+{
+    if (int rc = check_cascade(m, kind, a, b))
+        return rc;
+    if (!s)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    for (uint32_t j = 0; j < m; j++)
+        if (1.0 + a[3 * j + 1] + a[3 * j + 2] == 0.0)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "a section has 1 + a1 + a2 == 0 (a pole at z = 1): it has no steady state");
+    s[0] = gain;
+    for (uint32_t j = 0; j < m; j++) {
+        double b1, b2;
+        numerator(kind, b, j, &b1, &b2);
+        s[j + 1] = s[j] * (1.0 + b1 + b2) / (1.0 + a[3 * j + 1] + a[3 * j + 2]);
+    }
+    return SDSP_HIP_OK;
+}
+
+int filtfilt_default_padlen(uint32_t m, int kind, const double *a, const double *b, uint32_t *padlen)
+{
+    if (int rc = check_cascade(m, kind, a, b))
+        return rc;
+    if (!padlen)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    uint32_t zb = 0, za = 0;
+    for (uint32_t j = 0; j < m; j++) {
+        double b1, b2;
+        numerator(kind, b, j, &b1, &b2);
+        zb += b2 == 0.0;
+        za += a[3 * j + 2] == 0.0;
+    }
+    *padlen = 3 * (2 * m + 1 - std::min(zb, za));
+    return SDSP_HIP_OK;
+}
+
 // inverse STFT synthesis window: env[r] = sum over ascending k of w[r + k hop]^2, in double
 int istft_synthesis(uint32_t n, uint32_t hop, const double *w, int norm, double *g, double *env_min, double *env_max)
 {
@@ -443,5 +506,13 @@ int sdsp_hip_stft_frames(uint32_t hop, uint64_t samples, uint64_t *frames)
 int sdsp_hip_istft_synthesis_window(uint32_t n_fft, uint32_t hop, const double *window, int norm, double *g)
 {
     return istft_synthesis(n_fft, hop, window, norm, g, nullptr, nullptr);
+}
+int sdsp_hip_iir_steady_state(uint32_t sections, int kind, const double *a, const double *b, double gain, double *s)
+{
+    return iir_steady_state(sections, kind, a, b, gain, s);
+}
+int sdsp_hip_filtfilt_default_padlen(uint32_t sections, int kind, const double *a, const double *b, uint32_t *padlen)
+{
+    return filtfilt_default_padlen(sections, kind, a, b, padlen);
 }
 }

@@ -27,6 +27,10 @@ int design_bs(uint32_t m, double f0, double fs, double q, double gain_in, double
 int design_fir(uint32_t taps, int filter_type, double f0, double fs, double q, double gain_in, double *h);
 int preload(uint32_t m, int filter_type, const double *a, const double *b, double gain, double value,
             double *mem);
+// s[0..m]: s_0 = gain, s_{j+1} = s_j (1 + b1_j + b2_j) / (1 + a1_j + a2_j), the folded numerators for LP / HP / BP
+int iir_steady_state(uint32_t m, int kind, const double *a, const double *b, double gain, double *s);
+// scipy.signal.sosfiltfilt's default edge: 3 (2 m + 1 - min(#{b2_j == 0}, #{a2_j == 0}))
+int filtfilt_default_padlen(uint32_t m, int kind, const double *a, const double *b, uint32_t *padlen);
 
 // ------------------------------------------------------------------------------------------
 // FFT: one "tile" launch = every workgroup transforms `cols` independent length-n sequences held
@@ -210,6 +214,21 @@ int launch_iir(int precision, const iir_args &a, int variant, void *stream);
 // the kernel launch_iir would run for this shape and variant (iir.hip: iir_select -- the same function the launcher uses)
 const char *iir_kernel_for(int precision, const iir_args &a, int variant);
 int launch_iir_interleaved(int precision, const iir_args &a, int variant, void *stream);
+// zero-phase forward-backward filtering (iir_filtfilt.hip): one launch per workspace slice
+struct filtfilt_args {
+    void *data; // the slice's first row
+    void *ws;   // ceil(channels / 64) * 64 * padlen samples; null when padlen = 0
+    uint64_t channels, samples, stride;
+    uint32_t sections, padlen;
+    int kind, padtype;
+    double gain;
+    double a1[SDSP_HIP_MAX_SECTIONS], a2[SDSP_HIP_MAX_SECTIONS];
+    double b1[SDSP_HIP_MAX_SECTIONS], b2[SDSP_HIP_MAX_SECTIONS];
+    double ss[SDSP_HIP_MAX_SECTIONS + 1]; // steady state per level (host_math.cpp: iir_steady_state)
+};
+int launch_filtfilt(int precision, const filtfilt_args &a, int variant, void *stream);
+// the kernel launch_filtfilt runs for this shape and variant (the same selection function)
+const char *filtfilt_kernel_for(int precision, const filtfilt_args &a, int variant);
 
 // FIR bank
 struct fir_args {

@@ -30,6 +30,7 @@ class casc_2o_iir:
         self._plan = None
         self._state = None  # torch tensor (3*(m_t+1), channels) on the device, or None = zeros
         self._variant = 0
+        self._filtfilt_plans = {}  # (padtype, padlen) -> filtfilt_plan of the current design
 
     def _dtypes(self):
         """(sample dtype, state dtype): F32_F64STATE keeps float samples and a double recurrence"""
@@ -96,6 +97,7 @@ class casc_2o_iir:
         if self._plan:
             self._lib.sdsp_hip_iir_plan_destroy(self._plan)
             self._plan = None
+        self._filtfilt_plans = {}
 
     def _ensure_plan(self):
         if self._plan is None:
@@ -147,6 +149,14 @@ class casc_2o_iir:
         L.check(self._lib.sdsp_hip_iir_process(self._plan, data.data_ptr() + offset * data.element_size(),
                                                self.channels, samples, stride, self._state.data_ptr(), stream))
         return data
+
+    def filtfilt(self, data, samples: int | None = None, padtype="odd", padlen=None):
+        """Zero-phase forward-backward filtering (scipy.signal.sosfiltfilt) of data[:, :samples] of every row, in place, with the
+        bank's designed coefficients, kind and precision (include/sdsp_hip.h: sdsp_hip_filtfilt_*).  data: contiguous
+        (rows, stride) device tensor of the bank dtype, any number of rows.  The bank's streaming state is neither read nor
+        changed.  padtype: 'odd', 'even', 'constant' or None; padlen None = scipy's default for the cascade."""
+        from .filtfilt import bank_filtfilt
+        return bank_filtfilt(self, data, samples, padtype, padlen)
 
     def process_interleaved(self, data, samples: int | None = None, offset: int = 0):
         """data: contiguous device tensor (samples, channels) -- the sample-major "wire" layout
