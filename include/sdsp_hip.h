@@ -658,6 +658,89 @@ typedef struct {
 } sdsp_hip_filtfilt_plan_info;
 int sdsp_hip_filtfilt_plan_get_info(const sdsp_hip_filtfilt_plan *plan, sdsp_hip_filtfilt_plan_info *info);
 
+/* ------------------------------------------------------------------ Welch power spectral density banks */
+
+/*
+ * Welch power spectral density of `channels` independent real streams, accumulated across calls:
+ * scipy.signal.welch(x, fs, window, nperseg = N, noverlap = N - hop, detrend, scaling, return_onesided = True, average = "mean").
+ * N = n_fft (a power of two in the radix-2 real-input range: f32 32 .. 65536, f64 32 .. 32768), 1 <= hop <= N, bins = N / 2 + 1,
+ * hist = N - 1.
+ *   - segments are scipy's: segment m >= 0 covers stream samples [m hop, m hop + N).  A call receives `position` (samples of the
+ *     stream processed since reset, the same for every channel) and S samples per channel, any S >= 0, and counts exactly the
+ *     segments that end inside it: position < m hop + N <= position + S (sdsp_hip_welch_frames).  No segment reaches before sample 0.
+ *   - history: state[c hist + j] = x_c[position - 1 - j] (newest first), plan precision; read at entry, written at exit.  NULL is
+ *     allowed only with position == 0, and then the final history is dropped.
+ *   - detrend, per segment x_0 .. x_{N-1} of plan-precision samples: mu = sum x_n / N and, for LINEAR, beta = sum (n - (N-1)/2) x_n /
+ *     (N (N^2 - 1) / 12), in double; trend t_n = mu + beta (n - (N-1)/2) (beta = 0 for CONSTANT); d_n = round_p(x_n - t_n) with the
+ *     difference taken in double; windowed sample round_p(d_n w_n).  NONE: round_p(x_n w_n), the STFT bank's frame value.  Sum
+ *     order: every lane sums its samples in order, the lanes of a segment then add in an xor butterfly, the waves in ascending order.
+ *   - transform: the library's forward real-input plan of n_real = N, radix 2 (unchanged).  p_k = re re + im im in double from the
+ *     plan-precision re and im, no FMA contraction; bins 0 and N / 2 from the packed slot 0.
+ *   - acc[c acc_stride + k], k < bins: doubles owned by the caller, beside the history.  A call adds its segments' p_k: runs of up to
+ *     R segments of one channel are summed in ascending order, then each channel's runs in ascending order, then one addition into
+ *     acc (R: DESIGN.md section 5.14).  No atomics: identical calls give identical bits, and a call that counts one segment leaves
+ *     acc + p_k with a single rounding.  Block-by-block calls agree with one long call to rounding.
+ *   - finalize: out[c out_stride + k] = round_p(acc c_k), c_k = m_k scale / frames_total in double on the host, m_k = 2 for
+ *     0 < k < N / 2 and 1 otherwise; scale = 1 / (fs sum w^2) for DENSITY, 1 / (sum w)^2 for SPECTRUM, summed in double over the
+ *     plan's rounded window.
+ *   - strides count elements.  `in` is never written; nothing past each row's bins of acc or out is.
+ * A call runs in slices of the plan's workspace: detrended, windowed segments -> the forward real-input transform -> run sums ->
+ * per-channel combine into acc, then one launch for the new history (the STFT bank's state launch with hist = N - 1).
+ */
+#define SDSP_HIP_DETREND_NONE 0
+#define SDSP_HIP_DETREND_CONSTANT 1
+#define SDSP_HIP_DETREND_LINEAR 2
+#define SDSP_HIP_SCALING_DENSITY 0
+#define SDSP_HIP_SCALING_SPECTRUM 1
+typedef struct sdsp_hip_welch_plan sdsp_hip_welch_plan;
+/* segments one call of `samples` per channel at `position` counts; host only.  n_fft = 0 or hop = 0: SDSP_HIP_ERR_INVALID_SIZE;
+ * frames NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_welch_frames(uint32_t n_fft, uint32_t hop, uint64_t position, uint64_t samples, uint64_t *frames);
+/* window: n_fft host doubles (sdsp_hip_stft_window gives scipy's periodic windows).  detrend: SDSP_HIP_DETREND_*; scaling:
+ * SDSP_HIP_SCALING_*; fs > 0.  workspace_bytes: the slice budget (0 = the default, 256 MiB); a slice of u segments takes
+ * u (N size(precision) + (N / 2 + 1) 8) bytes, at least one segment.  Errors: n_fft not a power of two, hop = 0 or hop > n_fft:
+ * SDSP_HIP_ERR_INVALID_SIZE; n_fft outside the real-input range of the precision: SDSP_HIP_ERR_UNSUPPORTED; a null pointer, a
+ * precision other than F32 / F64, an unknown detrend or scaling, fs <= 0 or not finite: SDSP_HIP_ERR_INVALID_ARG; no device:
+ * SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_welch_plan_create(sdsp_hip_welch_plan **plan, uint32_t n_fft, uint32_t hop, const double *window, int detrend, int scaling,
+                               double fs, int precision, uint64_t workspace_bytes, int device);
+int sdsp_hip_welch_plan_destroy(sdsp_hip_welch_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples).  state: DEVICE pointer (or NULL at position 0).  acc: DEVICE pointer,
+ * doubles, channel c = acc[c acc_stride .. + bins).  Asynchronous on `stream`, allocates nothing (stream-capturable); one call per
+ * plan in flight.  Errors: a null plan, in or acc, state NULL with position > 0, in_stride < samples or acc_stride < bins with more
+ * than one channel, `in` overlapping state or acc, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG.  channels == 0 or samples == 0:
+ * nothing to do.  DESIGN.md section 5.14.
+ */
+int sdsp_hip_welch_process(sdsp_hip_welch_plan *plan, const void *in, uint64_t in_stride, uint64_t channels, uint64_t samples,
+                           uint64_t position, void *state, double *acc, uint64_t acc_stride, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_welch_process_host(sdsp_hip_welch_plan *plan, const void *host_in, uint64_t in_stride, uint64_t channels, uint64_t samples,
+                                uint64_t position, void *host_state, double *host_acc, uint64_t acc_stride);
+/* out: DEVICE pointer, plan precision, channel c = out[c out_stride .. + bins).  frames_total: the segments acc holds.  Asynchronous,
+ * one launch.  Errors: frames_total == 0: SDSP_HIP_ERR_INVALID_SIZE; a null plan, acc or out, acc_stride or out_stride < bins with
+ * more than one channel, overlapping acc and out, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG.  channels == 0: nothing to do. */
+int sdsp_hip_welch_finalize(sdsp_hip_welch_plan *plan, const double *acc, uint64_t acc_stride, uint64_t frames_total, void *out,
+                            uint64_t out_stride, uint64_t channels, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_welch_finalize_host(sdsp_hip_welch_plan *plan, const double *host_acc, uint64_t acc_stride, uint64_t frames_total,
+                                 void *host_out, uint64_t out_stride, uint64_t channels);
+/* bytes of a state buffer for `channels` channels: (n_fft - 1) channels element size */
+int sdsp_hip_welch_state_bytes(const sdsp_hip_welch_plan *plan, uint64_t channels, uint64_t *bytes);
+/* kernel launches of one process call of `samples` per channel at `position` with a state buffer (frame, transform, run and combine
+ * launches per slice, plus the state launch when samples > 0); finalize is one more */
+int sdsp_hip_welch_plan_launches(const sdsp_hip_welch_plan *plan, uint64_t channels, uint64_t samples, uint64_t position,
+                                 uint64_t *launches);
+typedef struct {
+    uint32_t n_fft, hop, bins, hist;
+    int detrend, scaling;
+    double fs;
+    int precision, device;
+    uint64_t workspace_bytes;
+    char kernel[64]; /* the inner transform's kernel */
+} sdsp_hip_welch_plan_info;
+int sdsp_hip_welch_plan_get_info(const sdsp_hip_welch_plan *plan, sdsp_hip_welch_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

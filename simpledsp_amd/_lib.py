@@ -92,6 +92,18 @@ class FiltfiltPlanInfo(C.Structure):
 PAD_NONE, PAD_ODD, PAD_EVEN, PAD_CONSTANT = 0, 1, 2, 3
 
 
+class WelchPlanInfo(C.Structure):
+    _fields_ = [
+        ("n_fft", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32), ("detrend", C.c_int),
+        ("scaling", C.c_int), ("fs", C.c_double), ("precision", C.c_int), ("device", C.c_int), ("workspace_bytes", C.c_uint64),
+        ("kernel", C.c_char * 64),
+    ]
+
+
+DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR = 0, 1, 2
+SCALING_DENSITY, SCALING_SPECTRUM = 0, 1
+
+
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -189,6 +201,16 @@ SIGNATURES = {
     "sdsp_hip_filtfilt_plan_kernel": (_i, [_vp, _vp, _u64, _u64, _u64, C.c_char_p, _sz]),
     "sdsp_hip_filtfilt_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_filtfilt_plan_get_info": (_i, [_vp, C.POINTER(FiltfiltPlanInfo)]),
+    "sdsp_hip_welch_frames": (_i, [_u32, _u32, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_welch_plan_create": (_i, [_pp, _u32, _u32, _vp, _i, _i, _d, _i, _u64, _i]),
+    "sdsp_hip_welch_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_welch_process": (_i, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp, _u64, _vp]),
+    "sdsp_hip_welch_process_host": (_i, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp, _u64]),
+    "sdsp_hip_welch_finalize": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_welch_finalize_host": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _u64]),
+    "sdsp_hip_welch_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_welch_plan_launches": (_i, [_vp, _u64, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_welch_plan_get_info": (_i, [_vp, C.POINTER(WelchPlanInfo)]),
 }
 
 _lib = None

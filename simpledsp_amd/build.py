@@ -48,6 +48,7 @@ SOURCES = {
     "fir_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64: multiply then add per tap, as fir.hip
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
+    "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA
 }
 
 

@@ -3,6 +3,7 @@
 // fft_tile.hip / fft4096.hip / iir.hip; there is no CPU implementation behind these entry points.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -342,6 +343,17 @@ struct sdsp_hip_istft_plan {
     void *ws = nullptr;                 // ws_units x n reals: the slice's packed spectra, transformed in place
     uint64_t ws_units = 0, workspace_bytes = 0;
     double env_min = 0, env_max = 0;
+};
+
+struct sdsp_hip_welch_plan {
+    uint32_t n = 0, hop = 0, hist = 0, bins = 0; // hist = n - 1, bins = n / 2 + 1
+    int detrend = 0, scaling = 0, precision = 0, device = 0;
+    double fs = 1.0, scale = 1.0;       // scale: 1 / (fs sum w^2) or 1 / (sum w)^2 over the rounded window
+    sdsp_hip_fft_plan *inner = nullptr; // forward real-input plan of n_real = n, radix 2
+    void *window = nullptr;             // n values, plan precision
+    void *ws = nullptr;                 // ws_units x n reals (the slice's segments, transformed in place), then the run partials
+    double *part = nullptr;             // inside ws: up to ws_units x bins doubles
+    uint64_t ws_units = 0, workspace_bytes = 0;
 };
 
 struct sdsp_hip_filtfilt_plan {
@@ -2997,6 +3009,394 @@ int sdsp_hip_filtfilt_process_host(sdsp_hip_filtfilt_plan *p, void *host_data, u
             rc = hip_fail(e, "filtfilt host read-back");
     }
     (void)hipFree(d);
+    return rc;
+}
+
+// ------------------------------------------------------------------ Welch PSD banks (welch.hip)
+
+namespace
+{
+// the STFT bank's measured slice budget, now split between segments and run partials
+constexpr uint64_t kWelchDefaultBudget = 256ull << 20;
+
+uint64_t welch_unit_bytes(uint32_t n, int precision)
+{
+    return static_cast<uint64_t>(n) * (precision == SDSP_HIP_F64 ? 8 : 4) + (static_cast<uint64_t>(n) / 2 + 1) * 8;
+}
+
+// segments per run: one run per channel up to 16 segments, else the smallest power of two R with R^2 >= the segments one channel
+// has in a slice, so that the run stage and the combine stage both loop about sqrt of them
+uint32_t welch_run_length(uint64_t frames, uint64_t ws_units)
+{
+    const uint64_t f = std::min(frames, ws_units);
+    if (f <= 16)
+        return static_cast<uint32_t>(std::max<uint64_t>(f, 1));
+    uint32_t r = 1;
+    while (static_cast<uint64_t>(r) * r < f)
+        r <<= 1;
+    return r;
+}
+
+int welch_run(sdsp_hip_welch_plan *p, const void *in, uint64_t in_stride, uint64_t channels, uint64_t samples, uint64_t position,
+              void *state, double *acc, uint64_t acc_stride, hipStream_t stream)
+{
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_welch_frames(p->n, p->hop, position, samples, &frames))
+        return rc;
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many segments per channel for one call");
+    if (frames && channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many segments for one call");
+    const uint64_t total = channels * frames;
+    const uint64_t first = position < p->n ? 0 : (position - p->n) / p->hop + 1; // the call's first segment
+    welch_args a{};
+    a.in = in;
+    a.state = state;
+    a.window = p->window;
+    a.ws = p->ws;
+    a.part = p->part;
+    a.acc = acc;
+    a.in_stride = in_stride;
+    a.acc_stride = acc_stride;
+    a.channels = channels;
+    a.frames = static_cast<uint32_t>(frames);
+    a.n = p->n;
+    a.hop = p->hop;
+    a.off0 = static_cast<uint32_t>(first * p->hop + p->hist - position); // in [0, max(N - 1, hop - 1)]
+    a.run = welch_run_length(frames, p->ws_units);
+    a.detrend = p->detrend;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        a.g0 = g0;
+        a.units = static_cast<uint32_t>(std::min(p->ws_units, total - g0));
+        if (int rc = launch_welch(p->precision, a, WELCH_FRAME, stream))
+            return rc;
+        if (int rc = fft_exec_pieces(p->inner, p->ws, a.units, stream, p->inner->variant))
+            return rc;
+        if (int rc = launch_welch(p->precision, a, WELCH_RUN, stream))
+            return rc;
+        if (int rc = launch_welch(p->precision, a, WELCH_COMBINE, stream))
+            return rc;
+    }
+    if (!state || samples == 0)
+        return SDSP_HIP_OK;
+    stft_args s{}; // after every frame launch: they may read the old history
+    s.in = in;
+    s.state = state;
+    s.in_stride = in_stride;
+    s.channels = channels;
+    s.samples = samples;
+    s.hist = p->hist;
+    return launch_stft(p->precision, s, STFT_STATE, stream);
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int welch_check(const sdsp_hip_welch_plan *p, const void *in, uint64_t in_stride, uint64_t channels, uint64_t samples,
+                uint64_t position, const void *state, const double *acc, uint64_t acc_stride)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_welch_frames(p->n, p->hop, position, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !acc)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or acc is null");
+    if (!state && position > 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "state may be null only at position 0");
+    if (channels > 1 && (in_stride < samples || acc_stride < p->bins))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and acc_stride >= bins");
+    return SDSP_HIP_OK;
+}
+
+int welch_finalize_check(const sdsp_hip_welch_plan *p, const double *acc, uint64_t acc_stride, uint64_t frames_total, const void *out,
+                         uint64_t out_stride, uint64_t channels)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (frames_total == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "frames_total must be >= 1");
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (!acc || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc or out is null");
+    if (channels > 1 && (acc_stride < p->bins || out_stride < p->bins))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc_stride and out_stride must be >= bins");
+    return SDSP_HIP_OK;
+}
+
+bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+int welch_finalize_run(const sdsp_hip_welch_plan *p, const double *acc, uint64_t acc_stride, uint64_t frames_total, void *out,
+                       uint64_t out_stride, uint64_t channels, hipStream_t stream)
+{
+    welch_args a{};
+    a.acc = const_cast<double *>(acc);
+    a.acc_stride = acc_stride;
+    a.out = out;
+    a.out_stride = out_stride;
+    a.channels = channels;
+    a.n = p->n;
+    a.c_edge = p->scale / static_cast<double>(frames_total);
+    a.c_mid = 2.0 * p->scale / static_cast<double>(frames_total);
+    return launch_welch(p->precision, a, WELCH_FINALIZE, stream);
+}
+} // namespace
+
+int sdsp_hip_welch_plan_create(sdsp_hip_welch_plan **out, uint32_t n_fft, uint32_t hop, const double *window, int detrend, int scaling,
+                               double fs, int precision, uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (!sdsp_hip_is_power_of_2(n_fft))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
+    if (hop == 0 || hop > n_fft)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
+    if (!window)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (detrend != SDSP_HIP_DETREND_NONE && detrend != SDSP_HIP_DETREND_CONSTANT && detrend != SDSP_HIP_DETREND_LINEAR)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "detrend must be SDSP_HIP_DETREND_NONE, _CONSTANT or _LINEAR");
+    if (scaling != SDSP_HIP_SCALING_DENSITY && scaling != SDSP_HIP_SCALING_SPECTRUM)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scaling must be SDSP_HIP_SCALING_DENSITY or _SPECTRUM");
+    if (!(fs > 0.0) || !std::isfinite(fs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "fs must be finite and > 0");
+    if (n_fft < 32 || n_fft > stft_max_n(precision))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    // the window rounded once to the plan precision; the scale sums run over those values
+    std::vector<double> wr(window, window + n_fft);
+    if (precision == SDSP_HIP_F32)
+        for (double &v : wr)
+            v = static_cast<double>(static_cast<float>(v));
+    double sw = 0.0, sw2 = 0.0;
+    for (double v : wr) {
+        sw += v;
+        sw2 += v * v;
+    }
+    if (int rc = use_device(device))
+        return rc;
+    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t unit_bytes = welch_unit_bytes(n_fft, precision);
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kWelchDefaultBudget;
+    auto *p = new sdsp_hip_welch_plan();
+    p->n = n_fft;
+    p->hop = hop;
+    p->hist = n_fft - 1;
+    p->bins = n_fft / 2 + 1;
+    p->detrend = detrend;
+    p->scaling = scaling;
+    p->fs = fs;
+    p->scale = scaling == SDSP_HIP_SCALING_DENSITY ? 1.0 / (fs * sw2) : 1.0 / (sw * sw);
+    p->precision = precision;
+    p->device = device;
+    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->workspace_bytes = p->ws_units * unit_bytes;
+    int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device, 1);
+    if (!rc) {
+        hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
+        if (e == hipSuccess) {
+            p->part = reinterpret_cast<double *>(static_cast<char *>(p->ws) + p->ws_units * n_fft * rs);
+            e = hipMalloc(&p->window, n_fft * rs);
+        }
+        if (e == hipSuccess) {
+            if (precision == SDSP_HIP_F64) {
+                e = hipMemcpy(p->window, wr.data(), n_fft * rs, hipMemcpyHostToDevice);
+            } else {
+                const std::vector<float> wf(wr.begin(), wr.end());
+                e = hipMemcpy(p->window, wf.data(), n_fft * rs, hipMemcpyHostToDevice);
+            }
+        }
+        if (e != hipSuccess)
+            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "welch plan: out of device memory") : hip_fail(e, "welch plan");
+    }
+    if (rc) {
+        sdsp_hip_welch_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_welch_plan_destroy(sdsp_hip_welch_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->ws);
+        (void)hipFree(p->window);
+    }
+    if (p->inner)
+        sdsp_hip_fft_plan_destroy(p->inner);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_welch_state_bytes(const sdsp_hip_welch_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_welch_plan_get_info(const sdsp_hip_welch_plan *p, sdsp_hip_welch_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->n_fft = p->n;
+    info->hop = p->hop;
+    info->bins = p->bins;
+    info->hist = p->hist;
+    info->detrend = p->detrend;
+    info->scaling = p->scaling;
+    info->fs = p->fs;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->workspace_bytes = p->workspace_bytes;
+    std::strncpy(info->kernel, select_kernel(p->inner, p->inner->variant).name, sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_welch_plan_launches(const sdsp_hip_welch_plan *p, uint64_t channels, uint64_t samples, uint64_t position,
+                                 uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_welch_frames(p->n, p->hop, position, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t total = channels * frames;
+    uint64_t n = 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t units = std::min(p->ws_units, total - g0);
+        n += 3 + fft_launch_count(p->inner, units, p->inner->variant);
+    }
+    *launches = n + 1;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_welch_process(sdsp_hip_welch_plan *p, const void *in, uint64_t in_stride, uint64_t channels, uint64_t samples,
+                           uint64_t position, void *state, double *acc, uint64_t acc_stride, void *stream)
+{
+    if (int rc = welch_check(p, in, in_stride, channels, samples, position, state, acc, acc_stride))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
+    if (ranges_overlap(in, in_bytes, state, channels * p->hist * rs) ||
+        ranges_overlap(in, in_bytes, acc, ((channels - 1) * acc_stride + p->bins) * 8))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in overlaps state or acc");
+    if (reinterpret_cast<uintptr_t>(in) % rs || reinterpret_cast<uintptr_t>(state) % rs || reinterpret_cast<uintptr_t>(acc) % 8)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, state and acc must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return welch_run(p, in, in_stride, channels, samples, position, state, acc, acc_stride, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_welch_process_host(sdsp_hip_welch_plan *p, const void *host_in, uint64_t in_stride, uint64_t channels, uint64_t samples,
+                                uint64_t position, void *host_state, double *host_acc, uint64_t acc_stride)
+{
+    if (int rc = welch_check(p, host_in, in_stride, channels, samples, position, host_state, host_acc, acc_stride))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
+    const size_t acc_bytes = ((channels - 1) * acc_stride + p->bins) * 8;
+    const size_t state_bytes = channels * p->hist * rs;
+    void *di = nullptr, *da = nullptr, *s = nullptr;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&di, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&da, acc_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) // rows of acc past bins keep what the caller had there
+        e = hipMemcpy(da, host_acc, acc_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && host_state) {
+        e = hipMalloc(&s, state_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+        rc = hip_fail(e, "welch host staging");
+    if (!rc)
+        rc = welch_run(p, di, in_stride, channels, samples, position, s, static_cast<double *>(da), acc_stride, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_acc, da, acc_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && host_state)
+            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "welch host read-back");
+    }
+    (void)hipFree(di);
+    (void)hipFree(da);
+    (void)hipFree(s);
+    return rc;
+}
+
+int sdsp_hip_welch_finalize(sdsp_hip_welch_plan *p, const double *acc, uint64_t acc_stride, uint64_t frames_total, void *out,
+                            uint64_t out_stride, uint64_t channels, void *stream)
+{
+    if (int rc = welch_finalize_check(p, acc, acc_stride, frames_total, out, out_stride, channels))
+        return rc;
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    if (ranges_overlap(acc, ((channels - 1) * acc_stride + p->bins) * 8, out, ((channels - 1) * out_stride + p->bins) * rs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc and out overlap");
+    if (reinterpret_cast<uintptr_t>(acc) % 8 || reinterpret_cast<uintptr_t>(out) % rs)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc and out must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return welch_finalize_run(p, acc, acc_stride, frames_total, out, out_stride, channels, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_welch_finalize_host(sdsp_hip_welch_plan *p, const double *host_acc, uint64_t acc_stride, uint64_t frames_total,
+                                 void *host_out, uint64_t out_stride, uint64_t channels)
+{
+    if (int rc = welch_finalize_check(p, host_acc, acc_stride, frames_total, host_out, out_stride, channels))
+        return rc;
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t acc_bytes = ((channels - 1) * acc_stride + p->bins) * 8;
+    const size_t out_bytes = ((channels - 1) * out_stride + p->bins) * rs;
+    void *da = nullptr, *dout = nullptr;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&da, acc_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&dout, out_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(da, host_acc, acc_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) // rows of out past bins keep what the caller had there
+        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        rc = hip_fail(e, "welch host staging");
+    if (!rc)
+        rc = welch_finalize_run(p, static_cast<const double *>(da), acc_stride, frames_total, dout, out_stride, channels, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "welch host read-back");
+    }
+    (void)hipFree(da);
+    (void)hipFree(dout);
     return rc;
 }
 }

@@ -503,6 +503,20 @@ int sdsp_hip_stft_frames(uint32_t hop, uint64_t samples, uint64_t *frames)
     *frames = samples / hop;
     return SDSP_HIP_OK;
 }
+int sdsp_hip_welch_frames(uint32_t n_fft, uint32_t hop, uint64_t position, uint64_t samples, uint64_t *frames)
+{
+    if (!frames)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *frames = 0;
+    if (n_fft == 0 || hop == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft and hop must be >= 1");
+    if (samples > ~0ull - position)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "position + samples overflows");
+    // segments m with m hop + N <= P: 0 for P < N, else (P - N) / hop + 1; the call counts those ending in (position, position + S]
+    auto ended = [&](uint64_t p) { return p < n_fft ? 0 : (p - n_fft) / hop + 1; };
+    *frames = ended(position + samples) - ended(position);
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_istft_synthesis_window(uint32_t n_fft, uint32_t hop, const double *window, int norm, double *g)
 {
     return istft_synthesis(n_fft, hop, window, norm, g, nullptr, nullptr);

@@ -296,4 +296,23 @@ struct istft_args {
 int launch_istft(int precision, const istft_args &a, int step, void *stream);
 // host_math.cpp: the synthesis window (n doubles) and the range of env[r] = sum_k w[r + k hop]^2; NOLA is checked for NORMALIZED
 int istft_synthesis(uint32_t n, uint32_t hop, const double *w, int norm, double *g, double *env_min, double *env_max);
+// Welch PSD banks (welch.hip): the launches of one slice around the plan's real-input transform, and finalize
+enum { WELCH_FRAME = 0, WELCH_RUN = 1, WELCH_COMBINE = 2, WELCH_FINALIZE = 3 };
+struct welch_args {
+    const void *in;
+    const void *state;  // channels x (n - 1), newest first; null only when no segment reaches into the history
+    const void *window; // device, plan precision, n values
+    void *ws;           // units x n reals (detrended, windowed segments, then their packed half spectra)
+    double *part;       // the slice's run partials: runs x (n / 2 + 1) doubles
+    double *acc;        // acc[c acc_stride + k]
+    void *out;          // finalize: out[c out_stride + k], plan precision
+    uint64_t in_stride, acc_stride, out_stride, channels;
+    uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, segment) numbering
+    uint32_t units, frames, n, hop;
+    uint32_t off0;      // x offset of the call's first segment (x = history followed by the block)
+    uint32_t run;       // R: segments per run
+    int detrend;        // SDSP_HIP_DETREND_*
+    double c_edge, c_mid; // finalize: c_k for k = 0, N / 2 and for the bins between
+};
+int launch_welch(int precision, const welch_args &a, int step, void *stream);
 } // namespace sdsp_hip
