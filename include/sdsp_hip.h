@@ -741,6 +741,90 @@ typedef struct {
 } sdsp_hip_welch_plan_info;
 int sdsp_hip_welch_plan_get_info(const sdsp_hip_welch_plan *plan, sdsp_hip_welch_plan_info *info);
 
+/* ------------------------------------------------------------------ polyphase filter-bank channelizer banks */
+
+/*
+ * Polyphase filter bank (PFB) of `channels` independent streams: every stream is split into M equally spaced
+ * sub-bands with a prototype low-pass of L = P M taps h[0 .. L), one M-point transform per frame.  M = channels_m (a power of two),
+ * P = taps_per_channel (1 .. SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL), L <= 2^20, D = hop (1 <= D <= M; D = M critically sampled, D = M / 2
+ * oversampled by 2), hist = L - D.  A call takes S samples per channel, S a multiple of D, and writes exactly F = S / D frames.  With
+ * x = the channel's history followed by the block (the block starts at index hist), frame j of the call is
+ *     u_j[r] = sum over p < P of fl(x[j D + p M + r] h[p M + r]),  0 <= r < M     (ascending p; every product and sum rounded on its own)
+ *     Y_j[k] = sum over r < M of v_j[r] e^(-2 pi i k r / M)                       (the library's forward transform, unchanged)
+ *   - phase FRAME: v_j = u_j.  Y_j[k] is bin k P of the L-point STFT with window h:
+ *     torch.stft(concat(history, block), n_fft = L, hop = D, window = h, center = False)[k P].
+ *   - phase TIME: v_j[(r + s_j) mod M] = u_j[r] with s_j = (position + j D - hist) mod M, a circular shift by the absolute index of the
+ *     frame's first sample: Y_j[k] = sum over n of x[n0 + n] h[n] e^(-2 pi i k (n0 + n) / M), n0 that absolute index -- every sub-band
+ *     is a down-converted baseband signal whose phase is continuous from frame to frame for any D.  `position` is the number of samples
+ *     of the stream that earlier calls consumed.  For D = M and position a multiple of M both references coincide.
+ *   - h multiplies x in window (correlation) order, as the STFT window does: a caller who thinks in convolution order (y = x * g)
+ *     passes the reversed taps h[n] = g[L - 1 - n].  A symmetric prototype is the same either way.
+ *   - input kinds: REAL = samples of the plan precision, M / 2 + 1 bins per frame through the real-input plans (M in their radix-2
+ *     range: f32 32 .. 65536, f64 32 .. 32768; bins 0 and M / 2 with zero imaginary parts -- the STFT bank's COMPLEX layout);
+ *     COMPLEX = interleaved complex samples (real and imaginary parts folded separately with the real tap), M bins per frame in
+ *     natural order through the complex plans (SDSP_HIP_RADIX_AUTO; M = 16 .. 65536 in f32, 16 .. 32768 in f64).
+ *   - history: state[c hist + j] = x_c[-1 - j] (newest first), elements of the input kind; read at entry, written at exit; NULL = zero
+ *     history, final history dropped.  A fresh stream (NULL or zeroed state) is the stream with hist zeros in front of it.
+ *   - block-by-block calls equal one long call bit for bit for any split into multiples of D (blocks shorter than hist included).
+ *   - the taps: L host doubles, rounded once to the plan precision at creation.
+ *   - strides count elements (a complex sample or bin is one element).  `in` is never written; nothing past each channel's F bins
+ *     outputs is.  Output is complex: out[c out_stride + j bins + k].
+ * A call runs in slices of the workspace budget: fold -> transform (-> unpack to the output rows, REAL), then one launch for the new
+ * history.  REAL folds into the plan's workspace; COMPLEX folds straight into the output rows and transforms them in place (no
+ * workspace is allocated; the budget only sets the slice).
+ */
+#define SDSP_HIP_PFB_REAL 0
+#define SDSP_HIP_PFB_COMPLEX 1
+#define SDSP_HIP_PFB_PHASE_FRAME 0
+#define SDSP_HIP_PFB_PHASE_TIME 1
+#define SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL 64
+#define SDSP_HIP_PFB_MAX_TAPS (1u << 20)
+typedef struct sdsp_hip_pfb_plan sdsp_hip_pfb_plan;
+/* the windowed-sinc prototype of p m taps with cutoff at half the sub-band spacing and unit DC gain, host only:
+ * scipy.signal.firwin(p m, 1.0 / m, window = name) for the four SDSP_HIP_WINDOW_* kinds (firwin's SYMMETRIC window, not the periodic
+ * one sdsp_hip_stft_window returns).  m < 2, p = 0, p > SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL or p m > SDSP_HIP_PFB_MAX_TAPS:
+ * SDSP_HIP_ERR_INVALID_SIZE; unknown kind or h NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_pfb_prototype(int window_kind, uint32_t m, uint32_t p, double *h);
+/* frames one call of `samples` per channel writes (samples / hop); host only.  Errors as sdsp_hip_stft_frames. */
+int sdsp_hip_pfb_frames(uint32_t hop, uint64_t samples, uint64_t *frames);
+/* taps: p m host doubles.  workspace_bytes: the slice budget (0 = the default, 256 MiB); a slice holds at least one frame.  Errors:
+ * channels_m not a power of two, taps_per_channel = 0 or above the maximum, p m > SDSP_HIP_PFB_MAX_TAPS, hop = 0 or hop > channels_m:
+ * SDSP_HIP_ERR_INVALID_SIZE; channels_m outside the transform range of the kind and precision: SDSP_HIP_ERR_UNSUPPORTED; a null
+ * pointer, a precision other than F32 / F64, an unknown input kind or phase: SDSP_HIP_ERR_INVALID_ARG; no device:
+ * SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_pfb_plan_create(sdsp_hip_pfb_plan **plan, uint32_t channels_m, uint32_t taps_per_channel, uint32_t hop, const double *taps,
+                             int input_kind, int phase, int precision, uint64_t workspace_bytes, int device);
+int sdsp_hip_pfb_plan_destroy(sdsp_hip_pfb_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples) elements.  out: DEVICE pointer, channel c = out[c out_stride .. + F bins)
+ * complex elements.  state: DEVICE pointer or NULL.  position: samples of the stream consumed before this call (phase TIME; ignored for
+ * FRAME).  Asynchronous on `stream`, allocates nothing (stream-capturable); one call per plan in flight.  Errors: samples % hop != 0:
+ * SDSP_HIP_ERR_INVALID_SIZE; null plan, in or out, in_stride < samples or out_stride < F bins with more than one channel, overlapping
+ * in and out ranges, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG.  channels == 0 or samples == 0: nothing to do.
+ */
+int sdsp_hip_pfb_process(sdsp_hip_pfb_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                         uint64_t samples, uint64_t position, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_pfb_process_host(sdsp_hip_pfb_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, uint64_t position, void *host_state);
+/* bytes of a state buffer for `channels` channels: hist channels element size (0 when p = 1 and hop = channels_m) */
+int sdsp_hip_pfb_state_bytes(const sdsp_hip_pfb_plan *plan, uint64_t channels, uint64_t *bytes);
+/* the kernel variant of the inner transform plan (sdsp_hip_fft_plan_set_variant); SDSP_HIP_ERR_UNSUPPORTED where it has no such variant */
+int sdsp_hip_pfb_plan_set_variant(sdsp_hip_pfb_plan *plan, int variant);
+/* measurement and cross-check hook: 0 = the fold form the sizes select (sliding where hop divides channels_m, else plain), 1 = the
+ * plain per-frame form for every hop.  Both forms give the same bits. */
+int sdsp_hip_pfb_plan_set_fold_form(sdsp_hip_pfb_plan *plan, int form);
+/* kernel launches of one process call of `samples` per channel with a state buffer and out_stride = F bins */
+int sdsp_hip_pfb_plan_launches(const sdsp_hip_pfb_plan *plan, uint64_t channels, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t channels_m, taps_per_channel, hop, bins, hist;
+    int input_kind, phase, precision, device;
+    uint64_t workspace_bytes; /* allocated (REAL) or the slice budget in use (COMPLEX) */
+    char kernel[64];          /* the inner transform's kernel */
+    char fold[16];            /* "sliding" or "plain" */
+} sdsp_hip_pfb_plan_info;
+int sdsp_hip_pfb_plan_get_info(const sdsp_hip_pfb_plan *plan, sdsp_hip_pfb_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,18 @@ class WelchPlanInfo(C.Structure):
     ]
 
 
+class PfbPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels_m", C.c_uint32), ("taps_per_channel", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32),
+        ("input_kind", C.c_int), ("phase", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("workspace_bytes", C.c_uint64),
+        ("kernel", C.c_char * 64), ("fold", C.c_char * 16),
+    ]
+
+
+PFB_REAL, PFB_COMPLEX = 0, 1
+PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
+PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
+
 DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR = 0, 1, 2
 SCALING_DENSITY, SCALING_SPECTRUM = 0, 1
 
@@ -211,6 +223,17 @@ SIGNATURES = {
     "sdsp_hip_welch_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_welch_plan_launches": (_i, [_vp, _u64, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_welch_plan_get_info": (_i, [_vp, C.POINTER(WelchPlanInfo)]),
+    "sdsp_hip_pfb_prototype": (_i, [_i, _u32, _u32, _vp]),
+    "sdsp_hip_pfb_frames": (_i, [_u32, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_pfb_plan_create": (_i, [_pp, _u32, _u32, _u32, _vp, _i, _i, _i, _u64, _i]),
+    "sdsp_hip_pfb_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_pfb_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_pfb_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_pfb_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_pfb_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_pfb_plan_set_fold_form": (_i, [_vp, _i]),
+    "sdsp_hip_pfb_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_pfb_plan_get_info": (_i, [_vp, C.POINTER(PfbPlanInfo)]),
 }
 
 _lib = None

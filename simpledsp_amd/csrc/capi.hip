@@ -356,6 +356,15 @@ struct sdsp_hip_welch_plan {
     uint64_t ws_units = 0, workspace_bytes = 0;
 };
 
+struct sdsp_hip_pfb_plan {
+    uint32_t m = 0, p = 0, hop = 0, hist = 0, bins = 0; // hist = p m - hop; bins = m / 2 + 1 (REAL) or m (COMPLEX)
+    int kind = 0, phase = 0, precision = 0, device = 0, form = 0;
+    sdsp_hip_fft_plan *inner = nullptr; // REAL: forward real-input plan of n_real = m, radix 2; COMPLEX: forward complex plan of m, RADIX_AUTO
+    void *taps = nullptr;               // p m values, plan precision
+    void *ws = nullptr;                 // REAL: ws_units x m reals (the slice's folded frames, transformed in place); COMPLEX: none
+    uint64_t ws_units = 0, workspace_bytes = 0;
+};
+
 struct sdsp_hip_filtfilt_plan {
     uint32_t sections = 0, padlen = 0;
     int kind = 0, precision = 0, device = 0, padtype = 0, variant = 0;
@@ -3397,6 +3406,374 @@ int sdsp_hip_welch_finalize_host(sdsp_hip_welch_plan *p, const double *host_acc,
     }
     (void)hipFree(da);
     (void)hipFree(dout);
+    return rc;
+}
+
+// ------------------------------------------------------------------ polyphase filter-bank channelizer banks (pfb.hip)
+
+namespace
+{
+constexpr uint64_t kPfbDefaultBudget = 256ull << 20; // the STFT bank's
+
+uint64_t pfb_in_esize(const sdsp_hip_pfb_plan *p)
+{
+    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    return p->kind == SDSP_HIP_PFB_COMPLEX ? 2 * rs : rs;
+}
+uint64_t pfb_out_esize(const sdsp_hip_pfb_plan *p) { return p->precision == SDSP_HIP_F64 ? 16 : 8; }
+
+// the slice [g0, g0 + units) of the channel-major (channel, frame) numbering as rectangles: a partial first channel, whole channels, a
+// partial last channel.  f(c0, nc, j0, nj) is called for each; a non-zero return stops the walk.
+extern "C++" template <typename F> int pfb_rects(uint64_t g0, uint64_t units, uint64_t frames, F f)
+{
+    uint64_t g = g0;
+    const uint64_t end = g0 + units;
+    while (g < end) {
+        const uint64_t c = g / frames, j = g - c * frames;
+        uint64_t nc = 1, nj;
+        if (j == 0 && end - g >= frames) {
+            nc = (end - g) / frames;
+            nj = frames;
+        } else {
+            nj = std::min(frames - j, end - g);
+        }
+        if (int rc = f(c, nc, static_cast<uint32_t>(j), static_cast<uint32_t>(nj)))
+            return rc;
+        g += nc * nj;
+    }
+    return SDSP_HIP_OK;
+}
+
+int pfb_run(sdsp_hip_pfb_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels, uint64_t samples,
+            uint64_t position, void *state, hipStream_t stream)
+{
+    const uint64_t frames = samples / p->hop;
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames per channel for one call");
+    if (channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * frames;
+    const bool cplx = p->kind == SDSP_HIP_PFB_COMPLEX;
+    const bool whole = cplx && (channels == 1 || out_stride == frames * p->m); // the output rows are one contiguous run of frames
+    if (p->inner->sync) // this call's launches report into a clean sticky abort word (as sdsp_hip_fft_exec)
+        HIP_TRY(hipMemsetAsync(fft1m_sticky(p->inner), 0, sizeof(unsigned), stream));
+    pfb_args a{};
+    a.in = in;
+    a.state = p->hist ? state : nullptr;
+    a.taps = p->taps;
+    a.in_stride = in_stride;
+    a.m = p->m;
+    a.p = p->p;
+    a.hop = p->hop;
+    a.hist = p->hist;
+    a.complex_in = cplx;
+    a.rotate = p->phase == SDSP_HIP_PFB_PHASE_TIME;
+    a.shift0 = static_cast<uint32_t>((position % p->m + p->hop) % p->m); // (position - hist) mod m: hist = p m - hop
+    a.form = p->form;
+    stft_args e{}; // REAL: the STFT bank's emit and state launches
+    e.in = in;
+    e.out = out;
+    e.state = p->hist ? state : nullptr;
+    e.ws = p->ws;
+    e.in_stride = in_stride;
+    e.out_stride = out_stride;
+    e.channels = channels;
+    e.samples = samples;
+    e.frames = static_cast<uint32_t>(frames);
+    e.n = p->m;
+    e.hop = p->hop;
+    e.hist = p->hist;
+    e.output = SDSP_HIP_STFT_COMPLEX;
+    char *const ob = static_cast<char *>(out);
+    const uint64_t oes = pfb_out_esize(p);
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t units = std::min(p->ws_units, total - g0);
+        a.dst = cplx ? out : p->ws;
+        a.dst_cstride = cplx ? out_stride : frames * p->m;
+        a.dst_sub = cplx ? 0 : g0 * p->m;
+        if (int rc = pfb_rects(g0, units, frames, [&](uint64_t c0, uint64_t nc, uint32_t j0, uint32_t nj) {
+                a.c0 = c0;
+                a.nc = nc;
+                a.j0 = j0;
+                a.nj = nj;
+                return launch_pfb(p->precision, a, PFB_FOLD, stream);
+            }))
+            return rc;
+        if (!cplx) {
+            e.g0 = g0;
+            e.units = static_cast<uint32_t>(units);
+            if (int rc = fft_exec_pieces(p->inner, p->ws, units, stream, p->inner->variant))
+                return rc;
+            if (int rc = launch_stft(p->precision, e, STFT_EMIT, stream))
+                return rc;
+        } else if (whole) {
+            if (int rc = fft_exec_pieces(p->inner, ob + g0 * p->m * oes, units, stream, p->inner->variant))
+                return rc;
+        } else { // padded rows: every channel's run of frames on its own
+            if (int rc = pfb_rects(g0, units, frames, [&](uint64_t c0, uint64_t nc, uint32_t j0, uint32_t nj) {
+                    for (uint64_t c = c0; c < c0 + nc; c++)
+                        if (int rc2 = fft_exec_pieces(p->inner, ob + (c * out_stride + static_cast<uint64_t>(j0) * p->m) * oes, nj, stream,
+                                                      p->inner->variant))
+                            return rc2;
+                    return static_cast<int>(SDSP_HIP_OK);
+                }))
+                return rc;
+        }
+    }
+    // after every fold launch: they may read the old history
+    if (!cplx)
+        return launch_stft(p->precision, e, STFT_STATE, stream);
+    a.state_out = p->hist ? state : nullptr;
+    a.channels = channels;
+    a.samples = samples;
+    return launch_pfb(p->precision, a, PFB_STATE, stream);
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int pfb_check(const sdsp_hip_pfb_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride, uint64_t channels,
+              uint64_t samples, uint64_t *frames)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (int rc = sdsp_hip_pfb_frames(p->hop, samples, frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < *frames * p->bins))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= frames * bins");
+    return SDSP_HIP_OK;
+}
+} // namespace
+
+int sdsp_hip_pfb_plan_create(sdsp_hip_pfb_plan **out, uint32_t channels_m, uint32_t taps_per_channel, uint32_t hop, const double *taps,
+                             int input_kind, int phase, int precision, uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    const uint32_t m = channels_m;
+    if (!sdsp_hip_is_power_of_2(m))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels_m must be a power of 2");
+    if (taps_per_channel == 0 || taps_per_channel > SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps_per_channel must be in [1, SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL]");
+    if (static_cast<uint64_t>(m) * taps_per_channel > SDSP_HIP_PFB_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "the prototype may have at most SDSP_HIP_PFB_MAX_TAPS taps");
+    if (hop == 0 || hop > m)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, channels_m]");
+    if (!taps)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "taps pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (input_kind != SDSP_HIP_PFB_REAL && input_kind != SDSP_HIP_PFB_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input_kind must be SDSP_HIP_PFB_REAL or SDSP_HIP_PFB_COMPLEX");
+    if (phase != SDSP_HIP_PFB_PHASE_FRAME && phase != SDSP_HIP_PFB_PHASE_TIME)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "phase must be SDSP_HIP_PFB_PHASE_FRAME or SDSP_HIP_PFB_PHASE_TIME");
+    const bool cplx = input_kind == SDSP_HIP_PFB_COMPLEX;
+    if (m < (cplx ? 16u : 32u) || m > stft_max_n(precision))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED,
+                    "channels_m must be in the transform range (f32 .. 65536, f64 .. 32768; from 32 for real input, 16 for complex)");
+    if (int rc = use_device(device))
+        return rc;
+    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t taps_n = static_cast<uint64_t>(m) * taps_per_channel;
+    const uint64_t unit_bytes = static_cast<uint64_t>(m) * rs * (cplx ? 2 : 1);
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kPfbDefaultBudget;
+    auto *p = new sdsp_hip_pfb_plan();
+    p->m = m;
+    p->p = taps_per_channel;
+    p->hop = hop;
+    p->hist = static_cast<uint32_t>(taps_n - hop);
+    p->bins = cplx ? m : m / 2 + 1;
+    p->kind = input_kind;
+    p->phase = phase;
+    p->precision = precision;
+    p->device = device;
+    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->workspace_bytes = p->ws_units * unit_bytes;
+    int rc = cplx ? fft_plan_create(&p->inner, m, SDSP_HIP_RADIX_AUTO, SDSP_HIP_FORWARD, precision, p->ws_units, device, 0)
+                  : fft_plan_create(&p->inner, m / 2, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device, 1);
+    if (!rc) {
+        hipError_t e = cplx ? hipSuccess : hipMalloc(&p->ws, p->workspace_bytes);
+        if (e == hipSuccess)
+            e = hipMalloc(&p->taps, taps_n * rs);
+        if (e == hipSuccess) { // rounded once to the plan precision
+            if (precision == SDSP_HIP_F64) {
+                e = hipMemcpy(p->taps, taps, taps_n * rs, hipMemcpyHostToDevice);
+            } else {
+                const std::vector<float> hf(taps, taps + taps_n);
+                e = hipMemcpy(p->taps, hf.data(), taps_n * rs, hipMemcpyHostToDevice);
+            }
+        }
+        if (e != hipSuccess)
+            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "pfb plan: out of device memory") : hip_fail(e, "pfb plan");
+    }
+    if (rc) {
+        sdsp_hip_pfb_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_plan_destroy(sdsp_hip_pfb_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->ws);
+        (void)hipFree(p->taps);
+    }
+    if (p->inner)
+        sdsp_hip_fft_plan_destroy(p->inner);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_state_bytes(const sdsp_hip_pfb_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * pfb_in_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_plan_set_variant(sdsp_hip_pfb_plan *p, int variant)
+{
+    if (!p || variant < 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
+    const fft_kernel_sel sel = select_kernel(p->inner, variant);
+    if (sel.id == K_UNSUPPORTED)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the inner plan has no such kernel variant");
+    if (int rc = check_table(p->inner, sel))
+        return rc;
+    if (sel.workspace) { // a multi-pass alternate of a single-pass default: its workspace is allocated here, not on the launch path
+        if (int rc = use_device(p->device))
+            return rc;
+        if (int rc = ensure_workspace(p->inner))
+            return rc;
+    }
+    p->inner->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_plan_set_fold_form(sdsp_hip_pfb_plan *p, int form)
+{
+    if (!p || (form != 0 && form != 1))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "form must be 0 (chosen from the sizes) or 1 (plain)");
+    p->form = form;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_plan_get_info(const sdsp_hip_pfb_plan *p, sdsp_hip_pfb_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->channels_m = p->m;
+    info->taps_per_channel = p->p;
+    info->hop = p->hop;
+    info->bins = p->bins;
+    info->hist = p->hist;
+    info->input_kind = p->kind;
+    info->phase = p->phase;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->workspace_bytes = p->workspace_bytes;
+    std::strncpy(info->kernel, select_kernel(p->inner, p->inner->variant).name, sizeof(info->kernel) - 1);
+    std::strncpy(info->fold, p->form ? "plain" : pfb_form_for(p->m, p->hop), sizeof(info->fold) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_plan_launches(const sdsp_hip_pfb_plan *p, uint64_t channels, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_pfb_frames(p->hop, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t total = channels * frames;
+    uint64_t n = 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t units = std::min(p->ws_units, total - g0);
+        pfb_rects(g0, units, frames, [&](uint64_t, uint64_t, uint32_t, uint32_t) {
+            n++;
+            return 0;
+        });
+        n += fft_launch_count(p->inner, units, p->inner->variant) + (p->kind == SDSP_HIP_PFB_REAL ? 1 : 0);
+    }
+    *launches = n + (p->hist ? 1 : 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_process(sdsp_hip_pfb_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                         uint64_t samples, uint64_t position, void *state, void *stream)
+{
+    uint64_t frames = 0;
+    if (int rc = pfb_check(p, in, in_stride, out, out_stride, channels, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t ies = pfb_in_esize(p), oes = pfb_out_esize(p);
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + samples) * ies;
+    const uintptr_t o1 = o0 + ((channels - 1) * out_stride + frames * p->bins) * oes;
+    if (i0 < o1 && o0 < i1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the filter bank runs out of place)");
+    if (i0 % ies || o0 % oes || reinterpret_cast<uintptr_t>(state) % ies)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return pfb_run(p, in, in_stride, out, out_stride, channels, samples, position, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_pfb_process_host(sdsp_hip_pfb_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, uint64_t position, void *host_state)
+{
+    uint64_t frames = 0;
+    if (int rc = pfb_check(p, host_in, in_stride, host_out, out_stride, channels, samples, &frames))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * pfb_in_esize(p);
+    const size_t out_bytes = ((channels - 1) * out_stride + frames * p->bins) * pfb_out_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_pfb_state_bytes(p, channels, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    void *di = nullptr, *dout = nullptr, *s = nullptr;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&di, in_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&dout, out_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) // rows of out past F bins keep what the caller had there
+        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && with_state) {
+        e = hipMalloc(&s, state_bytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+        rc = hip_fail(e, "pfb host staging");
+    if (!rc)
+        rc = pfb_run(p, di, in_stride, dout, out_stride, channels, samples, position, s, nullptr);
+    if (!rc) {
+        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && with_state)
+            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = hip_fail(e, "pfb host read-back");
+    }
+    (void)hipFree(di);
+    (void)hipFree(dout);
+    (void)hipFree(s);
     return rc;
 }
 }

@@ -184,6 +184,38 @@ int design_bs(uint32_t m, double f0, double fs, double q, double gain_in, double
     return SDSP_HIP_OK;
 }
 
+// firwin's construction, shared by design_fir and the filter-bank prototype: the ideal responses of the pass bands (left, right
+// edges as fractions of Nyquist) times the SYMMETRIC window of `taps` points, scaled to `gain` at DC / Nyquist / the first band's centre
+static void windowed_sinc(uint64_t taps, const double (*bands)[2], int nb, int window_kind, double gain, double *h)
+{
+    auto sinc = [](double x) { return x == 0 ? 1.0 : std::sin(M_PI * x) / (M_PI * x); };
+    const double alpha = 0.5 * (taps - 1);
+    for (uint64_t i = 0; i < taps; i++) {
+        const double m = i - alpha;
+        double v = 0;
+        for (int bnd = 0; bnd < nb; bnd++)
+            v += bands[bnd][1] * sinc(bands[bnd][1] * m) - bands[bnd][0] * sinc(bands[bnd][0] * m);
+        double w = 1.0;
+        if (taps > 1) {
+            const double c1 = std::cos(2 * M_PI * i / (taps - 1));
+            switch (window_kind) {
+            case SDSP_HIP_WINDOW_RECT: w = 1.0; break;
+            case SDSP_HIP_WINDOW_HANN: w = 0.5 - 0.5 * c1; break;
+            case SDSP_HIP_WINDOW_HAMMING: w = 0.54 - 0.46 * c1; break;
+            default: w = 0.42 - 0.5 * c1 + 0.08 * std::cos(4 * M_PI * i / (taps - 1)); break;
+            }
+        }
+        h[i] = v * w;
+    }
+    const double left = bands[0][0], right = bands[0][1];
+    const double scale_frequency = left == 0 ? 0.0 : (right == 1 ? 1.0 : 0.5 * (left + right));
+    double s = 0;
+    for (uint64_t i = 0; i < taps; i++)
+        s += h[i] * std::cos(M_PI * (i - alpha) * scale_frequency);
+    for (uint64_t i = 0; i < taps; i++)
+        h[i] = h[i] / s * gain;
+}
+
 // FIR design -- the reference's README.md:16 TODO; no reference code.  Windowed-sinc (Hamming) design,
 // the same construction as scipy.signal.firwin (which the tests pin it to): ideal band responses
 // sum(right sinc(right m) - left sinc(left m)) over the pass bands, times the symmetric Hamming window,
@@ -219,23 +251,15 @@ int design_fir(uint32_t taps, int filter_type, double f0, double fs, double q, d
     else if (filter_type == SDSP_HIP_FILTER_BAND_PASS) { bands[nb][0] = lo; bands[nb++][1] = hi; }
     else { bands[nb][0] = 0; bands[nb++][1] = lo; bands[nb][0] = hi; bands[nb++][1] = 1; }
     (void)pass_zero;
-    auto sinc = [](double x) { return x == 0 ? 1.0 : std::sin(M_PI * x) / (M_PI * x); };
-    const double alpha = 0.5 * (taps - 1);
-    for (uint32_t i = 0; i < taps; i++) {
-        const double m = i - alpha;
-        double v = 0;
-        for (int bnd = 0; bnd < nb; bnd++)
-            v += bands[bnd][1] * sinc(bands[bnd][1] * m) - bands[bnd][0] * sinc(bands[bnd][0] * m);
-        const double w = taps == 1 ? 1.0 : 0.54 - 0.46 * std::cos(2 * M_PI * i / (taps - 1));
-        h[i] = v * w;
-    }
-    const double left = bands[0][0], right = bands[0][1];
-    const double scale_frequency = left == 0 ? 0.0 : (right == 1 ? 1.0 : 0.5 * (left + right));
-    double s = 0;
-    for (uint32_t i = 0; i < taps; i++)
-        s += h[i] * std::cos(M_PI * (i - alpha) * scale_frequency);
-    for (uint32_t i = 0; i < taps; i++)
-        h[i] = h[i] / s * gain_in;
+    windowed_sinc(taps, bands, nb, SDSP_HIP_WINDOW_HAMMING, gain_in, h);
+    return SDSP_HIP_OK;
+}
+
+// the polyphase filter bank's prototype: the same construction with one pass band [0, cutoff] and any of the four windows
+int windowed_sinc_lowpass(uint64_t taps, double cutoff, int window_kind, double *h)
+{
+    const double bands[1][2] = { { 0.0, cutoff } };
+    windowed_sinc(taps, bands, 1, window_kind, 1.0, h);
     return SDSP_HIP_OK;
 }
 
@@ -502,6 +526,17 @@ int sdsp_hip_stft_frames(uint32_t hop, uint64_t samples, uint64_t *frames)
         return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be a multiple of hop");
     *frames = samples / hop;
     return SDSP_HIP_OK;
+}
+int sdsp_hip_pfb_frames(uint32_t hop, uint64_t samples, uint64_t *frames) { return sdsp_hip_stft_frames(hop, samples, frames); }
+int sdsp_hip_pfb_prototype(int window_kind, uint32_t m, uint32_t p, double *h)
+{
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    if (window_kind < SDSP_HIP_WINDOW_RECT || window_kind > SDSP_HIP_WINDOW_BLACKMAN)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window kind must be SDSP_HIP_WINDOW_RECT / HANN / HAMMING / BLACKMAN");
+    if (m < 2 || p == 0 || p > SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL || static_cast<uint64_t>(m) * p > SDSP_HIP_PFB_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "need m >= 2, 1 <= p <= SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL and p m <= SDSP_HIP_PFB_MAX_TAPS");
+    return windowed_sinc_lowpass(static_cast<uint64_t>(m) * p, 1.0 / m, window_kind, h);
 }
 int sdsp_hip_welch_frames(uint32_t n_fft, uint32_t hop, uint64_t position, uint64_t samples, uint64_t *frames)
 {

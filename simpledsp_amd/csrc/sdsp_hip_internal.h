@@ -315,4 +315,27 @@ struct welch_args {
     double c_edge, c_mid; // finalize: c_k for k = 0, N / 2 and for the bins between
 };
 int launch_welch(int precision, const welch_args &a, int step, void *stream);
+// polyphase filter-bank channelizers (pfb.hip): the fold launch of one rectangle of (channel, frame) units in
+// front of the plan's transform, and the state launch for complex elements (real banks use the STFT bank's, STFT_STATE)
+enum { PFB_FOLD = 0, PFB_STATE = 1 };
+struct pfb_args {
+    const void *in;
+    const void *state;  // nullable; channels x hist elements, newest first
+    const void *taps;   // device, plan precision, p x m reals
+    void *dst;          // fold: frame j of channel c at dst + (c dst_cstride + j m - dst_sub) elements
+    void *state_out;    // state launch
+    uint64_t in_stride, channels, samples; // state launch: the whole call
+    uint64_t dst_cstride, dst_sub;
+    uint64_t c0, nc;    // fold: channels [c0, c0 + nc)
+    uint32_t j0, nj;    // fold: frames [j0, j0 + nj) of each
+    uint32_t m, p, hop, hist;
+    uint32_t shift0;    // TIME: frame j is rotated by (shift0 + j hop) mod m; FRAME: rotate = 0
+    int complex_in, rotate;
+    int form;           // 0: chosen from hop and m; 1: the plain per-frame form (measurement and cross-checks)
+};
+int launch_pfb(int precision, const pfb_args &a, int step, void *stream);
+// the fold form a plan of these sizes runs: "sliding" where hop divides m, else "plain"
+const char *pfb_form_for(uint32_t m, uint32_t hop);
+// host_math.cpp: symmetric-window sinc low-pass of `taps` points with cutoff `cutoff` (fraction of Nyquist) and unit DC gain
+int windowed_sinc_lowpass(uint64_t taps, double cutoff, int window_kind, double *h);
 } // namespace sdsp_hip
