@@ -137,7 +137,10 @@ int sdsp_hip_fft_plan_create(sdsp_hip_fft_plan **plan, uint32_t n, int radix, in
 int sdsp_hip_fft_plan_destroy(sdsp_hip_fft_plan *plan);
 
 /* data: DEVICE pointer, batch x n interleaved complex of the plan precision, transformed in
- * place.  Asynchronous on `stream`. */
+ * place.  Asynchronous on `stream`.  Alignment: `data` must be aligned to ONE complex element of the plan precision (8 bytes
+ * in f32, 16 in f64; real-input plans included: a pointer aligned to one real sample only is SDSP_HIP_ERR_INVALID_ARG) and
+ * needs no more than that: every kernel takes such a pointer and gives the bits of an allocator-aligned one
+ * (tests/test_gpu_isolation.py).  The same holds for `data` and `h` of sdsp_hip_fft_convolve. */
 int sdsp_hip_fft_exec(sdsp_hip_fft_plan *plan, void *data, uint64_t batch, void *stream);
 /* same with a HOST pointer: H2D, transform, D2H, synchronous (the single-call drop-in path) */
 int sdsp_hip_fft_exec_host(sdsp_hip_fft_plan *plan, void *host_data, uint64_t batch);
@@ -358,7 +361,9 @@ int sdsp_hip_fir_plan_set_variant(sdsp_hip_fir_plan *plan, int variant);
  * FFT-domain FIR plans (overlap-save) for long filters: the same filter as a direct plan of the same h,
  * computed per frame of N = fft_n inputs as IFFT(FFT(frame) .* H) with H = FFT(h zero-padded to N), computed in double at
  * creation and rounded once to the plan precision.  Hop L = N - taps + 1 outputs per frame; N >= 2 (taps - 1).  Two frames
- * of one channel share one complex transform (real / imaginary part).  Rounding differs from the direct form (the error is
+ * of one channel share one complex transform (real / imaginary part): a NaN or Inf input reaches every output of the frame
+ * pairs (frames 2p and 2p + 1) whose frames read it, not only the `taps` outputs that depend on it, and no other channel.
+ * Rounding differs from the direct form (the error is
  * normwise per frame pair, ~1e-7 in f32, ~1e-15 in f64), so block-by-block calls match one long call within that
  * tolerance, not bit for bit.
  * sdsp_hip_fir_process / _process_host / _state_bytes / _plan_set_variant / _plan_destroy take these plans with the same

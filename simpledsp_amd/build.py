@@ -82,7 +82,28 @@ def _dep_files(dfile: Path):
     for line in text.splitlines():
         if ":" in line:
             deps += line.split(":", 1)[1].split()
-    return [Path(d) for d in deps]
+    return [_in_tree(Path(d)) for d in deps]
+
+
+def _in_tree(dep: Path) -> Path:
+    """a prerequisite recorded under another root -- the build directory moved with its tree, or the tree is reached through
+    another path than the one the objects were compiled under -- is this tree's file of the same relative name where there is
+    one: staleness is about the sources the next build would read, not about where they lay when the object was made"""
+    try:
+        dep.relative_to(ROOT)
+        return dep
+    except ValueError:
+        pass
+    parts = dep.parts
+    for anchor in (("simpledsp_amd", "csrc"), ("include",)):
+        k = len(anchor)
+        for i in range(len(parts) - k - 1, -1, -1):
+            if parts[i:i + k] == anchor:
+                here = ROOT.joinpath(*parts[i:])
+                if here.is_file():
+                    return here
+                break
+    return dep
 
 
 def _stale(target: Path, deps) -> bool:

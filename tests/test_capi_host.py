@@ -211,6 +211,24 @@ def test_a_touched_kernel_header_makes_its_objects_stale():
     assert not B.object_stale(big, B.CSRC / "fft_big.hip")
 
 
+def test_dependency_lists_written_under_another_root_track_this_tree(tmp_path):
+    """a dependency file that names the sources under another root (objects compiled in one checkout and moved with their tree,
+    or a tree reached through another path) is read as this tree's files where they exist: the touched-header rule above
+    holds for such objects too; prerequisites that this tree does not have stay as written (missing: the object is stale)"""
+    from simpledsp_amd import build as B
+    other = tmp_path / "elsewhere" / "tree"
+    d = tmp_path / "fft_big.d"
+    d.write_text(f"{tmp_path}/fft_big.o: {B.CSRC / 'fft_big.hip'} \\\n  {other}/simpledsp_amd/csrc/fft32.h \\\n"
+                 f"  {other}/simpledsp_amd/csrc/fft32_r4.h \\\n  {other}/include/sdsp_hip.h \\\n"
+                 f"  {other}/simpledsp_amd/csrc/no_such_header.h\n")
+    deps = B._dep_files(d)
+    assert deps[:4] == [B.CSRC / "fft_big.hip", B.CSRC / "fft32.h", B.CSRC / "fft32_r4.h", B.ROOT / "include" / "sdsp_hip.h"]
+    assert deps[4] == other / "simpledsp_amd" / "csrc" / "no_such_header.h"
+    obj = tmp_path / "fft_big.o"
+    obj.write_bytes(b"")
+    assert B.object_stale(obj, B.CSRC / "fft_big.hip")  # a prerequisite that exists nowhere
+
+
 def test_loader_refuses_a_library_built_from_other_sources(monkeypatch):
     """the in-tree .so is what travels to the GPU box: one whose embedded source hash differs from the tree is refused"""
     import simpledsp_amd._lib as L

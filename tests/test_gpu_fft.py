@@ -143,7 +143,7 @@ def test_register_pass_family_ragged_and_variants(sd, torch_cuda, oracle, n, rad
             if variant == 2 and not big and (n, radix) != (4096, 2):
                 assert plan.info.kernel.decode() == ("sdsp_fft1024_wave" if n == 1024 else "sdsp_fft_wave_f32" if wave2 else "sdsp_fft_reg_kernel")
             d = torch.from_numpy(x).cuda()
-            guard = torch.full((64,), 7.0 + 3.0j, dtype=torch.complex64, device="cuda")  # overrun detector
+            guard = torch.full((64,), 7.0 + 3.0j, dtype=torch.complex64, device="cuda")  # overrun detector (weak: not adjacent; the framed tests are tests/test_gpu_isolation.py)
             plan.exec(d)
             torch.cuda.synchronize()
             outs.append(d.cpu().numpy())
