@@ -1,10 +1,13 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
-// multi-device convenience paths.  Everything that computes goes to the HIP kernels in
-// fft_tile.hip / fft4096.hip / iir.hip; there is no CPU implementation behind these entry points.
+// multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
+// transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample) and the framed banks (stft, istft, welch, pfb); there is no CPU implementation
+// behind these entry points.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <thread>
 #include <vector>
 
@@ -56,9 +59,85 @@ int use_device(int device)
     return SDSP_HIP_OK;
 }
 
-size_t esize(int precision) { return precision == SDSP_HIP_F64 ? 16 : 8; } // one complex element
+size_t esize(int precision) { return precision == SDSP_HIP_F64 ? 16 : 8; }    // one complex element
+size_t real_size(int precision) { return precision == SDSP_HIP_F64 ? 8 : 4; } // one real sample (the mixed mode stores floats)
 
-// round a double table to the plan precision and park it in HBM
+bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+bool misaligned(const void *ptr, uint64_t element_bytes) { return reinterpret_cast<uintptr_t>(ptr) % element_bytes != 0; }
+
+// what the out-of-place framed banks ask of their device pointers: in and out apart, and in, out and state (null passes) aligned
+// to their element size
+int check_out_of_place(const void *in, uint64_t in_bytes, uint64_t in_esize, const void *out, uint64_t out_bytes, uint64_t out_esize,
+                       const void *state, uint64_t state_esize, const char *overlap_msg)
+{
+    if (ranges_overlap(in, in_bytes, out, out_bytes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, overlap_msg);
+    if (misaligned(in, in_esize) || misaligned(out, out_esize) || misaligned(state, state_esize))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    return SDSP_HIP_OK;
+}
+
+// The device side of every *_process_host / *_finalize_host call.  Each host buffer gets a device buffer of its size, filled from
+// it before the run -- outputs too, so that what lies between and behind their rows keeps what the caller had there -- and the ones
+// flagged `copy_back` return after a run that succeeded.  An item whose host pointer is null is absent: its device pointer stays
+// null.  Everything is freed when the stage goes out of scope.
+struct host_stage {
+    struct item {
+        const void *host;
+        size_t bytes;
+        bool copy_back; // `host` is writable where this is set
+    };
+    const char *family;
+    item items[3] = {};
+    void *dev[3] = {};
+    size_t n = 0;
+
+    host_stage(const char *family_, std::initializer_list<item> list) : family(family_)
+    {
+        for (const item &it : list)
+            items[n++] = it;
+    }
+    host_stage(const host_stage &) = delete;
+    host_stage &operator=(const host_stage &) = delete;
+    ~host_stage()
+    {
+        for (void *d : dev)
+            (void)hipFree(d);
+    }
+    // every allocation, then every copy to the device
+    int in()
+    {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < n && e == hipSuccess; i++)
+            if (items[i].host)
+                e = hipMalloc(&dev[i], items[i].bytes);
+        for (size_t i = 0; i < n && e == hipSuccess; i++)
+            if (items[i].host)
+                e = hipMemcpy(dev[i], items[i].host, items[i].bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess ? SDSP_HIP_OK : hip_fail(e, (std::string(family) + " host staging").c_str());
+    }
+    // the call's result: `rc` of a run that failed (nothing is copied back), else that of the copies back
+    int out(int rc)
+    {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < n && !rc && e == hipSuccess; i++)
+            if (items[i].host && items[i].copy_back)
+                e = hipMemcpy(const_cast<void *>(items[i].host), dev[i], items[i].bytes, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? rc : hip_fail(e, (std::string(family) + " host read-back").c_str());
+    }
+};
+
+// units per workspace slice of a framed plan: what the budget holds, at least one; the kernels count a slice's units in 32 bits
+uint64_t slice_units(uint64_t budget, uint64_t unit_bytes)
+{
+    return std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+}
+
 // launch granularity, sdsp_hip.h: sdsp_hip_set_launch_piece_bytes
 std::atomic<uint64_t> g_piece_bytes{ SDSP_HIP_DEFAULT_PIECE_BYTES };
 
@@ -73,6 +152,7 @@ uint64_t piece_units(uint64_t units, uint64_t unit_bytes, uint64_t multiple)
     return u ? u : multiple;
 }
 
+// round a double table to the plan precision and park it in HBM
 int upload_twiddles(const std::vector<double> &w, int precision, void **dev)
 {
     const size_t n = w.size() / 2;
@@ -87,6 +167,26 @@ int upload_twiddles(const std::vector<double> &w, int precision, void **dev)
         HIP_TRY(hipMemcpy(*dev, wf.data(), n * 8, hipMemcpyHostToDevice));
     }
     return SDSP_HIP_OK;
+}
+
+// its sibling for the real tables (windows, taps): n values rounded once, by conversion, to the plan precision.  The HIP error comes
+// back as it is, since what a failed creation reports differs by family; *dev is the caller's to free either way.
+hipError_t upload_reals(const double *src, size_t n, int precision, void **dev)
+{
+    const hipError_t e = hipMalloc(dev, n * real_size(precision));
+    if (e != hipSuccess)
+        return e;
+    if (precision == SDSP_HIP_F64)
+        return hipMemcpy(*dev, src, n * sizeof(double), hipMemcpyHostToDevice);
+    const std::vector<float> f(src, src + n);
+    return hipMemcpy(*dev, f.data(), n * sizeof(float), hipMemcpyHostToDevice);
+}
+
+// a HIP error of plan creation, as the families with plan-owned workspaces report it: out of memory has a code of its own
+int plan_fail(hipError_t e, const char *family)
+{
+    const std::string what = std::string(family) + " plan";
+    return e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, what + ": out of device memory") : hip_fail(e, what.c_str());
 }
 
 // Thread-twiddle table of the tuned N = 4096 f32 kernels (fft4096.hip): the stage twiddles each thread needs,
@@ -937,6 +1037,49 @@ int fft1m_check_sticky(sdsp_hip_fft_plan *p)
     return SDSP_HIP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// What the framed banks (STFT, inverse STFT, Welch, filter bank) share around their inner FFT plan.
+
+// The kernel variant of a bank's inner plan.  Rejected here rather than at the next process call: a variant without a kernel, or whose
+// kernel needs a table this size's plan does not upload.  `with_workspace`: a multi-pass alternate of a single-pass default gets
+// its workspace here, not on the launch path.
+int set_inner_variant(sdsp_hip_fft_plan *inner, int variant, const char *unsupported_msg, bool with_workspace = false)
+{
+    const fft_kernel_sel sel = select_kernel(inner, variant);
+    if (sel.id == K_UNSUPPORTED)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, unsupported_msg);
+    if (int rc = check_table(inner, sel))
+        return rc;
+    if (with_workspace && sel.workspace) {
+        if (int rc = use_device(inner->device))
+            return rc;
+        if (int rc = ensure_workspace(inner))
+            return rc;
+    }
+    inner->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+// kernel launches of a bank's slice loop over `total` units: per slice, `own` launches of the bank and the inner transform's
+uint64_t slice_launch_count(const sdsp_hip_fft_plan *inner, uint64_t total, uint64_t ws_units, uint64_t own)
+{
+    uint64_t n = 0;
+    for (uint64_t g0 = 0; g0 < total; g0 += ws_units)
+        n += own + fft_launch_count(inner, std::min(ws_units, total - g0), inner->variant);
+    return n;
+}
+
+// the device side of a bank's plan_destroy: its workspace, its table (window or taps) and its inner plan
+void free_bank(int device, void *ws, void *table, sdsp_hip_fft_plan *inner)
+{
+    if (use_device(device) == SDSP_HIP_OK) {
+        (void)hipFree(ws);
+        (void)hipFree(table);
+    }
+    if (inner)
+        sdsp_hip_fft_plan_destroy(inner);
+}
+
 } // namespace
 
 extern "C" {
@@ -1602,33 +1745,15 @@ int sdsp_hip_iir_process_host(sdsp_hip_iir_plan *p, void *host_data, uint64_t ch
         return fail(SDSP_HIP_ERR_INVALID_ARG, "data is null");
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4; // sample size (the mixed mode stores floats)
+    const size_t rs = real_size(p->precision); // sample size (the mixed mode stores floats)
     const size_t data_bytes = ((channels - 1) * stride + samples) * rs;
     uint64_t state_bytes = 0;
     sdsp_hip_iir_state_bytes(p, channels, &state_bytes);
-    void *d = nullptr, *s = nullptr;
-    HIP_TRY(hipMalloc(&d, data_bytes));
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMemcpy(d, host_data, data_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && host_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "iir host staging");
+    host_stage st("iir", { { host_data, data_bytes, true }, { host_state, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = sdsp_hip_iir_process(p, d, channels, samples, stride, s, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_data, d, data_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && host_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "iir host read-back");
-    }
-    (void)hipFree(d);
-    (void)hipFree(s);
-    return rc;
+        rc = sdsp_hip_iir_process(p, st.dev[0], channels, samples, stride, st.dev[1], nullptr);
+    return st.out(rc);
 }
 
 int sdsp_hip_iir_process_sharded(sdsp_hip_iir_plan *const *plans, int n_plans, void *host_data, uint64_t channels,
@@ -1643,7 +1768,7 @@ int sdsp_hip_iir_process_sharded(sdsp_hip_iir_plan *const *plans, int n_plans, v
         return SDSP_HIP_OK;
     if (!host_data)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "data is null");
-    const size_t row = samples * (plans[0]->precision == SDSP_HIP_F64 ? 8 : 4);
+    const size_t row = samples * real_size(plans[0]->precision);
     std::vector<int> rcs(n_plans, 0);
     std::vector<std::string> errs(n_plans);
     std::vector<std::thread> th;
@@ -1682,17 +1807,7 @@ int sdsp_hip_fir_plan_create(sdsp_hip_fir_plan **out, uint32_t taps, const doubl
     p->taps = taps;
     p->precision = precision;
     p->device = device;
-    hipError_t e;
-    if (precision == SDSP_HIP_F64) {
-        e = hipMalloc(&p->h_dev, taps * sizeof(double));
-        if (e == hipSuccess)
-            e = hipMemcpy(p->h_dev, h, taps * sizeof(double), hipMemcpyHostToDevice);
-    } else {
-        std::vector<float> hf(h, h + taps);
-        e = hipMalloc(&p->h_dev, taps * sizeof(float));
-        if (e == hipSuccess)
-            e = hipMemcpy(p->h_dev, hf.data(), taps * sizeof(float), hipMemcpyHostToDevice);
-    }
+    const hipError_t e = upload_reals(h, taps, precision, &p->h_dev);
     if (e != hipSuccess) {
         (void)hipFree(p->h_dev);
         delete p;
@@ -1818,7 +1933,7 @@ std::vector<double> fir_fft_response(const double *h, uint32_t taps, uint32_t n)
 
 int fir_fft_process(sdsp_hip_fir_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride, void *state, void *stream)
 {
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t rs = real_size(p->precision);
     const uint32_t t1 = p->taps - 1;
     uint64_t frames = 0, pairs = 0;
     fir_fft_grid(p, samples, &frames, &pairs);
@@ -1897,7 +2012,7 @@ int sdsp_hip_fir_fft_plan_create(sdsp_hip_fir_plan **out, uint32_t taps, const d
     }
     if (int rc = use_device(device))
         return rc;
-    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t rs = real_size(precision);
     const uint64_t unit_bytes = 2ull * fft_n * rs + static_cast<uint64_t>(taps - 1) * rs; // one frame pair + its staged history
     const uint64_t budget = workspace_bytes ? workspace_bytes : kFirFftDefaultBudget;
     auto *p = new sdsp_hip_fir_plan();
@@ -1916,26 +2031,15 @@ int sdsp_hip_fir_fft_plan_create(sdsp_hip_fir_plan **out, uint32_t taps, const d
         hipError_t e = hipMalloc(&p->ws, p->ws_units * unit_bytes);
         if (e == hipSuccess)
             e = hipMalloc(&p->carry, std::max<size_t>(1, 2ull * (taps - 1) * rs));
+        // coefficients and response rounded once to the plan precision (the twiddle-table convention)
         if (e == hipSuccess)
-            e = hipMalloc(&p->h_dev, taps * rs);
-        if (e == hipSuccess)
-            e = hipMalloc(&p->H, 2ull * fft_n * rs);
+            e = upload_reals(h, taps, precision, &p->h_dev);
         if (e == hipSuccess) {
-            // coefficients and response rounded once to the plan precision (the twiddle-table convention)
-            const std::vector<double> resp = fir_fft_response(h, taps, fft_n);
-            if (precision == SDSP_HIP_F64) {
-                e = hipMemcpy(p->h_dev, h, taps * rs, hipMemcpyHostToDevice);
-                if (e == hipSuccess)
-                    e = hipMemcpy(p->H, resp.data(), resp.size() * rs, hipMemcpyHostToDevice);
-            } else {
-                const std::vector<float> hf(h, h + taps), rf(resp.begin(), resp.end());
-                e = hipMemcpy(p->h_dev, hf.data(), taps * rs, hipMemcpyHostToDevice);
-                if (e == hipSuccess)
-                    e = hipMemcpy(p->H, rf.data(), rf.size() * rs, hipMemcpyHostToDevice);
-            }
+            const std::vector<double> resp = fir_fft_response(h, taps, fft_n); // fft_n complex values, re and im interleaved
+            e = upload_reals(resp.data(), resp.size(), precision, &p->H);
         }
         if (e != hipSuccess)
-            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "fir fft plan: out of device memory") : hip_fail(e, "fir fft plan");
+            rc = plan_fail(e, "fir fft");
     }
     if (rc) {
         sdsp_hip_fir_plan_destroy(p);
@@ -1991,7 +2095,7 @@ int sdsp_hip_fir_state_bytes(const sdsp_hip_fir_plan *p, uint64_t channels, uint
 {
     if (!p || !bytes)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
-    *bytes = static_cast<uint64_t>(p->taps - 1) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    *bytes = static_cast<uint64_t>(p->taps - 1) * channels * real_size(p->precision);
     return SDSP_HIP_OK;
 }
 
@@ -2045,34 +2149,15 @@ int sdsp_hip_fir_process_host(sdsp_hip_fir_plan *p, void *host_data, uint64_t ch
         return fail(SDSP_HIP_ERR_INVALID_ARG, "data is null");
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    const size_t data_bytes = ((channels - 1) * stride + samples) * rs;
+    const size_t data_bytes = ((channels - 1) * stride + samples) * real_size(p->precision);
     uint64_t state_bytes = 0;
     sdsp_hip_fir_state_bytes(p, channels, &state_bytes);
     const bool with_state = host_state && state_bytes;
-    void *d = nullptr, *s = nullptr;
-    HIP_TRY(hipMalloc(&d, data_bytes));
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMemcpy(d, host_data, data_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && with_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "fir host staging");
+    host_stage st("fir", { { host_data, data_bytes, true }, { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = sdsp_hip_fir_process(p, d, channels, samples, stride, s, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_data, d, data_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && with_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "fir host read-back");
-    }
-    (void)hipFree(d);
-    (void)hipFree(s);
-    return rc;
+        rc = sdsp_hip_fir_process(p, st.dev[0], channels, samples, stride, st.dev[1], nullptr);
+    return st.out(rc);
 }
 
 // ------------------------------------------------------------------ polyphase FIR resampler banks (fir_resample.hip)
@@ -2107,11 +2192,7 @@ int sdsp_hip_resample_plan_create(sdsp_hip_resample_plan **out, uint32_t taps, c
     p->hist = (taps - 1) / up;
     p->precision = precision;
     p->device = device;
-    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
-    std::vector<float> hf(h, h + taps);
-    hipError_t e = hipMalloc(&p->h_dev, taps * rs);
-    if (e == hipSuccess)
-        e = hipMemcpy(p->h_dev, precision == SDSP_HIP_F64 ? static_cast<const void *>(h) : hf.data(), taps * rs, hipMemcpyHostToDevice);
+    const hipError_t e = upload_reals(h, taps, precision, &p->h_dev);
     if (e != hipSuccess) {
         (void)hipFree(p->h_dev);
         delete p;
@@ -2135,7 +2216,7 @@ int sdsp_hip_resample_state_bytes(const sdsp_hip_resample_plan *p, uint64_t chan
 {
     if (!p || !bytes)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
-    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    *bytes = static_cast<uint64_t>(p->hist) * channels * real_size(p->precision);
     return SDSP_HIP_OK;
 }
 
@@ -2182,10 +2263,8 @@ int sdsp_hip_resample_process(sdsp_hip_resample_plan *p, const void *in, uint64_
         return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
     if (channels > 1 && (in_stride < samples || out_stride < outs))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= samples * up / down");
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + samples) * rs, o1 = o0 + ((channels - 1) * out_stride + outs) * rs;
-    if (i0 < o1 && o0 < i1)
+    const uint64_t rs = real_size(p->precision);
+    if (ranges_overlap(in, ((channels - 1) * in_stride + samples) * rs, out, ((channels - 1) * out_stride + outs) * rs))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the resampler runs out of place)");
     if (int rc = use_device(p->device))
         return rc;
@@ -2220,41 +2299,18 @@ int sdsp_hip_resample_process_host(sdsp_hip_resample_plan *p, const void *host_i
         return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= samples * up / down");
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t rs = real_size(p->precision);
     const size_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
     const size_t out_bytes = ((channels - 1) * out_stride + outs) * rs;
     uint64_t state_bytes = 0;
     sdsp_hip_resample_state_bytes(p, channels, &state_bytes);
     const bool with_state = host_state && state_bytes;
-    void *di = nullptr, *dout = nullptr, *s = nullptr;
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMalloc(&di, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc(&dout, out_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) // rows of out past S U / D keep what the caller had there
-        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && with_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "resample host staging");
+    host_stage st("resample", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                            { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = sdsp_hip_resample_process(p, di, in_stride, dout, out_stride, channels, samples, s, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && with_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "resample host read-back");
-    }
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(s);
-    return rc;
+        rc = sdsp_hip_resample_process(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, st.dev[2], nullptr);
+    return st.out(rc);
 }
 
 // ------------------------------------------------------------------ STFT banks (stft.hip)
@@ -2266,6 +2322,26 @@ namespace
 constexpr uint64_t kStftDefaultBudget = 256ull << 20;
 
 uint32_t stft_max_n(int precision) { return precision == SDSP_HIP_F64 ? 32768u : 65536u; }
+
+// create-time checks the STFT, inverse STFT and Welch banks share; each runs its own between the two
+int check_frame_shape(uint32_t n_fft, uint32_t hop, const double *window, int precision)
+{
+    if (!sdsp_hip_is_power_of_2(n_fft))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
+    if (hop == 0 || hop > n_fft)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
+    if (!window)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    return SDSP_HIP_OK;
+}
+int check_real_input_range(uint32_t n_fft, int precision)
+{
+    if (n_fft < 32 || n_fft > stft_max_n(precision))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    return SDSP_HIP_OK;
+}
 
 int stft_run(sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
              uint64_t samples, void *state, hipStream_t stream)
@@ -2323,8 +2399,7 @@ int stft_check(const sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, 
 
 uint64_t stft_out_esize(const sdsp_hip_stft_plan *p)
 {
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    return p->output == SDSP_HIP_STFT_COMPLEX ? 2 * rs : rs;
+    return p->output == SDSP_HIP_STFT_COMPLEX ? esize(p->precision) : real_size(p->precision);
 }
 } // namespace
 
@@ -2334,22 +2409,15 @@ int sdsp_hip_stft_plan_create(sdsp_hip_stft_plan **out, uint32_t n_fft, uint32_t
     if (!out)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
     *out = nullptr;
-    if (!sdsp_hip_is_power_of_2(n_fft))
-        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
-    if (hop == 0 || hop > n_fft)
-        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
-    if (!window)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
-    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (int rc = check_frame_shape(n_fft, hop, window, precision))
+        return rc;
     if (output != SDSP_HIP_STFT_COMPLEX && output != SDSP_HIP_STFT_POWER && output != SDSP_HIP_STFT_MAGNITUDE)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "output must be SDSP_HIP_STFT_COMPLEX, _POWER or _MAGNITUDE");
-    if (n_fft < 32 || n_fft > stft_max_n(precision))
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    if (int rc = check_real_input_range(n_fft, precision))
+        return rc;
     if (int rc = use_device(device))
         return rc;
-    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
-    const uint64_t unit_bytes = static_cast<uint64_t>(n_fft) * rs;
+    const uint64_t unit_bytes = static_cast<uint64_t>(n_fft) * real_size(precision);
     const uint64_t budget = workspace_bytes ? workspace_bytes : kStftDefaultBudget;
     auto *p = new sdsp_hip_stft_plan();
     p->n = n_fft;
@@ -2359,23 +2427,15 @@ int sdsp_hip_stft_plan_create(sdsp_hip_stft_plan **out, uint32_t n_fft, uint32_t
     p->output = output;
     p->precision = precision;
     p->device = device;
-    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->ws_units = slice_units(budget, unit_bytes);
     p->workspace_bytes = p->ws_units * unit_bytes;
     int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device, 1);
     if (!rc) {
         hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
         if (e == hipSuccess)
-            e = hipMalloc(&p->window, n_fft * rs);
-        if (e == hipSuccess) { // rounded once to the plan precision
-            if (precision == SDSP_HIP_F64) {
-                e = hipMemcpy(p->window, window, n_fft * rs, hipMemcpyHostToDevice);
-            } else {
-                const std::vector<float> wf(window, window + n_fft);
-                e = hipMemcpy(p->window, wf.data(), n_fft * rs, hipMemcpyHostToDevice);
-            }
-        }
+            e = upload_reals(window, n_fft, precision, &p->window);
         if (e != hipSuccess)
-            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "stft plan: out of device memory") : hip_fail(e, "stft plan");
+            rc = plan_fail(e, "stft");
     }
     if (rc) {
         sdsp_hip_stft_plan_destroy(p);
@@ -2389,12 +2449,7 @@ int sdsp_hip_stft_plan_destroy(sdsp_hip_stft_plan *p)
 {
     if (!p)
         return SDSP_HIP_OK;
-    if (use_device(p->device) == SDSP_HIP_OK) {
-        (void)hipFree(p->ws);
-        (void)hipFree(p->window);
-    }
-    if (p->inner)
-        sdsp_hip_fft_plan_destroy(p->inner);
+    free_bank(p->device, p->ws, p->window, p->inner);
     delete p;
     return SDSP_HIP_OK;
 }
@@ -2403,7 +2458,7 @@ int sdsp_hip_stft_state_bytes(const sdsp_hip_stft_plan *p, uint64_t channels, ui
 {
     if (!p || !bytes)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
-    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    *bytes = static_cast<uint64_t>(p->hist) * channels * real_size(p->precision);
     return SDSP_HIP_OK;
 }
 
@@ -2411,15 +2466,7 @@ int sdsp_hip_stft_plan_set_variant(sdsp_hip_stft_plan *p, int variant)
 {
     if (!p || variant < 0)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
-    // rejected here rather than at the next process call: a variant without a kernel, or whose kernel needs a table this size's
-    // plan does not upload
-    const fft_kernel_sel sel = select_kernel(p->inner, variant);
-    if (sel.id == K_UNSUPPORTED)
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the inner real-input plan has no such kernel variant");
-    if (int rc = check_table(p->inner, sel))
-        return rc;
-    p->inner->variant = variant;
-    return SDSP_HIP_OK;
+    return set_inner_variant(p->inner, variant, "the inner real-input plan has no such kernel variant");
 }
 
 int sdsp_hip_stft_plan_get_info(const sdsp_hip_stft_plan *p, sdsp_hip_stft_plan_info *info)
@@ -2449,13 +2496,7 @@ int sdsp_hip_stft_plan_launches(const sdsp_hip_stft_plan *p, uint64_t channels, 
         return rc;
     if (channels == 0 || samples == 0)
         return SDSP_HIP_OK;
-    const uint64_t total = channels * frames;
-    uint64_t n = 0;
-    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
-        const uint64_t units = std::min(p->ws_units, total - g0);
-        n += 2 + fft_launch_count(p->inner, units, p->inner->variant);
-    }
-    *launches = n + (p->hist ? 1 : 0);
+    *launches = slice_launch_count(p->inner, channels * frames, p->ws_units, 2) + (p->hist ? 1 : 0);
     return SDSP_HIP_OK;
 }
 
@@ -2467,14 +2508,11 @@ int sdsp_hip_stft_process(sdsp_hip_stft_plan *p, const void *in, uint64_t in_str
         return rc;
     if (channels == 0 || samples == 0)
         return SDSP_HIP_OK;
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + samples) * rs;
-    const uintptr_t o1 = o0 + ((channels - 1) * out_stride + frames * p->bins) * stft_out_esize(p);
-    if (i0 < o1 && o0 < i1)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the STFT runs out of place)");
-    if (i0 % rs || o0 % stft_out_esize(p) || reinterpret_cast<uintptr_t>(state) % rs)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    const uint64_t rs = real_size(p->precision), oes = stft_out_esize(p);
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + samples) * rs, rs, out,
+                                    ((channels - 1) * out_stride + frames * p->bins) * oes, oes, state, rs,
+                                    "in and out ranges overlap (the STFT runs out of place)"))
+        return rc;
     if (int rc = use_device(p->device))
         return rc;
     return stft_run(p, in, in_stride, out, out_stride, channels, samples, state, reinterpret_cast<hipStream_t>(stream));
@@ -2490,41 +2528,17 @@ int sdsp_hip_stft_process_host(sdsp_hip_stft_plan *p, const void *host_in, uint6
         return SDSP_HIP_OK;
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    const size_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * real_size(p->precision);
     const size_t out_bytes = ((channels - 1) * out_stride + frames * p->bins) * stft_out_esize(p);
     uint64_t state_bytes = 0;
     sdsp_hip_stft_state_bytes(p, channels, &state_bytes);
     const bool with_state = host_state && state_bytes;
-    void *di = nullptr, *dout = nullptr, *s = nullptr;
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMalloc(&di, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc(&dout, out_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) // rows of out past F bins keep what the caller had there
-        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && with_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "stft host staging");
+    host_stage st("stft", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                        { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = stft_run(p, di, in_stride, dout, out_stride, channels, samples, s, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && with_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "stft host read-back");
-    }
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(s);
-    return rc;
+        rc = stft_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, st.dev[2], nullptr);
+    return st.out(rc);
 }
 
 // ------------------------------------------------------------------ inverse STFT banks (istft.hip)
@@ -2596,24 +2610,17 @@ int sdsp_hip_istft_plan_create(sdsp_hip_istft_plan **out, uint32_t n_fft, uint32
     if (!out)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
     *out = nullptr;
-    if (!sdsp_hip_is_power_of_2(n_fft))
-        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
-    if (hop == 0 || hop > n_fft)
-        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
-    if (!window)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
-    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
-    if (n_fft < 32 || n_fft > stft_max_n(precision))
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    if (int rc = check_frame_shape(n_fft, hop, window, precision))
+        return rc;
+    if (int rc = check_real_input_range(n_fft, precision))
+        return rc;
     std::vector<double> g(n_fft);
     double env_min = 0, env_max = 0;
     if (int rc = istft_synthesis(n_fft, hop, window, norm, g.data(), &env_min, &env_max))
         return rc;
     if (int rc = use_device(device))
         return rc;
-    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
-    const uint64_t unit_bytes = static_cast<uint64_t>(n_fft) * rs;
+    const uint64_t unit_bytes = static_cast<uint64_t>(n_fft) * real_size(precision);
     const uint64_t budget = workspace_bytes ? workspace_bytes : kIstftDefaultBudget;
     auto *p = new sdsp_hip_istft_plan();
     p->n = n_fft;
@@ -2625,23 +2632,15 @@ int sdsp_hip_istft_plan_create(sdsp_hip_istft_plan **out, uint32_t n_fft, uint32
     p->device = device;
     p->env_min = env_min;
     p->env_max = env_max;
-    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->ws_units = slice_units(budget, unit_bytes);
     p->workspace_bytes = p->ws_units * unit_bytes;
     int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_REVERSE, precision, p->ws_units, device, 2);
     if (!rc) {
         hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
         if (e == hipSuccess)
-            e = hipMalloc(&p->g, n_fft * rs);
-        if (e == hipSuccess) { // rounded once to the plan precision
-            if (precision == SDSP_HIP_F64) {
-                e = hipMemcpy(p->g, g.data(), n_fft * rs, hipMemcpyHostToDevice);
-            } else {
-                const std::vector<float> gf(g.begin(), g.end());
-                e = hipMemcpy(p->g, gf.data(), n_fft * rs, hipMemcpyHostToDevice);
-            }
-        }
+            e = upload_reals(g.data(), n_fft, precision, &p->g);
         if (e != hipSuccess)
-            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "istft plan: out of device memory") : hip_fail(e, "istft plan");
+            rc = plan_fail(e, "istft");
     }
     if (rc) {
         sdsp_hip_istft_plan_destroy(p);
@@ -2655,12 +2654,7 @@ int sdsp_hip_istft_plan_destroy(sdsp_hip_istft_plan *p)
 {
     if (!p)
         return SDSP_HIP_OK;
-    if (use_device(p->device) == SDSP_HIP_OK) {
-        (void)hipFree(p->ws);
-        (void)hipFree(p->g);
-    }
-    if (p->inner)
-        sdsp_hip_fft_plan_destroy(p->inner);
+    free_bank(p->device, p->ws, p->g, p->inner);
     delete p;
     return SDSP_HIP_OK;
 }
@@ -2669,7 +2663,7 @@ int sdsp_hip_istft_state_bytes(const sdsp_hip_istft_plan *p, uint64_t channels, 
 {
     if (!p || !bytes)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
-    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    *bytes = static_cast<uint64_t>(p->hist) * channels * real_size(p->precision);
     return SDSP_HIP_OK;
 }
 
@@ -2677,13 +2671,7 @@ int sdsp_hip_istft_plan_set_variant(sdsp_hip_istft_plan *p, int variant)
 {
     if (!p || variant < 0)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
-    const fft_kernel_sel sel = select_kernel(p->inner, variant);
-    if (sel.id == K_UNSUPPORTED)
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the inner real-input plan has no such kernel variant");
-    if (int rc = check_table(p->inner, sel))
-        return rc;
-    p->inner->variant = variant;
-    return SDSP_HIP_OK;
+    return set_inner_variant(p->inner, variant, "the inner real-input plan has no such kernel variant");
 }
 
 int sdsp_hip_istft_plan_get_info(const sdsp_hip_istft_plan *p, sdsp_hip_istft_plan_info *info)
@@ -2714,13 +2702,7 @@ int sdsp_hip_istft_plan_launches(const sdsp_hip_istft_plan *p, uint64_t channels
         return SDSP_HIP_OK;
     if (channels > ~0ull / frames)
         return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
-    const uint64_t total = channels * frames;
-    uint64_t n = p->hist ? 1 : 0;
-    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
-        const uint64_t units = std::min(p->ws_units, total - g0);
-        n += 2 + fft_launch_count(p->inner, units, p->inner->variant);
-    }
-    *launches = n;
+    *launches = (p->hist ? 1 : 0) + slice_launch_count(p->inner, channels * frames, p->ws_units, 2);
     return SDSP_HIP_OK;
 }
 
@@ -2731,14 +2713,11 @@ int sdsp_hip_istft_process(sdsp_hip_istft_plan *p, const void *in, uint64_t in_s
         return rc;
     if (channels == 0 || frames == 0)
         return SDSP_HIP_OK;
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + frames * p->bins) * 2 * rs;
-    const uintptr_t o1 = o0 + ((channels - 1) * out_stride + frames * p->hop) * rs;
-    if (i0 < o1 && o0 < i1)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the inverse STFT runs out of place)");
-    if (i0 % (2 * rs) || o0 % rs || reinterpret_cast<uintptr_t>(state) % rs)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    const uint64_t rs = real_size(p->precision);
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + frames * p->bins) * 2 * rs, 2 * rs, out,
+                                    ((channels - 1) * out_stride + frames * p->hop) * rs, rs, state, rs,
+                                    "in and out ranges overlap (the inverse STFT runs out of place)"))
+        return rc;
     if (int rc = use_device(p->device))
         return rc;
     return istft_run(p, in, in_stride, out, out_stride, channels, frames, state, reinterpret_cast<hipStream_t>(stream));
@@ -2753,41 +2732,18 @@ int sdsp_hip_istft_process_host(sdsp_hip_istft_plan *p, const void *host_in, uin
         return SDSP_HIP_OK;
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t rs = real_size(p->precision);
     const size_t in_bytes = ((channels - 1) * in_stride + frames * p->bins) * 2 * rs;
     const size_t out_bytes = ((channels - 1) * out_stride + frames * p->hop) * rs;
     uint64_t state_bytes = 0;
     sdsp_hip_istft_state_bytes(p, channels, &state_bytes);
     const bool with_state = host_state && state_bytes;
-    void *di = nullptr, *dout = nullptr, *s = nullptr;
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMalloc(&di, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc(&dout, out_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) // rows of out past F hop keep what the caller had there
-        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && with_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "istft host staging");
+    host_stage st("istft", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                         { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = istft_run(p, di, in_stride, dout, out_stride, channels, frames, s, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && with_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "istft host read-back");
-    }
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(s);
-    return rc;
+        rc = istft_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, frames, st.dev[2], nullptr);
+    return st.out(rc);
 }
 
 // ------------------------------------------------------------------ forward-backward filtering (iir_filtfilt.hip)
@@ -2826,7 +2782,7 @@ filtfilt_args filtfilt_make_args(const sdsp_hip_filtfilt_plan *p, void *data, ui
 
 int filtfilt_run(sdsp_hip_filtfilt_plan *p, void *data, uint64_t channels, uint64_t samples, uint64_t stride, hipStream_t stream)
 {
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t rs = real_size(p->precision);
     for (uint64_t c0 = 0; c0 < channels; c0 += p->slice_channels) {
         const uint64_t n = std::min(p->slice_channels, channels - c0);
         const filtfilt_args a = filtfilt_make_args(p, static_cast<char *>(data) + c0 * stride * rs, n, samples, stride);
@@ -2879,7 +2835,7 @@ int sdsp_hip_filtfilt_plan_create(sdsp_hip_filtfilt_plan **out, uint32_t section
     }
     if (int rc = use_device(device))
         return rc;
-    const uint64_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t rs = real_size(precision);
     auto *p = new sdsp_hip_filtfilt_plan();
     p->sections = sections;
     p->padlen = pad;
@@ -2909,8 +2865,7 @@ int sdsp_hip_filtfilt_plan_create(sdsp_hip_filtfilt_plan **out, uint32_t section
         hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
         if (e != hipSuccess) {
             p->ws = nullptr;
-            const int rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "filtfilt plan: out of device memory")
-                                                    : hip_fail(e, "filtfilt plan");
+            const int rc = plan_fail(e, "filtfilt");
             sdsp_hip_filtfilt_plan_destroy(p);
             return rc;
         }
@@ -2986,8 +2941,7 @@ int sdsp_hip_filtfilt_process(sdsp_hip_filtfilt_plan *p, void *data, uint64_t ch
         return rc;
     if (channels == 0)
         return SDSP_HIP_OK;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    if (reinterpret_cast<uintptr_t>(data) % rs)
+    if (misaligned(data, real_size(p->precision)))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "data must be aligned to its element size");
     if (int rc = use_device(p->device))
         return rc;
@@ -3002,23 +2956,11 @@ int sdsp_hip_filtfilt_process_host(sdsp_hip_filtfilt_plan *p, void *host_data, u
         return SDSP_HIP_OK;
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    const size_t bytes = ((channels - 1) * stride + samples) * rs;
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, bytes));
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMemcpy(d, host_data, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-        rc = hip_fail(e, "filtfilt host staging");
+    host_stage st("filtfilt", { { host_data, ((channels - 1) * stride + samples) * real_size(p->precision), true } });
+    int rc = st.in();
     if (!rc)
-        rc = filtfilt_run(p, d, channels, samples, stride, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_data, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "filtfilt host read-back");
-    }
-    (void)hipFree(d);
-    return rc;
+        rc = filtfilt_run(p, st.dev[0], channels, samples, stride, nullptr);
+    return st.out(rc);
 }
 
 // ------------------------------------------------------------------ Welch PSD banks (welch.hip)
@@ -3030,7 +2972,7 @@ constexpr uint64_t kWelchDefaultBudget = 256ull << 20;
 
 uint64_t welch_unit_bytes(uint32_t n, int precision)
 {
-    return static_cast<uint64_t>(n) * (precision == SDSP_HIP_F64 ? 8 : 4) + (static_cast<uint64_t>(n) / 2 + 1) * 8;
+    return static_cast<uint64_t>(n) * real_size(precision) + (static_cast<uint64_t>(n) / 2 + 1) * 8;
 }
 
 // segments per run: one run per channel up to 16 segments, else the smallest power of two R with R^2 >= the segments one channel
@@ -3134,12 +3076,6 @@ int welch_finalize_check(const sdsp_hip_welch_plan *p, const double *acc, uint64
     return SDSP_HIP_OK;
 }
 
-bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 int welch_finalize_run(const sdsp_hip_welch_plan *p, const double *acc, uint64_t acc_stride, uint64_t frames_total, void *out,
                        uint64_t out_stride, uint64_t channels, hipStream_t stream)
 {
@@ -3162,22 +3098,16 @@ int sdsp_hip_welch_plan_create(sdsp_hip_welch_plan **out, uint32_t n_fft, uint32
     if (!out)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
     *out = nullptr;
-    if (!sdsp_hip_is_power_of_2(n_fft))
-        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n_fft must be a power of 2");
-    if (hop == 0 || hop > n_fft)
-        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, n_fft]");
-    if (!window)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "window pointer is null");
-    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (int rc = check_frame_shape(n_fft, hop, window, precision))
+        return rc;
     if (detrend != SDSP_HIP_DETREND_NONE && detrend != SDSP_HIP_DETREND_CONSTANT && detrend != SDSP_HIP_DETREND_LINEAR)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "detrend must be SDSP_HIP_DETREND_NONE, _CONSTANT or _LINEAR");
     if (scaling != SDSP_HIP_SCALING_DENSITY && scaling != SDSP_HIP_SCALING_SPECTRUM)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "scaling must be SDSP_HIP_SCALING_DENSITY or _SPECTRUM");
     if (!(fs > 0.0) || !std::isfinite(fs))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "fs must be finite and > 0");
-    if (n_fft < 32 || n_fft > stft_max_n(precision))
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "n_fft must be in the radix-2 real-input range (f32 32 .. 65536, f64 32 .. 32768)");
+    if (int rc = check_real_input_range(n_fft, precision))
+        return rc;
     // the window rounded once to the plan precision; the scale sums run over those values
     std::vector<double> wr(window, window + n_fft);
     if (precision == SDSP_HIP_F32)
@@ -3190,7 +3120,6 @@ int sdsp_hip_welch_plan_create(sdsp_hip_welch_plan **out, uint32_t n_fft, uint32
     }
     if (int rc = use_device(device))
         return rc;
-    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
     const uint64_t unit_bytes = welch_unit_bytes(n_fft, precision);
     const uint64_t budget = workspace_bytes ? workspace_bytes : kWelchDefaultBudget;
     auto *p = new sdsp_hip_welch_plan();
@@ -3204,25 +3133,17 @@ int sdsp_hip_welch_plan_create(sdsp_hip_welch_plan **out, uint32_t n_fft, uint32
     p->scale = scaling == SDSP_HIP_SCALING_DENSITY ? 1.0 / (fs * sw2) : 1.0 / (sw * sw);
     p->precision = precision;
     p->device = device;
-    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->ws_units = slice_units(budget, unit_bytes);
     p->workspace_bytes = p->ws_units * unit_bytes;
     int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device, 1);
     if (!rc) {
         hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
         if (e == hipSuccess) {
-            p->part = reinterpret_cast<double *>(static_cast<char *>(p->ws) + p->ws_units * n_fft * rs);
-            e = hipMalloc(&p->window, n_fft * rs);
-        }
-        if (e == hipSuccess) {
-            if (precision == SDSP_HIP_F64) {
-                e = hipMemcpy(p->window, wr.data(), n_fft * rs, hipMemcpyHostToDevice);
-            } else {
-                const std::vector<float> wf(wr.begin(), wr.end());
-                e = hipMemcpy(p->window, wf.data(), n_fft * rs, hipMemcpyHostToDevice);
-            }
+            p->part = reinterpret_cast<double *>(static_cast<char *>(p->ws) + p->ws_units * n_fft * real_size(precision));
+            e = upload_reals(wr.data(), n_fft, precision, &p->window); // wr holds the rounded values: converting them again is exact
         }
         if (e != hipSuccess)
-            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "welch plan: out of device memory") : hip_fail(e, "welch plan");
+            rc = plan_fail(e, "welch");
     }
     if (rc) {
         sdsp_hip_welch_plan_destroy(p);
@@ -3236,12 +3157,7 @@ int sdsp_hip_welch_plan_destroy(sdsp_hip_welch_plan *p)
 {
     if (!p)
         return SDSP_HIP_OK;
-    if (use_device(p->device) == SDSP_HIP_OK) {
-        (void)hipFree(p->ws);
-        (void)hipFree(p->window);
-    }
-    if (p->inner)
-        sdsp_hip_fft_plan_destroy(p->inner);
+    free_bank(p->device, p->ws, p->window, p->inner);
     delete p;
     return SDSP_HIP_OK;
 }
@@ -3250,7 +3166,7 @@ int sdsp_hip_welch_state_bytes(const sdsp_hip_welch_plan *p, uint64_t channels, 
 {
     if (!p || !bytes)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
-    *bytes = static_cast<uint64_t>(p->hist) * channels * (p->precision == SDSP_HIP_F64 ? 8 : 4);
+    *bytes = static_cast<uint64_t>(p->hist) * channels * real_size(p->precision);
     return SDSP_HIP_OK;
 }
 
@@ -3284,13 +3200,7 @@ int sdsp_hip_welch_plan_launches(const sdsp_hip_welch_plan *p, uint64_t channels
         return rc;
     if (channels == 0 || samples == 0)
         return SDSP_HIP_OK;
-    const uint64_t total = channels * frames;
-    uint64_t n = 0;
-    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
-        const uint64_t units = std::min(p->ws_units, total - g0);
-        n += 3 + fft_launch_count(p->inner, units, p->inner->variant);
-    }
-    *launches = n + 1;
+    *launches = slice_launch_count(p->inner, channels * frames, p->ws_units, 3) + 1;
     return SDSP_HIP_OK;
 }
 
@@ -3301,12 +3211,12 @@ int sdsp_hip_welch_process(sdsp_hip_welch_plan *p, const void *in, uint64_t in_s
         return rc;
     if (channels == 0 || samples == 0)
         return SDSP_HIP_OK;
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t rs = real_size(p->precision);
     const uint64_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
     if (ranges_overlap(in, in_bytes, state, channels * p->hist * rs) ||
         ranges_overlap(in, in_bytes, acc, ((channels - 1) * acc_stride + p->bins) * 8))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "in overlaps state or acc");
-    if (reinterpret_cast<uintptr_t>(in) % rs || reinterpret_cast<uintptr_t>(state) % rs || reinterpret_cast<uintptr_t>(acc) % 8)
+    if (misaligned(in, rs) || misaligned(state, rs) || misaligned(acc, 8))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "in, state and acc must be aligned to their element size");
     if (int rc = use_device(p->device))
         return rc;
@@ -3322,39 +3232,16 @@ int sdsp_hip_welch_process_host(sdsp_hip_welch_plan *p, const void *host_in, uin
         return SDSP_HIP_OK;
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const size_t rs = real_size(p->precision);
     const size_t in_bytes = ((channels - 1) * in_stride + samples) * rs;
     const size_t acc_bytes = ((channels - 1) * acc_stride + p->bins) * 8;
     const size_t state_bytes = channels * p->hist * rs;
-    void *di = nullptr, *da = nullptr, *s = nullptr;
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMalloc(&di, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc(&da, acc_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) // rows of acc past bins keep what the caller had there
-        e = hipMemcpy(da, host_acc, acc_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && host_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "welch host staging");
+    host_stage st("welch", { { host_in, in_bytes, false }, { host_acc, acc_bytes, true }, { host_state, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = welch_run(p, di, in_stride, channels, samples, position, s, static_cast<double *>(da), acc_stride, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_acc, da, acc_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && host_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "welch host read-back");
-    }
-    (void)hipFree(di);
-    (void)hipFree(da);
-    (void)hipFree(s);
-    return rc;
+        rc = welch_run(p, st.dev[0], in_stride, channels, samples, position, st.dev[2], static_cast<double *>(st.dev[1]), acc_stride,
+                       nullptr);
+    return st.out(rc);
 }
 
 int sdsp_hip_welch_finalize(sdsp_hip_welch_plan *p, const double *acc, uint64_t acc_stride, uint64_t frames_total, void *out,
@@ -3364,10 +3251,10 @@ int sdsp_hip_welch_finalize(sdsp_hip_welch_plan *p, const double *acc, uint64_t 
         return rc;
     if (channels == 0)
         return SDSP_HIP_OK;
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
+    const uint64_t rs = real_size(p->precision);
     if (ranges_overlap(acc, ((channels - 1) * acc_stride + p->bins) * 8, out, ((channels - 1) * out_stride + p->bins) * rs))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "acc and out overlap");
-    if (reinterpret_cast<uintptr_t>(acc) % 8 || reinterpret_cast<uintptr_t>(out) % rs)
+    if (misaligned(acc, 8) || misaligned(out, rs))
         return fail(SDSP_HIP_ERR_INVALID_ARG, "acc and out must be aligned to their element size");
     if (int rc = use_device(p->device))
         return rc;
@@ -3383,30 +3270,14 @@ int sdsp_hip_welch_finalize_host(sdsp_hip_welch_plan *p, const double *host_acc,
         return SDSP_HIP_OK;
     if (int rc = use_device(p->device))
         return rc;
-    const size_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
     const size_t acc_bytes = ((channels - 1) * acc_stride + p->bins) * 8;
-    const size_t out_bytes = ((channels - 1) * out_stride + p->bins) * rs;
-    void *da = nullptr, *dout = nullptr;
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMalloc(&da, acc_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc(&dout, out_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpy(da, host_acc, acc_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) // rows of out past bins keep what the caller had there
-        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-        rc = hip_fail(e, "welch host staging");
+    const size_t out_bytes = ((channels - 1) * out_stride + p->bins) * real_size(p->precision);
+    host_stage st("welch", { { host_acc, acc_bytes, false }, { host_out, out_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = welch_finalize_run(p, static_cast<const double *>(da), acc_stride, frames_total, dout, out_stride, channels, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "welch host read-back");
-    }
-    (void)hipFree(da);
-    (void)hipFree(dout);
-    return rc;
+        rc = welch_finalize_run(p, static_cast<const double *>(st.dev[0]), acc_stride, frames_total, st.dev[1], out_stride, channels,
+                                nullptr);
+    return st.out(rc);
 }
 
 // ------------------------------------------------------------------ polyphase filter-bank channelizer banks (pfb.hip)
@@ -3417,10 +3288,9 @@ constexpr uint64_t kPfbDefaultBudget = 256ull << 20; // the STFT bank's
 
 uint64_t pfb_in_esize(const sdsp_hip_pfb_plan *p)
 {
-    const uint64_t rs = p->precision == SDSP_HIP_F64 ? 8 : 4;
-    return p->kind == SDSP_HIP_PFB_COMPLEX ? 2 * rs : rs;
+    return p->kind == SDSP_HIP_PFB_COMPLEX ? esize(p->precision) : real_size(p->precision);
 }
-uint64_t pfb_out_esize(const sdsp_hip_pfb_plan *p) { return p->precision == SDSP_HIP_F64 ? 16 : 8; }
+uint64_t pfb_out_esize(const sdsp_hip_pfb_plan *p) { return esize(p->precision); }
 
 // the slice [g0, g0 + units) of the channel-major (channel, frame) numbering as rectangles: a partial first channel, whole channels, a
 // partial last channel.  f(c0, nc, j0, nj) is called for each; a non-zero return stops the walk.
@@ -3576,9 +3446,8 @@ int sdsp_hip_pfb_plan_create(sdsp_hip_pfb_plan **out, uint32_t channels_m, uint3
                     "channels_m must be in the transform range (f32 .. 65536, f64 .. 32768; from 32 for real input, 16 for complex)");
     if (int rc = use_device(device))
         return rc;
-    const size_t rs = precision == SDSP_HIP_F64 ? 8 : 4;
     const uint64_t taps_n = static_cast<uint64_t>(m) * taps_per_channel;
-    const uint64_t unit_bytes = static_cast<uint64_t>(m) * rs * (cplx ? 2 : 1);
+    const uint64_t unit_bytes = static_cast<uint64_t>(m) * real_size(precision) * (cplx ? 2 : 1);
     const uint64_t budget = workspace_bytes ? workspace_bytes : kPfbDefaultBudget;
     auto *p = new sdsp_hip_pfb_plan();
     p->m = m;
@@ -3590,24 +3459,16 @@ int sdsp_hip_pfb_plan_create(sdsp_hip_pfb_plan **out, uint32_t channels_m, uint3
     p->phase = phase;
     p->precision = precision;
     p->device = device;
-    p->ws_units = std::min<uint64_t>(std::max<uint64_t>(1, budget / unit_bytes), 1ull << 30);
+    p->ws_units = slice_units(budget, unit_bytes);
     p->workspace_bytes = p->ws_units * unit_bytes;
     int rc = cplx ? fft_plan_create(&p->inner, m, SDSP_HIP_RADIX_AUTO, SDSP_HIP_FORWARD, precision, p->ws_units, device, 0)
                   : fft_plan_create(&p->inner, m / 2, 2, SDSP_HIP_FORWARD, precision, p->ws_units, device, 1);
     if (!rc) {
         hipError_t e = cplx ? hipSuccess : hipMalloc(&p->ws, p->workspace_bytes);
         if (e == hipSuccess)
-            e = hipMalloc(&p->taps, taps_n * rs);
-        if (e == hipSuccess) { // rounded once to the plan precision
-            if (precision == SDSP_HIP_F64) {
-                e = hipMemcpy(p->taps, taps, taps_n * rs, hipMemcpyHostToDevice);
-            } else {
-                const std::vector<float> hf(taps, taps + taps_n);
-                e = hipMemcpy(p->taps, hf.data(), taps_n * rs, hipMemcpyHostToDevice);
-            }
-        }
+            e = upload_reals(taps, taps_n, precision, &p->taps);
         if (e != hipSuccess)
-            rc = e == hipErrorOutOfMemory ? fail(SDSP_HIP_ERR_NOMEM, "pfb plan: out of device memory") : hip_fail(e, "pfb plan");
+            rc = plan_fail(e, "pfb");
     }
     if (rc) {
         sdsp_hip_pfb_plan_destroy(p);
@@ -3621,12 +3482,7 @@ int sdsp_hip_pfb_plan_destroy(sdsp_hip_pfb_plan *p)
 {
     if (!p)
         return SDSP_HIP_OK;
-    if (use_device(p->device) == SDSP_HIP_OK) {
-        (void)hipFree(p->ws);
-        (void)hipFree(p->taps);
-    }
-    if (p->inner)
-        sdsp_hip_fft_plan_destroy(p->inner);
+    free_bank(p->device, p->ws, p->taps, p->inner);
     delete p;
     return SDSP_HIP_OK;
 }
@@ -3643,19 +3499,7 @@ int sdsp_hip_pfb_plan_set_variant(sdsp_hip_pfb_plan *p, int variant)
 {
     if (!p || variant < 0)
         return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
-    const fft_kernel_sel sel = select_kernel(p->inner, variant);
-    if (sel.id == K_UNSUPPORTED)
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the inner plan has no such kernel variant");
-    if (int rc = check_table(p->inner, sel))
-        return rc;
-    if (sel.workspace) { // a multi-pass alternate of a single-pass default: its workspace is allocated here, not on the launch path
-        if (int rc = use_device(p->device))
-            return rc;
-        if (int rc = ensure_workspace(p->inner))
-            return rc;
-    }
-    p->inner->variant = variant;
-    return SDSP_HIP_OK;
+    return set_inner_variant(p->inner, variant, "the inner plan has no such kernel variant", true);
 }
 
 int sdsp_hip_pfb_plan_set_fold_form(sdsp_hip_pfb_plan *p, int form)
@@ -3719,13 +3563,10 @@ int sdsp_hip_pfb_process(sdsp_hip_pfb_plan *p, const void *in, uint64_t in_strid
     if (channels == 0 || samples == 0)
         return SDSP_HIP_OK;
     const uint64_t ies = pfb_in_esize(p), oes = pfb_out_esize(p);
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((channels - 1) * in_stride + samples) * ies;
-    const uintptr_t o1 = o0 + ((channels - 1) * out_stride + frames * p->bins) * oes;
-    if (i0 < o1 && o0 < i1)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (the filter bank runs out of place)");
-    if (i0 % ies || o0 % oes || reinterpret_cast<uintptr_t>(state) % ies)
-        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out and state must be aligned to their element size");
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + samples) * ies, ies, out,
+                                    ((channels - 1) * out_stride + frames * p->bins) * oes, oes, state, ies,
+                                    "in and out ranges overlap (the filter bank runs out of place)"))
+        return rc;
     if (int rc = use_device(p->device))
         return rc;
     return pfb_run(p, in, in_stride, out, out_stride, channels, samples, position, state, reinterpret_cast<hipStream_t>(stream));
@@ -3746,34 +3587,11 @@ int sdsp_hip_pfb_process_host(sdsp_hip_pfb_plan *p, const void *host_in, uint64_
     uint64_t state_bytes = 0;
     sdsp_hip_pfb_state_bytes(p, channels, &state_bytes);
     const bool with_state = host_state && state_bytes;
-    void *di = nullptr, *dout = nullptr, *s = nullptr;
-    int rc = SDSP_HIP_OK;
-    hipError_t e = hipMalloc(&di, in_bytes);
-    if (e == hipSuccess)
-        e = hipMalloc(&dout, out_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpy(di, host_in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) // rows of out past F bins keep what the caller had there
-        e = hipMemcpy(dout, host_out, out_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && with_state) {
-        e = hipMalloc(&s, state_bytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(s, host_state, state_bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess)
-        rc = hip_fail(e, "pfb host staging");
+    host_stage st("pfb", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                       { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
     if (!rc)
-        rc = pfb_run(p, di, in_stride, dout, out_stride, channels, samples, position, s, nullptr);
-    if (!rc) {
-        e = hipMemcpy(host_out, dout, out_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && with_state)
-            e = hipMemcpy(host_state, s, state_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = hip_fail(e, "pfb host read-back");
-    }
-    (void)hipFree(di);
-    (void)hipFree(dout);
-    (void)hipFree(s);
-    return rc;
+        rc = pfb_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, position, st.dev[2], nullptr);
+    return st.out(rc);
 }
 }
