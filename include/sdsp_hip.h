@@ -830,6 +830,77 @@ typedef struct {
 } sdsp_hip_pfb_plan_info;
 int sdsp_hip_pfb_plan_get_info(const sdsp_hip_pfb_plan *plan, sdsp_hip_pfb_plan_info *info);
 
+/* ------------------------------------------------------------------ polyphase synthesis filter banks (inverse channelizer) */
+
+/*
+ * The synthesis half of the polyphase filter bank: `channels` independent streams are rebuilt from frames of
+ * M sub-bands in sdsp_hip_pfb_process's output layout.  M, P, L = P M, D, hist = L - D as above; g[0 .. L) is the synthesis prototype.
+ * A call takes F frames of `bins` complex values per channel and writes exactly F D samples per channel.  For frame j of the call:
+ *     v_j = the library's reverse M-point transform of the frame, 1 / M scaled (COMPLEX: the complex SDSP_HIP_RADIX_AUTO plan over M
+ *           bins; REAL: the real-input plan over M / 2 + 1 bins, the imaginary parts of bins 0 and M / 2 ignored, as the inverse STFT)
+ *     u_j = v_j (phase FRAME), or u_j[r] = v_j[(r + s_j) mod M] with s_j = (position + j D - hist) mod M (phase TIME: the analysis
+ *           bank's s_j; `position` is the number of samples per channel that earlier calls produced)
+ * Output position t of the call starts from the pending sum at t where one exists (t < hist and a state was given), else from 0, and
+ * receives fl(g[t - j D] u_j[(t - j D) mod M]) for every frame j with 0 <= t - j D < L, added in ascending j, every product and sum
+ * rounded on its own (COMPLEX: real and imaginary parts multiplied separately by the real tap).  Positions t < F D go to out,
+ * positions F D <= t < F D + hist are the new pending sums.
+ *   - state: hist elements of the output kind per channel, in time order; read at entry, written at exit; none when P = 1 and D = M.
+ *     NULL = start from zero and drop the tail.
+ *   - block-by-block calls equal one long call bit for bit for any split into frame counts (F D < hist included).
+ *   - with g a dual of the analysis prototype (sdsp_hip_pfb_dual_prototype), synthesis(analysis(x)), both fresh, is x delayed by hist
+ *     samples, for both kinds and both phases.
+ *   - the two limits: P = 1, FRAME, REAL is the inverse STFT bank with SDSP_HIP_ISTFT_RAW and window g; P = 1, D = M is the plain
+ *     reverse transform times g.
+ *   - strides count elements.  `in` is never written; in and out may not overlap; nothing outside each channel's F D output elements
+ *     and its state row is written.  The taps: L host doubles, rounded once to the plan precision at creation.
+ * A call runs as one launch that moves the old pending sums to their places, then slices of the workspace budget: spectra into the
+ * workspace (REAL: packed) -> reverse transform in place -> unfold (one owner per output position, no atomics).
+ */
+typedef struct sdsp_hip_pfb_synth_plan sdsp_hip_pfb_synth_plan;
+/* the minimum-norm synthesis prototype g (p m doubles) that reconstructs through the analysis prototype h (p m doubles) at this hop,
+ * host only: for every t0 in [0, hop) and every k in (-p, p), sum over i of g[t0 + i hop] h[t0 + i hop + k m] = (k == 0), over the i
+ * whose two indices lie in [0, p m).  Solved per t0 in double by a singular value decomposition (no normal equations).  Where the
+ * largest residual exceeds 1e-9 no dual of this support exists: SDSP_HIP_ERR_INVALID_ARG (hops above m / 2 with p > 1, typically).
+ * Size errors as sdsp_hip_pfb_prototype, and hop = 0 or hop > m: SDSP_HIP_ERR_INVALID_SIZE; h or g NULL: SDSP_HIP_ERR_INVALID_ARG.
+ * Cost: O(p^2 L) flops per Jacobi sweep over all residues together, a handful of sweeps -- milliseconds
+ * for the usual shapes, seconds at L = 2^20 with p = 8, and minutes at the extreme p = 64, L = 2^20 (one thread, no progress report). */
+int sdsp_hip_pfb_dual_prototype(uint32_t m, uint32_t p, uint32_t hop, const double *h, double *g);
+/* taps: the synthesis prototype, p m host doubles.  output_kind: SDSP_HIP_PFB_REAL or SDSP_HIP_PFB_COMPLEX; phase: SDSP_HIP_PFB_PHASE_*.
+ * workspace_bytes: the slice budget (0 = the default, 256 MiB); a slice holds at least one frame.  Errors and size ranges are those of
+ * sdsp_hip_pfb_plan_create. */
+int sdsp_hip_pfb_synth_plan_create(sdsp_hip_pfb_synth_plan **plan, uint32_t channels_m, uint32_t taps_per_channel, uint32_t hop,
+                                   const double *taps, int output_kind, int phase, int precision, uint64_t workspace_bytes, int device);
+int sdsp_hip_pfb_synth_plan_destroy(sdsp_hip_pfb_synth_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + frames bins) complex elements.  out: DEVICE pointer, channel c = out[c out_stride ..
+ * + frames hop) elements of the output kind.  state: DEVICE pointer or NULL.  position: samples per channel produced before this call
+ * (phase TIME; ignored for FRAME).  Asynchronous on `stream`, allocates nothing (stream-capturable); one call per plan in flight.
+ * Errors: null plan, in or out, in_stride < frames bins or out_stride < frames hop with more than one channel, overlapping in and out
+ * ranges, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG.  channels == 0 or frames == 0: nothing to do.
+ */
+int sdsp_hip_pfb_synth_process(sdsp_hip_pfb_synth_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                               uint64_t channels, uint64_t frames, uint64_t position, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_pfb_synth_process_host(sdsp_hip_pfb_synth_plan *plan, const void *host_in, uint64_t in_stride, void *host_out,
+                                    uint64_t out_stride, uint64_t channels, uint64_t frames, uint64_t position, void *host_state);
+/* bytes of a state buffer for `channels` channels: hist channels element size (0 when p = 1 and hop = channels_m) */
+int sdsp_hip_pfb_synth_state_bytes(const sdsp_hip_pfb_synth_plan *plan, uint64_t channels, uint64_t *bytes);
+/* the kernel variant of the inner reverse plan (sdsp_hip_fft_plan_set_variant); SDSP_HIP_ERR_UNSUPPORTED where it has no such variant */
+int sdsp_hip_pfb_synth_plan_set_variant(sdsp_hip_pfb_synth_plan *plan, int variant);
+/* measurement and cross-check hook: 0 = the unfold form the sizes select (sliding where hop = channels_m, else plain), 1 = the plain
+ * per-position form for every hop.  Both forms give the same bits. */
+int sdsp_hip_pfb_synth_plan_set_unfold_form(sdsp_hip_pfb_synth_plan *plan, int form);
+/* kernel launches of one process call of `frames` per channel with a state buffer */
+int sdsp_hip_pfb_synth_plan_launches(const sdsp_hip_pfb_synth_plan *plan, uint64_t channels, uint64_t frames, uint64_t *launches);
+typedef struct {
+    uint32_t channels_m, taps_per_channel, hop, bins, hist;
+    int output_kind, phase, precision, device;
+    uint64_t workspace_bytes;
+    char kernel[64];          /* the inner reverse transform's kernel */
+    char unfold[16];          /* "sliding" or "plain" */
+} sdsp_hip_pfb_synth_plan_info;
+int sdsp_hip_pfb_synth_plan_get_info(const sdsp_hip_pfb_synth_plan *plan, sdsp_hip_pfb_synth_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

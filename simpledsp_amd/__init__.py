@@ -19,6 +19,7 @@ from .istft import istft_bank, synthesis_window as istft_synthesis_window
 from .filtfilt import filtfilt_plan, sosfiltfilt, steady_state as iir_steady_state, default_padlen as filtfilt_default_padlen
 from .welch import welch_bank, welch
 from .pfb import pfb_bank, pfb_prototype
+from .pfb_synth import pfb_synthesis_bank, pfb_dual_prototype
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

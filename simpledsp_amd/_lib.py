@@ -108,6 +108,14 @@ class PfbPlanInfo(C.Structure):
     ]
 
 
+class PfbSynthPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels_m", C.c_uint32), ("taps_per_channel", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32),
+        ("output_kind", C.c_int), ("phase", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("workspace_bytes", C.c_uint64),
+        ("kernel", C.c_char * 64), ("unfold", C.c_char * 16),
+    ]
+
+
 PFB_REAL, PFB_COMPLEX = 0, 1
 PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
 PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
@@ -234,6 +242,16 @@ SIGNATURES = {
     "sdsp_hip_pfb_plan_set_fold_form": (_i, [_vp, _i]),
     "sdsp_hip_pfb_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_pfb_plan_get_info": (_i, [_vp, C.POINTER(PfbPlanInfo)]),
+    "sdsp_hip_pfb_dual_prototype": (_i, [_u32, _u32, _u32, _vp, _vp]),
+    "sdsp_hip_pfb_synth_plan_create": (_i, [_pp, _u32, _u32, _u32, _vp, _i, _i, _i, _u64, _i]),
+    "sdsp_hip_pfb_synth_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_pfb_synth_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_pfb_synth_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_pfb_synth_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_pfb_synth_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_pfb_synth_plan_set_unfold_form": (_i, [_vp, _i]),
+    "sdsp_hip_pfb_synth_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_pfb_synth_plan_get_info": (_i, [_vp, C.POINTER(PfbSynthPlanInfo)]),
 }
 
 _lib = None

@@ -50,6 +50,7 @@ SOURCES = {
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA
     "pfb.hip": ["-ffp-contract=off"],  # the fold: fl(x h) then one addition per tap, never an FMA
+    "pfb_synth.hip": ["-ffp-contract=off"],  # the unfold: fl(g v) then one addition per frame, never an FMA
 }
 
 

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample) and the framed banks (stft, istft, welch, pfb); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -462,6 +462,15 @@ struct sdsp_hip_pfb_plan {
     sdsp_hip_fft_plan *inner = nullptr; // REAL: forward real-input plan of n_real = m, radix 2; COMPLEX: forward complex plan of m, RADIX_AUTO
     void *taps = nullptr;               // p m values, plan precision
     void *ws = nullptr;                 // REAL: ws_units x m reals (the slice's folded frames, transformed in place); COMPLEX: none
+    uint64_t ws_units = 0, workspace_bytes = 0;
+};
+
+struct sdsp_hip_pfb_synth_plan {
+    uint32_t m = 0, p = 0, hop = 0, hist = 0, bins = 0; // hist = p m - hop; bins = m / 2 + 1 (REAL) or m (COMPLEX)
+    int kind = 0, phase = 0, precision = 0, device = 0, form = 0;
+    sdsp_hip_fft_plan *inner = nullptr; // REAL: reverse real-input plan of n_real = m, radix 2; COMPLEX: reverse complex plan of m, RADIX_AUTO
+    void *taps = nullptr;               // the synthesis prototype: p m values, plan precision
+    void *ws = nullptr;                 // ws_units x m elements: the slice's spectra, transformed in place
     uint64_t ws_units = 0, workspace_bytes = 0;
 };
 
@@ -3592,6 +3601,270 @@ int sdsp_hip_pfb_process_host(sdsp_hip_pfb_plan *p, const void *host_in, uint64_
     int rc = st.in();
     if (!rc)
         rc = pfb_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, position, st.dev[2], nullptr);
+    return st.out(rc);
+}
+
+// ------------------------------------------------------------------ polyphase synthesis banks (pfb_synth.hip)
+
+namespace
+{
+uint64_t pfb_synth_out_esize(const sdsp_hip_pfb_synth_plan *p)
+{
+    return p->kind == SDSP_HIP_PFB_COMPLEX ? esize(p->precision) : real_size(p->precision);
+}
+
+int pfb_synth_run(sdsp_hip_pfb_synth_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                  uint64_t frames, uint64_t position, void *state, hipStream_t stream)
+{
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames per channel for one call");
+    if (channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * frames;
+    const bool cplx = p->kind == SDSP_HIP_PFB_COMPLEX;
+    if (p->inner->sync) // this call's launches report into a clean sticky abort word (as sdsp_hip_fft_exec)
+        HIP_TRY(hipMemsetAsync(fft1m_sticky(p->inner), 0, sizeof(unsigned), stream));
+    pfb_synth_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = p->hist ? state : nullptr;
+    a.taps = p->taps;
+    a.ws = p->ws;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.channels = channels;
+    a.frames = static_cast<uint32_t>(frames);
+    a.m = p->m;
+    a.p = p->p;
+    a.hop = p->hop;
+    a.hist = p->hist;
+    a.complex_out = cplx;
+    a.rotate = p->phase == SDSP_HIP_PFB_PHASE_TIME;
+    a.shift0 = static_cast<uint32_t>((position % p->m + p->hop) % p->m); // (position - hist) mod m: hist = p m - hop
+    a.form = p->form;
+    istft_args r{}; // REAL: the inverse STFT bank's seed and pack launches
+    r.in = in;
+    r.out = out;
+    r.state = a.state;
+    r.ws = p->ws;
+    r.in_stride = in_stride;
+    r.out_stride = out_stride;
+    r.channels = channels;
+    r.frames = a.frames;
+    r.n = p->m;
+    r.hop = p->hop;
+    r.hist = p->hist;
+    // before every unfold launch: those write the new pending sums where the old ones were
+    if (int rc = cplx ? launch_pfb_synth(p->precision, a, PFB_SYNTH_SEED, stream) : launch_istft(p->precision, r, ISTFT_SEED, stream))
+        return rc;
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
+        const uint64_t units = std::min(p->ws_units, total - g0);
+        a.g0 = r.g0 = g0;
+        a.units = units;
+        r.units = static_cast<uint32_t>(units);
+        if (int rc = cplx ? launch_pfb_synth(p->precision, a, PFB_SYNTH_COPY, stream) : launch_istft(p->precision, r, ISTFT_PACK, stream))
+            return rc;
+        if (int rc = fft_exec_pieces(p->inner, p->ws, units, stream, p->inner->variant))
+            return rc;
+        if (int rc = pfb_rects(g0, units, frames, [&](uint64_t c0, uint64_t nc, uint32_t j0, uint32_t nj) {
+                a.c0 = c0;
+                a.nc = nc;
+                a.j0 = j0;
+                a.nj = nj;
+                return launch_pfb_synth(p->precision, a, PFB_SYNTH_UNFOLD, stream);
+            }))
+            return rc;
+    }
+    return SDSP_HIP_OK;
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int pfb_synth_check(const sdsp_hip_pfb_synth_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride,
+                    uint64_t channels, uint64_t frames)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (frames > ~0ull / p->m)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    if (channels > 1 && (in_stride < frames * p->bins || out_stride < frames * p->hop))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= frames * bins and out_stride >= frames * hop");
+    return SDSP_HIP_OK;
+}
+} // namespace
+
+int sdsp_hip_pfb_synth_plan_create(sdsp_hip_pfb_synth_plan **out, uint32_t channels_m, uint32_t taps_per_channel, uint32_t hop,
+                                   const double *taps, int output_kind, int phase, int precision, uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    const uint32_t m = channels_m;
+    if (!sdsp_hip_is_power_of_2(m))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels_m must be a power of 2");
+    if (taps_per_channel == 0 || taps_per_channel > SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps_per_channel must be in [1, SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL]");
+    if (static_cast<uint64_t>(m) * taps_per_channel > SDSP_HIP_PFB_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "the prototype may have at most SDSP_HIP_PFB_MAX_TAPS taps");
+    if (hop == 0 || hop > m)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, channels_m]");
+    if (!taps)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "taps pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (output_kind != SDSP_HIP_PFB_REAL && output_kind != SDSP_HIP_PFB_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "output_kind must be SDSP_HIP_PFB_REAL or SDSP_HIP_PFB_COMPLEX");
+    if (phase != SDSP_HIP_PFB_PHASE_FRAME && phase != SDSP_HIP_PFB_PHASE_TIME)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "phase must be SDSP_HIP_PFB_PHASE_FRAME or SDSP_HIP_PFB_PHASE_TIME");
+    const bool cplx = output_kind == SDSP_HIP_PFB_COMPLEX;
+    if (m < (cplx ? 16u : 32u) || m > stft_max_n(precision))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED,
+                    "channels_m must be in the transform range (f32 .. 65536, f64 .. 32768; from 32 for real output, 16 for complex)");
+    if (int rc = use_device(device))
+        return rc;
+    const uint64_t taps_n = static_cast<uint64_t>(m) * taps_per_channel;
+    const uint64_t unit_bytes = static_cast<uint64_t>(m) * real_size(precision) * (cplx ? 2 : 1);
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kPfbDefaultBudget;
+    auto *p = new sdsp_hip_pfb_synth_plan();
+    p->m = m;
+    p->p = taps_per_channel;
+    p->hop = hop;
+    p->hist = static_cast<uint32_t>(taps_n - hop);
+    p->bins = cplx ? m : m / 2 + 1;
+    p->kind = output_kind;
+    p->phase = phase;
+    p->precision = precision;
+    p->device = device;
+    p->ws_units = slice_units(budget, unit_bytes);
+    p->workspace_bytes = p->ws_units * unit_bytes;
+    int rc = cplx ? fft_plan_create(&p->inner, m, SDSP_HIP_RADIX_AUTO, SDSP_HIP_REVERSE, precision, p->ws_units, device, 0)
+                  : fft_plan_create(&p->inner, m / 2, 2, SDSP_HIP_REVERSE, precision, p->ws_units, device, 2);
+    if (!rc) {
+        hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
+        if (e == hipSuccess)
+            e = upload_reals(taps, taps_n, precision, &p->taps);
+        if (e != hipSuccess)
+            rc = plan_fail(e, "pfb synthesis");
+    }
+    if (rc) {
+        sdsp_hip_pfb_synth_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_synth_plan_destroy(sdsp_hip_pfb_synth_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    free_bank(p->device, p->ws, p->taps, p->inner);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_synth_state_bytes(const sdsp_hip_pfb_synth_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * pfb_synth_out_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_synth_plan_set_variant(sdsp_hip_pfb_synth_plan *p, int variant)
+{
+    if (!p || variant < 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bad argument");
+    return set_inner_variant(p->inner, variant, "the inner plan has no such kernel variant", true);
+}
+
+int sdsp_hip_pfb_synth_plan_set_unfold_form(sdsp_hip_pfb_synth_plan *p, int form)
+{
+    if (!p || (form != 0 && form != 1))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "form must be 0 (chosen from the sizes) or 1 (plain)");
+    p->form = form;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_synth_plan_get_info(const sdsp_hip_pfb_synth_plan *p, sdsp_hip_pfb_synth_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->channels_m = p->m;
+    info->taps_per_channel = p->p;
+    info->hop = p->hop;
+    info->bins = p->bins;
+    info->hist = p->hist;
+    info->output_kind = p->kind;
+    info->phase = p->phase;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->workspace_bytes = p->workspace_bytes;
+    std::strncpy(info->kernel, select_kernel(p->inner, p->inner->variant).name, sizeof(info->kernel) - 1);
+    std::strncpy(info->unfold, p->form ? "plain" : pfb_synth_form_for(p->m, p->hop), sizeof(info->unfold) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_synth_plan_launches(const sdsp_hip_pfb_synth_plan *p, uint64_t channels, uint64_t frames, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    if (channels > ~0ull / frames)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many frames for one call");
+    const uint64_t total = channels * frames;
+    uint64_t n = slice_launch_count(p->inner, total, p->ws_units, 1); // per slice: the copy / pack launch and the transform's
+    for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units)
+        pfb_rects(g0, std::min(p->ws_units, total - g0), frames, [&](uint64_t, uint64_t, uint32_t, uint32_t) {
+            n++;
+            return 0;
+        });
+    *launches = n + (p->hist ? 1 : 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pfb_synth_process(sdsp_hip_pfb_synth_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                               uint64_t channels, uint64_t frames, uint64_t position, void *state, void *stream)
+{
+    if (int rc = pfb_synth_check(p, in, in_stride, out, out_stride, channels, frames))
+        return rc;
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    const uint64_t ies = esize(p->precision), oes = pfb_synth_out_esize(p);
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + frames * p->bins) * ies, ies, out,
+                                    ((channels - 1) * out_stride + frames * p->hop) * oes, oes, state, oes,
+                                    "in and out ranges overlap (the synthesis bank runs out of place)"))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    return pfb_synth_run(p, in, in_stride, out, out_stride, channels, frames, position, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_pfb_synth_process_host(sdsp_hip_pfb_synth_plan *p, const void *host_in, uint64_t in_stride, void *host_out,
+                                    uint64_t out_stride, uint64_t channels, uint64_t frames, uint64_t position, void *host_state)
+{
+    if (int rc = pfb_synth_check(p, host_in, in_stride, host_out, out_stride, channels, frames))
+        return rc;
+    if (channels == 0 || frames == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t in_bytes = ((channels - 1) * in_stride + frames * p->bins) * esize(p->precision);
+    const size_t out_bytes = ((channels - 1) * out_stride + frames * p->hop) * pfb_synth_out_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_pfb_synth_state_bytes(p, channels, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    host_stage st("pfb synthesis", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                                 { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = pfb_synth_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, frames, position, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

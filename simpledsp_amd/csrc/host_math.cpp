@@ -380,6 +380,138 @@ int istft_synthesis(uint32_t n, uint32_t hop, const double *w, int norm, double 
         g[i] = norm == SDSP_HIP_ISTFT_RAW ? w[i] : w[i] / env[i % hop];
     return SDSP_HIP_OK;
 }
+// minimum-norm least-squares solution x (n) of A x = b, A (r x n, row-major), by a one-sided Jacobi singular value decomposition of
+// the taller of A and A^T: columns of B are rotated until they are orthogonal (B V = U S), singular values below eps max(r, n) S_max
+// are dropped, and x = A^+ b is assembled from what is left.  Backward stable; the systems here have at most 2 P - 1 rows.
+// Cost per sweep: min(r, n)^2 / 2 column pairs of max(r, n) elements, a few sweeps -- over all residues of a prototype O(P^2 L) per sweep
+// (minutes on one thread only at the extreme P = 64, L = 2^20).
+void min_norm_solve(const std::vector<double> &a, size_t r, size_t n, const std::vector<double> &b, std::vector<double> &x)
+{
+    const bool transposed = n >= r; // B = A^T (n x r), else B = A (r x n)
+    const size_t rows = transposed ? n : r, cols = transposed ? r : n;
+    std::vector<double> w(rows * cols), v(cols * cols, 0.0); // column-major: column k at [k rows, (k + 1) rows)
+    for (size_t i = 0; i < r; i++)
+        for (size_t j = 0; j < n; j++)
+            (transposed ? w[i * rows + j] : w[j * rows + i]) = a[i * n + j];
+    for (size_t k = 0; k < cols; k++)
+        v[k * cols + k] = 1.0;
+    const double eps = 2.220446049250313e-16;
+    for (int sweep = 0; sweep < 60; sweep++) {
+        bool rotated = false;
+        for (size_t p = 0; p + 1 < cols; p++) {
+            for (size_t q = p + 1; q < cols; q++) {
+                double *wp = &w[p * rows], *wq = &w[q * rows];
+                double alpha = 0, beta = 0, gamma = 0;
+                for (size_t i = 0; i < rows; i++) {
+                    alpha += wp[i] * wp[i];
+                    beta += wq[i] * wq[i];
+                    gamma += wp[i] * wq[i];
+                }
+                if (gamma == 0.0 || std::fabs(gamma) <= eps * std::sqrt(alpha * beta))
+                    continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+                for (size_t i = 0; i < rows; i++) {
+                    const double xp = wp[i], xq = wq[i];
+                    wp[i] = c * xp - s * xq;
+                    wq[i] = s * xp + c * xq;
+                }
+                double *vp = &v[p * cols], *vq = &v[q * cols];
+                for (size_t i = 0; i < cols; i++) {
+                    const double xp = vp[i], xq = vq[i];
+                    vp[i] = c * xp - s * xq;
+                    vq[i] = s * xp + c * xq;
+                }
+            }
+        }
+        if (!rotated)
+            break;
+    }
+    std::vector<double> s2(cols);
+    double s2max = 0;
+    for (size_t k = 0; k < cols; k++) {
+        double acc = 0;
+        for (size_t i = 0; i < rows; i++)
+            acc += w[k * rows + i] * w[k * rows + i];
+        s2[k] = acc;
+        s2max = std::max(s2max, acc);
+    }
+    const double cut = eps * static_cast<double>(std::max(r, n));
+    x.assign(n, 0.0);
+    for (size_t k = 0; k < cols; k++) {
+        if (!(s2[k] > cut * cut * s2max))
+            continue;
+        // transposed: A^+ = U S^-1 V^T with w_k = s_k u_k: x += w_k (v_k . b) / s_k^2; else A^+ = V S^-1 U^T: x += v_k (w_k . b) / s_k^2
+        double dot = 0;
+        if (transposed) {
+            for (size_t i = 0; i < r; i++)
+                dot += v[k * cols + i] * b[i];
+            for (size_t j = 0; j < n; j++)
+                x[j] += w[k * rows + j] * (dot / s2[k]);
+        } else {
+            for (size_t i = 0; i < r; i++)
+                dot += w[k * rows + i] * b[i];
+            for (size_t j = 0; j < n; j++)
+                x[j] += v[k * cols + j] * (dot / s2[k]);
+        }
+    }
+}
+
+// the dual prototype of the polyphase synthesis banks: one small system per residue t0 of the hop
+int pfb_dual_prototype(uint32_t m, uint32_t p, uint32_t hop, const double *h, double *g)
+{
+    if (!h || !g)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null prototype pointer");
+    if (m < 2 || p == 0 || p > SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL || static_cast<uint64_t>(m) * p > SDSP_HIP_PFB_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "need m >= 2, 1 <= p <= SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL and p m <= SDSP_HIP_PFB_MAX_TAPS");
+    if (hop == 0 || hop > m)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "hop must be in [1, m]");
+    const int64_t len = static_cast<int64_t>(m) * p;
+    double worst = 0;
+    std::vector<double> a, b, x;
+    for (uint32_t t0 = 0; t0 < hop; t0++) {
+        const size_t n = static_cast<size_t>((len - t0 + hop - 1) / hop); // unknowns g[t0 + i hop]
+        a.clear();
+        b.clear();
+        for (int64_t k = 1 - static_cast<int64_t>(p); k < static_cast<int64_t>(p); k++) {
+            const size_t at = a.size();
+            a.resize(at + n, 0.0);
+            bool any = false;
+            for (size_t i = 0; i < n; i++) {
+                const int64_t q = static_cast<int64_t>(t0) + static_cast<int64_t>(i) * hop + k * m;
+                if (q >= 0 && q < len && h[q] != 0.0) {
+                    a[at + i] = h[q];
+                    any = true;
+                }
+            }
+            if (any) {
+                b.push_back(k == 0 ? 1.0 : 0.0);
+            } else { // a row that is identically zero: nothing to solve, and nothing can make its k = 0 right-hand side
+                a.resize(at);
+                if (k == 0)
+                    worst = std::max(worst, 1.0);
+            }
+        }
+        const size_t r = b.size();
+        x.assign(n, 0.0);
+        if (r)
+            min_norm_solve(a, r, n, b, x);
+        for (size_t i = 0; i < r; i++) {
+            double acc = 0;
+            for (size_t j = 0; j < n; j++)
+                acc += a[i * n + j] * x[j];
+            worst = std::max(worst, std::fabs(acc - b[i]));
+        }
+        for (size_t i = 0; i < n; i++)
+            g[t0 + i * hop] = x[i];
+    }
+    if (!(worst <= 1e-9))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the analysis prototype has no dual of its own support at this hop (perfect-reconstruction "
+                                              "residual above 1e-9): use a shorter hop or another prototype");
+    return SDSP_HIP_OK;
+}
 } // namespace sdsp_hip
 
 using namespace sdsp_hip;
@@ -537,6 +669,10 @@ int sdsp_hip_pfb_prototype(int window_kind, uint32_t m, uint32_t p, double *h)
     if (m < 2 || p == 0 || p > SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL || static_cast<uint64_t>(m) * p > SDSP_HIP_PFB_MAX_TAPS)
         return fail(SDSP_HIP_ERR_INVALID_SIZE, "need m >= 2, 1 <= p <= SDSP_HIP_PFB_MAX_TAPS_PER_CHANNEL and p m <= SDSP_HIP_PFB_MAX_TAPS");
     return windowed_sinc_lowpass(static_cast<uint64_t>(m) * p, 1.0 / m, window_kind, h);
+}
+int sdsp_hip_pfb_dual_prototype(uint32_t m, uint32_t p, uint32_t hop, const double *h, double *g)
+{
+    return pfb_dual_prototype(m, p, hop, h, g);
 }
 int sdsp_hip_welch_frames(uint32_t n_fft, uint32_t hop, uint64_t position, uint64_t samples, uint64_t *frames)
 {

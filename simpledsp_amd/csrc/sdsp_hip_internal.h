@@ -338,4 +338,29 @@ int launch_pfb(int precision, const pfb_args &a, int step, void *stream);
 const char *pfb_form_for(uint32_t m, uint32_t hop);
 // host_math.cpp: symmetric-window sinc low-pass of `taps` points with cutoff `cutoff` (fraction of Nyquist) and unit DC gain
 int windowed_sinc_lowpass(uint64_t taps, double cutoff, int window_kind, double *h);
+// polyphase synthesis banks (pfb_synth.hip): the seed launch for complex elements (real banks use the inverse
+// STFT bank's, ISTFT_SEED), the copy of one slice's complex spectra into the workspace (real banks pack with ISTFT_PACK), and the
+// unfold launch of one rectangle of (stream, frame) units behind the plan's reverse transform
+enum { PFB_SYNTH_SEED = 0, PFB_SYNTH_COPY = 1, PFB_SYNTH_UNFOLD = 2 };
+struct pfb_synth_args {
+    const void *in;     // complex bins, plan precision
+    void *out;
+    void *state;        // nullable; channels x hist elements of the output kind, time order
+    const void *taps;   // device, plan precision, p x m reals
+    void *ws;           // the slice's rows of m elements: spectra in, v_j after the transform
+    uint64_t in_stride, out_stride, channels;
+    uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, frame) numbering
+    uint64_t units;
+    uint64_t c0, nc;    // unfold: the rectangle's channels ...
+    uint32_t j0, nj;    // ... and frames
+    uint32_t frames, m, p, hop, hist;
+    uint32_t shift0;    // TIME: (position - hist) mod m
+    int complex_out, rotate;
+    int form;           // 0: chosen from hop and m; 1: the plain per-position form (measurement and cross-checks)
+};
+int launch_pfb_synth(int precision, const pfb_synth_args &a, int step, void *stream);
+// the unfold form a plan of these sizes runs: "sliding" where hop = m, else "plain"
+const char *pfb_synth_form_for(uint32_t m, uint32_t hop);
+// host_math.cpp: the minimum-norm dual of the analysis prototype h at hop `hop` (g: p m doubles); INVALID_ARG where none exists
+int pfb_dual_prototype(uint32_t m, uint32_t p, uint32_t hop, const double *h, double *g);
 } // namespace sdsp_hip
