@@ -51,6 +51,7 @@ SOURCES = {
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA
     "pfb.hip": ["-ffp-contract=off"],  # the fold: fl(x h) then one addition per tap, never an FMA
     "pfb_synth.hip": ["-ffp-contract=off"],  # the unfold: fl(g v) then one addition per frame, never an FMA
+    "stream_carry.hip": [],  # the banks' carried state: copies only, no arithmetic to pin
 }
 
 

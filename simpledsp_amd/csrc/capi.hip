@@ -2369,8 +2369,6 @@ int stft_run(sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, void *ou
     a.ws = p->ws;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
-    a.channels = channels;
-    a.samples = samples;
     a.frames = static_cast<uint32_t>(frames);
     a.n = p->n;
     a.hop = p->hop;
@@ -2386,7 +2384,8 @@ int stft_run(sdsp_hip_stft_plan *p, const void *in, uint64_t in_stride, void *ou
         if (int rc = launch_stft(p->precision, a, STFT_EMIT, stream))
             return rc;
     }
-    return launch_stft(p->precision, a, STFT_STATE, stream); // after every frame launch: they may read the old history
+    // after every frame launch: they may read the old history
+    return carry_history(p->precision, real_size(p->precision), in, in_stride, state, channels, samples, p->hist, stream, "stft");
 }
 
 // argument checks shared by process and process_host (device pointers or not)
@@ -2574,13 +2573,13 @@ int istft_run(sdsp_hip_istft_plan *p, const void *in, uint64_t in_stride, void *
     a.ws = p->ws;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
-    a.channels = channels;
     a.frames = static_cast<uint32_t>(frames);
     a.n = p->n;
     a.hop = p->hop;
     a.hist = p->hist;
     // before every overlap-add launch: those write the new pending sums where the old ones were
-    if (int rc = launch_istft(p->precision, a, ISTFT_SEED, stream))
+    if (int rc = carry_seed(p->precision, real_size(p->precision), out, out_stride, state, channels, frames * p->hop, p->hist, stream,
+                            "istft"))
         return rc;
     for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
         a.g0 = g0;
@@ -3037,16 +3036,10 @@ int welch_run(sdsp_hip_welch_plan *p, const void *in, uint64_t in_stride, uint64
         if (int rc = launch_welch(p->precision, a, WELCH_COMBINE, stream))
             return rc;
     }
-    if (!state || samples == 0)
+    if (samples == 0)
         return SDSP_HIP_OK;
-    stft_args s{}; // after every frame launch: they may read the old history
-    s.in = in;
-    s.state = state;
-    s.in_stride = in_stride;
-    s.channels = channels;
-    s.samples = samples;
-    s.hist = p->hist;
-    return launch_stft(p->precision, s, STFT_STATE, stream);
+    // after every frame launch: they may read the old history (the label keeps the message texts of the STFT bank's launch)
+    return carry_history(p->precision, real_size(p->precision), in, in_stride, state, channels, samples, p->hist, stream, "stft");
 }
 
 // argument checks shared by process and process_host (device pointers or not)
@@ -3349,19 +3342,12 @@ int pfb_run(sdsp_hip_pfb_plan *p, const void *in, uint64_t in_stride, void *out,
     a.rotate = p->phase == SDSP_HIP_PFB_PHASE_TIME;
     a.shift0 = static_cast<uint32_t>((position % p->m + p->hop) % p->m); // (position - hist) mod m: hist = p m - hop
     a.form = p->form;
-    stft_args e{}; // REAL: the STFT bank's emit and state launches
-    e.in = in;
+    stft_args e{}; // REAL: the STFT bank's emit launch
     e.out = out;
-    e.state = p->hist ? state : nullptr;
     e.ws = p->ws;
-    e.in_stride = in_stride;
     e.out_stride = out_stride;
-    e.channels = channels;
-    e.samples = samples;
     e.frames = static_cast<uint32_t>(frames);
     e.n = p->m;
-    e.hop = p->hop;
-    e.hist = p->hist;
     e.output = SDSP_HIP_STFT_COMPLEX;
     char *const ob = static_cast<char *>(out);
     const uint64_t oes = pfb_out_esize(p);
@@ -3375,7 +3361,7 @@ int pfb_run(sdsp_hip_pfb_plan *p, const void *in, uint64_t in_stride, void *out,
                 a.nc = nc;
                 a.j0 = j0;
                 a.nj = nj;
-                return launch_pfb(p->precision, a, PFB_FOLD, stream);
+                return launch_pfb(p->precision, a, stream);
             }))
             return rc;
         if (!cplx) {
@@ -3399,13 +3385,9 @@ int pfb_run(sdsp_hip_pfb_plan *p, const void *in, uint64_t in_stride, void *out,
                 return rc;
         }
     }
-    // after every fold launch: they may read the old history
-    if (!cplx)
-        return launch_stft(p->precision, e, STFT_STATE, stream);
-    a.state_out = p->hist ? state : nullptr;
-    a.channels = channels;
-    a.samples = samples;
-    return launch_pfb(p->precision, a, PFB_STATE, stream);
+    // after every fold launch: they may read the old history (the labels keep each kind's message texts)
+    return carry_history(p->precision, cplx ? esize(p->precision) : real_size(p->precision), in, in_stride, state, channels, samples,
+                         p->hist, stream, cplx ? "pfb" : "stft");
 }
 
 // argument checks shared by process and process_host (device pointers or not)
@@ -3632,7 +3614,6 @@ int pfb_synth_run(sdsp_hip_pfb_synth_plan *p, const void *in, uint64_t in_stride
     a.ws = p->ws;
     a.in_stride = in_stride;
     a.out_stride = out_stride;
-    a.channels = channels;
     a.frames = static_cast<uint32_t>(frames);
     a.m = p->m;
     a.p = p->p;
@@ -3642,20 +3623,15 @@ int pfb_synth_run(sdsp_hip_pfb_synth_plan *p, const void *in, uint64_t in_stride
     a.rotate = p->phase == SDSP_HIP_PFB_PHASE_TIME;
     a.shift0 = static_cast<uint32_t>((position % p->m + p->hop) % p->m); // (position - hist) mod m: hist = p m - hop
     a.form = p->form;
-    istft_args r{}; // REAL: the inverse STFT bank's seed and pack launches
+    istft_args r{}; // REAL: the inverse STFT bank's pack launch
     r.in = in;
-    r.out = out;
-    r.state = a.state;
     r.ws = p->ws;
     r.in_stride = in_stride;
-    r.out_stride = out_stride;
-    r.channels = channels;
     r.frames = a.frames;
     r.n = p->m;
-    r.hop = p->hop;
-    r.hist = p->hist;
-    // before every unfold launch: those write the new pending sums where the old ones were
-    if (int rc = cplx ? launch_pfb_synth(p->precision, a, PFB_SYNTH_SEED, stream) : launch_istft(p->precision, r, ISTFT_SEED, stream))
+    // before every unfold launch: those write the new pending sums where the old ones were (the labels keep each kind's message texts)
+    if (int rc = carry_seed(p->precision, pfb_synth_out_esize(p), out, out_stride, a.state, channels, frames * p->hop, p->hist, stream,
+                            cplx ? "pfb synthesis" : "istft"))
         return rc;
     for (uint64_t g0 = 0; g0 < total; g0 += p->ws_units) {
         const uint64_t units = std::min(p->ws_units, total - g0);

@@ -16,26 +16,12 @@
 // reads 0, and the straddling channel's [s_b - (T-1), s_b) -- already overwritten by the previous slice's scatter -- reads the
 // previous slice's carry.  Every global access is 16 B per lane where the element offset is a multiple of 16 B and the chunk is
 // whole; the rest go element by element.
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
 namespace
 {
-constexpr int kThreads = 256;
-
-template <typename R> struct os_vec;
-template <> struct os_vec<float> {
-    typedef float type __attribute__((ext_vector_type(4)));
-    static constexpr int lanes = 4; // 16 B: four samples, two complex values
-};
-template <> struct os_vec<double> {
-    typedef double type __attribute__((ext_vector_type(2)));
-    static constexpr int lanes = 2; // 16 B: two samples, one complex value
-};
-
 // one slice's view of the stream; every quantity the kernels derive per unit comes from these
 struct os_view {
     uint64_t stride, samples;
@@ -71,10 +57,10 @@ template <typename R> __device__ __forceinline__ R load_input(const os_view &v, 
 
 // VEC consecutive inputs s0 .. s0+VEC of channel c: one 16-B load when the chunk is plain data and aligned
 template <typename R> __device__ __forceinline__ void load_chunk(const os_view &v, const os_ptrs<R> &q, uint64_t c, int64_t s0,
-                                                                  R (&out)[os_vec<R>::lanes])
+                                                                  R (&out)[vec16<R>::lanes])
 {
-    using V = typename os_vec<R>::type;
-    constexpr int VEC = os_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     const int64_t lo = c == v.cin_c ? v.cin_hi : 0;
     const uint64_t off = c * v.stride + static_cast<uint64_t>(s0);
     if (v.vec_ok && s0 >= lo && static_cast<uint64_t>(s0) + VEC <= v.samples && off % VEC == 0) {
@@ -91,8 +77,8 @@ template <typename R> __device__ __forceinline__ void load_chunk(const os_view &
 
 template <typename R> __global__ __launch_bounds__(kThreads) void sdsp_fir_os_frame(os_view v, os_ptrs<R> q)
 {
-    using V = typename os_vec<R>::type;
-    constexpr int VEC = os_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
     const uint64_t u = gid >> v.lc;
     if (u >= v.units)
@@ -141,8 +127,8 @@ template <typename R> __global__ __launch_bounds__(kThreads) void sdsp_fir_os_fr
 
 template <typename R> __global__ __launch_bounds__(kThreads) void sdsp_fir_os_scatter(os_view v, os_ptrs<R> q)
 {
-    using V = typename os_vec<R>::type;
-    constexpr int VEC = os_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
     const uint64_t u = gid >> v.lc;
     if (u >= v.units)
@@ -204,17 +190,9 @@ template <typename R> __global__ __launch_bounds__(kThreads) void sdsp_fir_os_st
         state[c_lo * t1 + i] = tails[i];
 }
 
-uint32_t log2u(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 template <typename R> int launch_os(const fir_os_args &a, int step, hipStream_t stream)
 {
-    constexpr int VEC = os_vec<R>::lanes;
+    constexpr int VEC = vec16<R>::lanes;
     const uint64_t g1 = a.g0 + a.units;
     if (step == FIR_OS_STATE) {
         const uint64_t c_lo = a.g0 / a.pairs, count = g1 / a.pairs - c_lo;
@@ -242,18 +220,15 @@ template <typename R> int launch_os(const fir_os_args &a, int step, hipStream_t 
         v.vec_ok = (reinterpret_cast<uintptr_t>(a.data) % 16 == 0 && (a.stride * sizeof(R)) % 16 == 0) ? 1 : 0;
         os_ptrs<R> q{ static_cast<R *>(a.data), static_cast<const R *>(a.state), static_cast<R *>(a.ws), static_cast<R *>(a.tails),
                       static_cast<const R *>(a.carry_in), static_cast<R *>(a.carry_out) };
-        const uint64_t threads = a.units << v.lc, blocks = (threads + kThreads - 1) / kThreads;
-        if (blocks > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "fir slice too large for one launch");
+        dim3 grid;
+        if (int rc = grid_for(a.units << v.lc, "fir slice", &grid))
+            return rc;
         if (step == FIR_OS_FRAME)
-            hipLaunchKernelGGL(sdsp_fir_os_frame<R>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, v, q);
+            hipLaunchKernelGGL(sdsp_fir_os_frame<R>, grid, dim3(kThreads), 0, stream, v, q);
         else
-            hipLaunchKernelGGL(sdsp_fir_os_scatter<R>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, v, q);
+            hipLaunchKernelGGL(sdsp_fir_os_scatter<R>, grid, dim3(kThreads), 0, stream, v, q);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(SDSP_HIP_ERR_HIP, std::string("fir overlap-save launch: ") + hipGetErrorString(e));
-    return SDSP_HIP_OK;
+    return launch_status("fir overlap-save");
 }
 } // namespace
 

@@ -20,9 +20,7 @@
 //                              wave-uniform), each lane four periods of that phase, 64 apart, on four accumulators.
 //   sdsp_resample_plain_kernel variant 1: one output per thread straight from global memory (+ sdsp_resample_state_kernel for the
 //                              history), the independent cross-check.
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
@@ -376,14 +374,6 @@ template <typename R> __global__ __launch_bounds__(256) void sdsp_resample_state
         st[j] = j < a.samples ? inp[a.samples - 1 - j] : st[j - a.samples];
 }
 
-uint32_t ceil_log2(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 uint32_t gcd_u32(uint32_t a, uint32_t b)
 {
     while (b) {
@@ -423,8 +413,8 @@ rs_launch select_resample(int precision, const resample_args &ra, int variant)
         l.name = "sdsp_resample_dec_kernel";
         l.hist = kBlk * ((ra.taps + kBlk - 1) / kBlk);
         // threads per row as launch_fir: enough for the row, never fewer than the history needs; 128-thread workgroups
-        uint32_t lg = ceil_log2((ra.samples + kBlk - 1) / kBlk);
-        const uint32_t lmin = ceil_log2(l.hist / kBlk);
+        uint32_t lg = log2u((ra.samples + kBlk - 1) / kBlk);
+        const uint32_t lmin = log2u(l.hist / kBlk);
         if (lg < lmin)
             lg = lmin;
         l.threads = lmin <= 7 ? 128 : 256;

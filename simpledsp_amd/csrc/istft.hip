@@ -1,14 +1,10 @@
 // istft.hip -- the streaming layer of the inverse STFT bank (sdsp_hip_istft_*).
 //
-// One sdsp_hip_istft_process call runs as one seed launch, then slices of pack -> transform -> overlap-add launches over the plan's
+// One sdsp_hip_istft_process call runs as the pending-sum seed (stream_carry.hip: carry_seed), then slices of pack -> transform -> overlap-add launches over the plan's
 // workspace.  The unit of work is one frame of N / 2 + 1 bins of one channel; units are numbered channel-major (g = c F + j, F frames
 // per channel) and a slice is a contiguous range of them, so a slice may start or end inside a channel.  Output position t of a
 // channel lives in out[c out_stride + t] for t < S = F hop and in state[c hist + t - S] above (the new pending sums).
 //
-//   sdsp_istft_seed  before the first slice, with a state: the old pending sums P[0 .. min(hist, S)) go to out; for S < hist the rest,
-//                    P[S .. hist), moves down to the start of the state row in place (one workgroup per row, chunks walked from the
-//                    low end up with a barrier between each chunk's reads and its writes: the mirror of stft.hip's
-//                    sdsp_stft_state_shift).  Afterwards every pending sum sits where its position lives.
 //   sdsp_istft_pack  bins -> the packed half spectrum the reverse real-input transform reads: Z[0] = (Re X[0], Re X[N/2]), Z[k] = X[k];
 //                    16-B stores (two f32 bins or one f64 bin per lane)
 //   (the plan's reverse real-input transform of n_real = N, radix 2, 1 / N scaled, in place on the slice: unchanged kernels)
@@ -19,30 +15,12 @@
 //                    the sum back to t's place (dropped past S without a state).  Every addition of the contract happens in
 //                    ascending j across slices too, so any slicing and any split into calls gives the same bits.  VEC consecutive
 //                    positions per lane when hop is a multiple of VEC: frame edges then fall on vector boundaries.
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
 namespace
 {
-constexpr int kThreads = 256;
-
-template <typename R, int VEC> struct is_vec {
-    typedef R type __attribute__((ext_vector_type(VEC)));
-};
-template <typename R> struct is_vec<R, 1> {
-    typedef R type;
-};
-template <typename R> struct is_lanes; // reals per 16 B
-template <> struct is_lanes<float> { static constexpr int value = 4; };
-template <> struct is_lanes<double> { static constexpr int value = 2; };
-
-template <typename R> struct is_cplx;
-template <> struct is_cplx<float> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct is_cplx<double> { typedef double type __attribute__((ext_vector_type(2))); };
-
 // one slice's view of the call; the slice's first unit is frame j0 of channel c0, its last frame j1 of channel c1
 struct is_view {
     uint64_t in_stride, out_stride;
@@ -59,44 +37,12 @@ struct is_view {
     uint32_t has_state;
 };
 
-// a / b with the 32-bit divide when both fit (the common case)
-__device__ __forceinline__ uint64_t udiv(uint64_t a, uint64_t b)
-{
-    return (a | b) < (1ull << 32) ? static_cast<uint64_t>(static_cast<uint32_t>(a) / static_cast<uint32_t>(b)) : a / b;
-}
-
-template <typename R>
-__global__ __launch_bounds__(kThreads) void sdsp_istft_seed(R *__restrict__ out, R *state, uint64_t out_stride, uint64_t samples,
-                                                            uint32_t hist)
-{
-    const uint64_t c = blockIdx.x;
-    R *row = state + c * hist;
-    const uint32_t m = samples < hist ? static_cast<uint32_t>(samples) : hist;
-    for (uint32_t i = threadIdx.x; i < m; i += kThreads)
-        out[c * out_stride + i] = row[i];
-    if (samples >= hist)
-        return;
-    __syncthreads(); // every read of row[0 .. m) above happens before the shift writes there
-    const uint32_t s = static_cast<uint32_t>(samples), keep = hist - s;
-    const uint32_t chunks = (keep + kThreads - 1) / kThreads;
-    for (uint32_t q = 0; q < chunks; q++) { // low to high: a chunk reads only above every index written before it
-        const uint32_t i = q * kThreads + threadIdx.x;
-        R val = R(0);
-        if (i < keep)
-            val = row[i + s];
-        __syncthreads();
-        if (i < keep)
-            row[i] = val;
-        __syncthreads();
-    }
-}
-
 template <typename R>
 __global__ __launch_bounds__(kThreads) void sdsp_istft_pack(is_view v, const R *__restrict__ in, R *__restrict__ ws)
 {
-    using C2 = typename is_cplx<R>::type;
-    constexpr int PB = is_lanes<R>::value / 2; // packed bins per lane (16 B)
-    using V = typename is_vec<R, 2 * PB>::type;
+    using C2 = typename cplx_pair<R>::type;
+    constexpr int PB = vec16<R>::lanes / 2; // packed bins per lane (16 B)
+    using V = typename vec_n<R, 2 * PB>::type;
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
     const uint64_t u = gid >> v.lc;
     if (u >= v.units)
@@ -121,7 +67,7 @@ __global__ __launch_bounds__(kThreads) void sdsp_istft_pack(is_view v, const R *
 template <typename R, int VEC>
 __global__ __launch_bounds__(kThreads) void sdsp_istft_ola(is_view v, const R *__restrict__ ws, const R *__restrict__ g, R *out, R *state)
 {
-    using V = typename is_vec<R, VEC>::type;
+    using V = typename vec_n<R, VEC>::type;
     const uint64_t p = (static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x);
     if (p >= v.positions)
         return;
@@ -162,80 +108,55 @@ __global__ __launch_bounds__(kThreads) void sdsp_istft_ola(is_view v, const R *_
         *reinterpret_cast<V *>(place) = acc;
 }
 
-uint32_t log2u(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 template <typename R> int launch(const istft_args &a, int step, hipStream_t stream)
 {
     R *out = static_cast<R *>(a.out);
     R *state = static_cast<R *>(a.state);
     const uint64_t samples = static_cast<uint64_t>(a.frames) * a.hop;
-    if (step == ISTFT_SEED) {
-        if (a.hist == 0 || !state || a.channels == 0)
-            return SDSP_HIP_OK;
-        if (a.channels > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "istft state too large for one launch");
-        hipLaunchKernelGGL(sdsp_istft_seed<R>, dim3(static_cast<uint32_t>(a.channels)), dim3(kThreads), 0, stream, out, state,
-                           a.out_stride, samples, a.hist);
+    is_view v{};
+    v.in_stride = a.in_stride;
+    v.out_stride = a.out_stride;
+    v.g0 = a.g0;
+    v.c0 = a.g0 / a.frames;
+    v.j0 = static_cast<uint32_t>(a.g0 - v.c0 * a.frames);
+    const uint64_t g1 = a.g0 + a.units - 1;
+    v.c1 = g1 / a.frames;
+    v.j1 = static_cast<uint32_t>(g1 - v.c1 * a.frames);
+    v.frames = a.frames;
+    v.units = a.units;
+    v.n = a.n;
+    v.hop = a.hop;
+    v.hist = a.hist;
+    v.samples = samples;
+    v.has_state = state ? 1 : 0;
+    const R *ws = static_cast<const R *>(a.ws);
+    dim3 grid;
+    if (step == ISTFT_PACK) {
+        v.lc = log2u(a.n / vec16<R>::lanes); // N / 2 packed bins, 16 B of them per lane
+        if (int rc = grid_for(static_cast<uint64_t>(a.units) << v.lc, "istft slice", &grid))
+            return rc;
+        hipLaunchKernelGGL(sdsp_istft_pack<R>, grid, dim3(kThreads), 0, stream, v, static_cast<const R *>(a.in), static_cast<R *>(a.ws));
     } else {
-        is_view v{};
-        v.in_stride = a.in_stride;
-        v.out_stride = a.out_stride;
-        v.g0 = a.g0;
-        v.c0 = a.g0 / a.frames;
-        v.j0 = static_cast<uint32_t>(a.g0 - v.c0 * a.frames);
-        const uint64_t g1 = a.g0 + a.units - 1;
-        v.c1 = g1 / a.frames;
-        v.j1 = static_cast<uint32_t>(g1 - v.c1 * a.frames);
-        v.frames = a.frames;
-        v.units = a.units;
-        v.n = a.n;
-        v.hop = a.hop;
-        v.hist = a.hist;
-        v.samples = samples;
-        v.has_state = state ? 1 : 0;
-        const R *ws = static_cast<const R *>(a.ws);
-        if (step == ISTFT_PACK) {
-            v.lc = log2u(a.n / is_lanes<R>::value); // N / 2 packed bins, 16 B of them per lane
-            const uint64_t threads = static_cast<uint64_t>(a.units) << v.lc, blocks = (threads + kThreads - 1) / kThreads;
-            if (blocks > 0x7fffffffull)
-                return fail(SDSP_HIP_ERR_UNSUPPORTED, "istft slice too large for one launch");
-            hipLaunchKernelGGL(sdsp_istft_pack<R>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, v,
-                               static_cast<const R *>(a.in), static_cast<R *>(a.ws));
-        } else {
-            const uint32_t je0 = v.c0 == v.c1 ? v.j1 + 1 : a.frames;
-            v.len0 = static_cast<uint64_t>(je0 - v.j0) * a.hop + a.hist;
-            v.len_full = samples + a.hist;
-            const uint64_t len1 = v.c0 == v.c1 ? 0 : static_cast<uint64_t>(v.j1 + 1) * a.hop + a.hist;
-            const uint64_t middle = v.c1 > v.c0 + 1 ? (v.c1 - v.c0 - 1) * v.len_full : 0;
-            const uint64_t total = v.len0 + middle + len1;
-            constexpr int VEC = is_lanes<R>::value;
-            // VEC positions per lane: frame edges (multiples of hop, + N) and the out / state split (S) on vector boundaries, and every
-            // vector address 16-B aligned
-            const bool vec = a.hop % VEC == 0 && reinterpret_cast<uintptr_t>(a.out) % 16 == 0 && a.out_stride % VEC == 0 &&
-                             reinterpret_cast<uintptr_t>(a.state) % 16 == 0;
-            v.positions = vec ? total / VEC : total;
-            const uint64_t blocks = (v.positions + kThreads - 1) / kThreads;
-            if (blocks > 0x7fffffffull)
-                return fail(SDSP_HIP_ERR_UNSUPPORTED, "istft slice too large for one launch");
-            const dim3 grid(static_cast<uint32_t>(blocks));
-            if (vec)
-                hipLaunchKernelGGL((sdsp_istft_ola<R, VEC>), grid, dim3(kThreads), 0, stream, v, ws, static_cast<const R *>(a.g), out,
-                                   state);
-            else
-                hipLaunchKernelGGL((sdsp_istft_ola<R, 1>), grid, dim3(kThreads), 0, stream, v, ws, static_cast<const R *>(a.g), out,
-                                   state);
-        }
+        const uint32_t je0 = v.c0 == v.c1 ? v.j1 + 1 : a.frames;
+        v.len0 = static_cast<uint64_t>(je0 - v.j0) * a.hop + a.hist;
+        v.len_full = samples + a.hist;
+        const uint64_t len1 = v.c0 == v.c1 ? 0 : static_cast<uint64_t>(v.j1 + 1) * a.hop + a.hist;
+        const uint64_t middle = v.c1 > v.c0 + 1 ? (v.c1 - v.c0 - 1) * v.len_full : 0;
+        const uint64_t total = v.len0 + middle + len1;
+        constexpr int VEC = vec16<R>::lanes;
+        // VEC positions per lane: frame edges (multiples of hop, + N) and the out / state split (S) on vector boundaries, and every
+        // vector address 16-B aligned
+        const bool vec = a.hop % VEC == 0 && reinterpret_cast<uintptr_t>(a.out) % 16 == 0 && a.out_stride % VEC == 0 &&
+                         reinterpret_cast<uintptr_t>(a.state) % 16 == 0;
+        v.positions = vec ? total / VEC : total;
+        if (int rc = grid_for(v.positions, "istft slice", &grid))
+            return rc;
+        if (vec)
+            hipLaunchKernelGGL((sdsp_istft_ola<R, VEC>), grid, dim3(kThreads), 0, stream, v, ws, static_cast<const R *>(a.g), out, state);
+        else
+            hipLaunchKernelGGL((sdsp_istft_ola<R, 1>), grid, dim3(kThreads), 0, stream, v, ws, static_cast<const R *>(a.g), out, state);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(SDSP_HIP_ERR_HIP, std::string("istft launch: ") + hipGetErrorString(e));
-    return SDSP_HIP_OK;
+    return launch_status("istft");
 }
 } // namespace
 

@@ -1,6 +1,7 @@
 // pfb.hip -- the fold kernel of the polyphase filter-bank channelizer banks (sdsp_hip_pfb_*).
 //
-// One sdsp_hip_pfb_process call runs as slices of fold -> transform (-> emit, real input) launches, then one state launch.  The unit
+// One sdsp_hip_pfb_process call runs as slices of fold -> transform (-> emit, real input) launches, then the history update
+// (stream_carry.hip: carry_history).  The unit
 // of work is one frame of M elements of one channel (an element is one real or one interleaved complex sample).
 //
 //   sdsp_pfb_fold   u_j[r] = sum over p < P of fl(x[j D + p M + r] h[p M + r]) in ascending p, every product and sum rounded on its own
@@ -13,34 +14,16 @@
 //                       chain, loads each sample once and adds its product into every frame that covers it -- P + J - 1 loads for J
 //                       outputs.  The J taps in use sit in a register ring (tap p is loaded at step m = p and last used at p + J - 1).
 //                     plain form (every other D, J = 1): one frame per thread, P loads per output; consecutive workgroups are placed on
-//                       one XCD (the STFT bank's placement), so the re-reads of overlapping frames hit its L2.
+//                       one XCD (stream_dev.h: xcd_block), so the re-reads of overlapping frames hit its L2.
 //                   Loads and stores are 16 bytes wide where the element offset allows (history, odd strides and rotations that split a
 //                   vector go element by element).
-//   sdsp_pfb_state_flat / _shift   the STFT bank's state kernels for complex elements (real banks launch stft.hip's own).
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
 namespace
 {
-constexpr int kThreads = 256;
 constexpr int kSlide = 8; // frames per thread of the sliding form
-
-template <typename R> struct pf_vec;
-template <> struct pf_vec<float> {
-    typedef float type __attribute__((ext_vector_type(4)));
-    static constexpr int lanes = 4;
-};
-template <> struct pf_vec<double> {
-    typedef double type __attribute__((ext_vector_type(2)));
-    static constexpr int lanes = 2;
-};
-
-template <typename R> struct pf_cplx;
-template <> struct pf_cplx<float> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct pf_cplx<double> { typedef double type __attribute__((ext_vector_type(2))); };
 
 // one fold launch: channels [c0, ..) x frames [j0, j0 + nj), as units (channel, chain a < q, chunk k < kc) with k fastest
 struct pf_view {
@@ -54,20 +37,12 @@ struct pf_view {
     uint32_t rotate, shift0, xcd;
 };
 
-// workgroup b -> the position it works on: the blocks that share an XCD (b mod 8) get one contiguous range (the STFT bank's
-// placement).  A bijection on [0, nb) for every nb.
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb)
-{
-    const uint32_t q = nb / 8, r = nb % 8, x = b % 8;
-    return x * q + min(x, r) + b / 8;
-}
-
 // VEC reals = VEC / CPX elements of channel c from element position q0 of x
 template <typename R, int CPX>
-__device__ __forceinline__ typename pf_vec<R>::type load_x(const pf_view &v, const R *in, const R *state, uint64_t c, uint64_t q0)
+__device__ __forceinline__ typename vec16<R>::type load_x(const pf_view &v, const R *in, const R *state, uint64_t c, uint64_t q0)
 {
-    using V = typename pf_vec<R>::type;
-    constexpr int VEC = pf_vec<R>::lanes, EPT = VEC / CPX;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes, EPT = VEC / CPX;
     V x;
     const uint64_t off = (c * v.in_stride + (q0 - v.hist)) * CPX; // in reals; only used where q0 >= hist
     if (v.in_vec_ok && q0 >= v.hist && off % VEC == 0) {
@@ -89,10 +64,10 @@ __device__ __forceinline__ typename pf_vec<R>::type load_x(const pf_view &v, con
 }
 
 // the taps of VEC reals from tap index t0 (= p M + the thread's first element): one tap per element
-template <typename R, int CPX> __device__ __forceinline__ typename pf_vec<R>::type load_taps(const R *taps, uint64_t t0)
+template <typename R, int CPX> __device__ __forceinline__ typename vec16<R>::type load_taps(const R *taps, uint64_t t0)
 {
-    using V = typename pf_vec<R>::type;
-    constexpr int VEC = pf_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     if (CPX == 1)
         return *reinterpret_cast<const V *>(taps + t0); // t0 is a multiple of VEC: M is, and so is the thread's first element
     V t;
@@ -106,9 +81,9 @@ template <typename R, int CPX, int J>
 __global__ __launch_bounds__(kThreads) void sdsp_pfb_fold(pf_view v, const R *__restrict__ in, const R *__restrict__ state,
                                                           const R *__restrict__ taps, R *__restrict__ dst)
 {
-    using V = typename pf_vec<R>::type;
-    using C2 = typename pf_cplx<R>::type;
-    constexpr int VEC = pf_vec<R>::lanes, EPT = VEC / CPX;
+    using V = typename vec16<R>::type;
+    using C2 = typename cplx_pair<R>::type;
+    constexpr int VEC = vec16<R>::lanes, EPT = VEC / CPX;
     const uint32_t b = v.xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
     const uint64_t gid = static_cast<uint64_t>(b) * kThreads + threadIdx.x;
     const uint64_t u = gid >> v.lc;
@@ -178,51 +153,11 @@ __global__ __launch_bounds__(kThreads) void sdsp_pfb_fold(pf_view v, const R *__
     }
 }
 
-// S >= hist: the new history is the block's last hist elements, newest first
-template <typename E>
-__global__ __launch_bounds__(kThreads) void sdsp_pfb_state_flat(const E *__restrict__ in, E *__restrict__ state, uint64_t in_stride,
-                                                                uint64_t samples, uint64_t channels, uint32_t hist)
-{
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
-    if (i >= channels * hist)
-        return;
-    const uint64_t c = i / hist, jj = i - c * hist;
-    state[i] = in[c * in_stride + (samples - 1 - jj)];
-}
-
-// S < hist: one workgroup per row, chunks from the high end down with a barrier between each chunk's reads and its writes
-template <typename E>
-__global__ __launch_bounds__(kThreads) void sdsp_pfb_state_shift(const E *__restrict__ in, E *state, uint64_t in_stride, uint32_t samples,
-                                                                 uint32_t hist)
-{
-    const uint64_t c = blockIdx.x;
-    E *row = state + c * hist;
-    const uint32_t chunks = (hist + kThreads - 1) / kThreads;
-    for (uint32_t q = chunks; q-- > 0;) {
-        const uint32_t jj = q * kThreads + threadIdx.x;
-        E val = E(0);
-        if (jj < hist)
-            val = jj < samples ? in[c * in_stride + (samples - 1 - jj)] : row[jj - samples];
-        __syncthreads();
-        if (jj < hist)
-            row[jj] = val;
-        __syncthreads();
-    }
-}
-
-uint32_t log2u(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 bool sliding(uint32_t m, uint32_t hop, int form) { return form == 0 && m % hop == 0; }
 
 template <typename R, int CPX> int launch_fold(const pfb_args &a, hipStream_t stream)
 {
-    constexpr int VEC = pf_vec<R>::lanes;
+    constexpr int VEC = vec16<R>::lanes;
     if (a.nc == 0 || a.nj == 0)
         return SDSP_HIP_OK;
     const bool slide = sliding(a.m, a.hop, a.form);
@@ -250,10 +185,11 @@ template <typename R, int CPX> int launch_fold(const pfb_args &a, hipStream_t st
     v.rotate = a.rotate ? 1 : 0;
     v.shift0 = a.shift0;
     v.xcd = slide ? 0 : 1;
-    const uint64_t threads = v.units << v.lc, blocks = (threads + kThreads - 1) / kThreads;
-    if ((v.units << v.lc) >> v.lc != v.units || blocks > 0x7fffffffull)
+    if ((v.units << v.lc) >> v.lc != v.units)
         return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb slice too large for one launch");
-    const dim3 grid(static_cast<uint32_t>(blocks));
+    dim3 grid;
+    if (int rc = grid_for(v.units << v.lc, "pfb slice", &grid))
+        return rc;
     const R *in = static_cast<const R *>(a.in), *st = static_cast<const R *>(a.state), *h = static_cast<const R *>(a.taps);
     R *dst = static_cast<R *>(a.dst);
     if (slide)
@@ -263,48 +199,18 @@ template <typename R, int CPX> int launch_fold(const pfb_args &a, hipStream_t st
     return SDSP_HIP_OK;
 }
 
-template <typename R> int launch_state(const pfb_args &a, hipStream_t stream)
+template <typename R> int launch(const pfb_args &a, hipStream_t stream)
 {
-    using E = typename pf_cplx<R>::type;
-    if (a.hist == 0 || !a.state_out || a.channels == 0)
-        return SDSP_HIP_OK;
-    const E *in = static_cast<const E *>(a.in);
-    E *state = static_cast<E *>(a.state_out);
-    if (a.samples >= a.hist) {
-        const uint64_t n = a.channels * a.hist, blocks = (n + kThreads - 1) / kThreads;
-        if (blocks > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb state too large for one launch");
-        hipLaunchKernelGGL(sdsp_pfb_state_flat<E>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, in, state, a.in_stride,
-                           a.samples, a.channels, a.hist);
-    } else {
-        if (a.channels > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb state too large for one launch");
-        hipLaunchKernelGGL(sdsp_pfb_state_shift<E>, dim3(static_cast<uint32_t>(a.channels)), dim3(kThreads), 0, stream, in, state,
-                           a.in_stride, static_cast<uint32_t>(a.samples), a.hist);
-    }
-    return SDSP_HIP_OK;
-}
-
-template <typename R> int launch(const pfb_args &a, int step, hipStream_t stream)
-{
-    int rc;
-    if (step == PFB_STATE)
-        rc = launch_state<R>(a, stream);
-    else
-        rc = a.complex_in ? launch_fold<R, 2>(a, stream) : launch_fold<R, 1>(a, stream);
-    if (rc)
+    if (int rc = a.complex_in ? launch_fold<R, 2>(a, stream) : launch_fold<R, 1>(a, stream))
         return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(SDSP_HIP_ERR_HIP, std::string("pfb launch: ") + hipGetErrorString(e));
-    return SDSP_HIP_OK;
+    return launch_status("pfb");
 }
 } // namespace
 
-int launch_pfb(int precision, const pfb_args &a, int step, void *stream)
+int launch_pfb(int precision, const pfb_args &a, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return precision == SDSP_HIP_F64 ? launch<double>(a, step, s) : launch<float>(a, step, s);
+    return precision == SDSP_HIP_F64 ? launch<double>(a, s) : launch<float>(a, s);
 }
 
 const char *pfb_form_for(uint32_t m, uint32_t hop) { return sliding(m, hop, 0) ? "sliding" : "plain"; }

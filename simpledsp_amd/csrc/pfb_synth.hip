@@ -1,12 +1,11 @@
 // pfb_synth.hip -- the unfold kernel of the polyphase synthesis filter banks (sdsp_hip_pfb_synth_*).
 //
-// One sdsp_hip_pfb_synth_process call runs as one seed launch, then slices of copy / pack -> reverse transform -> unfold launches over the
+// One sdsp_hip_pfb_synth_process call runs as the pending-sum seed (stream_carry.hip: carry_seed), then slices of copy / pack -> reverse transform -> unfold launches over the
 // plan's workspace.  The unit of work is one frame of M elements of one channel (an element is one real or one interleaved complex
 // sample); units are numbered channel-major (g = c F + j) and a slice is a contiguous range of them, unfolded as rectangles of
 // (channels, frames): a partial first channel, whole channels, a partial last channel.  Output position t of a channel lives in
 // out[c out_stride + t] for t < S = F D and in state[c hist + t - S] above (the new pending sums): the inverse STFT bank's place rule.
 //
-//   sdsp_pfb_synth_seed    istft.hip's sdsp_istft_seed for complex elements (real banks launch that one)
 //   sdsp_pfb_synth_copy    COMPLEX: the slice's spectra into the workspace rows, 16 bytes per lane where the input rows allow
 //   (the plan's reverse transform, 1 / M scaled, in place on the slice: unchanged kernels; v_j = row j afterwards)
 //   sdsp_pfb_synth_unfold  one owner per output position, no atomics.  The rectangle's frames of channel c are js .. je - 1 and cover
@@ -23,25 +22,15 @@
 //                       outputs, every accumulator receiving its frames in ascending j.  The J taps in use sit in a register ring
 //                       (tap p is loaded at step P - 1 - p and last used J - 1 steps later).
 //                     plain form (every other D): the owner of t loops over its ceil(L / D) covering frames; consecutive workgroups
-//                       are placed on one XCD (the STFT bank's placement), so the re-reads of the rows hit its L2.
+//                       are placed on one XCD (stream_dev.h: xcd_block), so the re-reads of the rows hit its L2.
 //                   Both forms perform the same additions in the same order: the same bits.
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
 namespace
 {
-constexpr int kThreads = 256;
 constexpr int kSlide = 8; // output hops per thread of the sliding form
-
-template <typename R, int N> struct ps_vec {
-    typedef R type __attribute__((ext_vector_type(N)));
-};
-template <typename R> struct ps_lanes; // reals per 16 B
-template <> struct ps_lanes<float> { static constexpr int value = 4; };
-template <> struct ps_lanes<double> { static constexpr int value = 2; };
 
 // one unfold launch: channels [c0, c0 + nc) x frames [j0, j0 + nj)
 struct ps_view {
@@ -56,35 +45,21 @@ struct ps_view {
     uint32_t rotate, shift0, has_state, place_vec_ok;
 };
 
-// workgroup b -> the position it works on: the blocks that share an XCD (b mod 8) get one contiguous range (the STFT bank's
-// placement).  A bijection on [0, nb) for every nb.
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb)
-{
-    const uint32_t q = nb / 8, r = nb % 8, x = b % 8;
-    return x * q + min(x, r) + b / 8;
-}
-
-// a / b with the 32-bit divide when both fit (the common case)
-__device__ __forceinline__ uint64_t udiv(uint64_t a, uint64_t b)
-{
-    return (a | b) < (1ull << 32) ? static_cast<uint64_t>(static_cast<uint32_t>(a) / static_cast<uint32_t>(b)) : a / b;
-}
-
 // N reals from / to an address aligned to N reals
 template <typename R, int N> __device__ __forceinline__ void ld(R *x, const R *p)
 {
-    const typename ps_vec<R, N>::type t = *reinterpret_cast<const typename ps_vec<R, N>::type *>(p);
+    const typename vec_n<R, N>::type t = *reinterpret_cast<const typename vec_n<R, N>::type *>(p);
 #pragma unroll
     for (int e = 0; e < N; e++)
         x[e] = t[e];
 }
 template <typename R, int N> __device__ __forceinline__ void st(R *p, const R *x)
 {
-    typename ps_vec<R, N>::type t;
+    typename vec_n<R, N>::type t;
 #pragma unroll
     for (int e = 0; e < N; e++)
         t[e] = x[e];
-    *reinterpret_cast<typename ps_vec<R, N>::type *>(p) = t;
+    *reinterpret_cast<typename vec_n<R, N>::type *>(p) = t;
 }
 
 // E elements of a workspace row from element index i (a multiple of E unless the TIME rotation says otherwise), wrapping at M
@@ -141,32 +116,6 @@ template <typename R, int CPX, int E> __device__ __forceinline__ void store_plac
 #pragma unroll
         for (int el = 0; el < E; el++)
             st<R, CPX>(place + el * CPX, x + el * CPX);
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void sdsp_pfb_synth_seed(T *__restrict__ out, T *state, uint64_t out_stride, uint64_t samples,
-                                                                uint32_t hist)
-{
-    const uint64_t c = blockIdx.x;
-    T *row = state + c * hist;
-    const uint32_t m = samples < hist ? static_cast<uint32_t>(samples) : hist;
-    for (uint32_t i = threadIdx.x; i < m; i += kThreads)
-        out[c * out_stride + i] = row[i];
-    if (samples >= hist)
-        return;
-    __syncthreads(); // every read of row[0 .. m) above happens before the shift writes there
-    const uint32_t s = static_cast<uint32_t>(samples), keep = hist - s;
-    const uint32_t chunks = (keep + kThreads - 1) / kThreads;
-    for (uint32_t q = 0; q < chunks; q++) { // low to high: a chunk reads only above every index written before it
-        const uint32_t i = q * kThreads + threadIdx.x;
-        T val = T(0);
-        if (i < keep)
-            val = row[i + s];
-        __syncthreads();
-        if (i < keep)
-            row[i] = val;
-        __syncthreads();
     }
 }
 
@@ -232,7 +181,7 @@ template <typename R, int CPX, int J>
 __global__ __launch_bounds__(kThreads) void sdsp_pfb_synth_unfold_slide(ps_view v, const R *__restrict__ ws, const R *__restrict__ taps,
                                                                         R *out, R *state)
 {
-    constexpr int E = ps_lanes<R>::value / CPX, N = E * CPX;
+    constexpr int E = vec16<R>::lanes / CPX, N = E * CPX;
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
     if (gid >= v.threads)
         return;
@@ -296,43 +245,24 @@ __global__ __launch_bounds__(kThreads) void sdsp_pfb_synth_unfold_slide(ps_view 
     }
 }
 
-uint32_t log2u(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 bool sliding(uint32_t m, uint32_t hop, int form) { return form == 0 && hop == m; }
-
-template <typename T> int launch_seed(const pfb_synth_args &a, hipStream_t stream)
-{
-    if (a.hist == 0 || !a.state || a.channels == 0)
-        return SDSP_HIP_OK;
-    if (a.channels > 0x7fffffffull)
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb synthesis state too large for one launch");
-    hipLaunchKernelGGL(sdsp_pfb_synth_seed<T>, dim3(static_cast<uint32_t>(a.channels)), dim3(kThreads), 0, stream, static_cast<T *>(a.out),
-                       static_cast<T *>(a.state), a.out_stride, static_cast<uint64_t>(a.frames) * a.hop, a.hist);
-    return SDSP_HIP_OK;
-}
 
 template <typename T> int launch_copy(const pfb_synth_args &a, uint64_t bin_bytes, hipStream_t stream)
 {
     const uint64_t per = sizeof(T) / bin_bytes; // bins per T
-    const uint64_t row = a.m / per, total = a.units * row, blocks = (total + kThreads - 1) / kThreads;
-    if (blocks > 0x7fffffffull)
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb synthesis slice too large for one launch");
-    if (blocks)
-        hipLaunchKernelGGL(sdsp_pfb_synth_copy<T>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream,
-                           static_cast<const T *>(a.in), static_cast<T *>(a.ws), a.in_stride / per, row, static_cast<uint64_t>(a.frames),
-                           a.g0, total);
+    const uint64_t row = a.m / per, total = a.units * row;
+    dim3 grid;
+    if (int rc = grid_for(total, "pfb synthesis slice", &grid))
+        return rc;
+    if (total)
+        hipLaunchKernelGGL(sdsp_pfb_synth_copy<T>, grid, dim3(kThreads), 0, stream, static_cast<const T *>(a.in), static_cast<T *>(a.ws),
+                           a.in_stride / per, row, static_cast<uint64_t>(a.frames), a.g0, total);
     return SDSP_HIP_OK;
 }
 
 template <typename R, int CPX> int launch_unfold(const pfb_synth_args &a, hipStream_t stream)
 {
-    constexpr int EPT = ps_lanes<R>::value / CPX;
+    constexpr int EPT = vec16<R>::lanes / CPX;
     if (a.nc == 0 || a.nj == 0)
         return SDSP_HIP_OK;
     const uint64_t es = sizeof(R) * CPX;
@@ -360,6 +290,7 @@ template <typename R, int CPX> int launch_unfold(const pfb_synth_args &a, hipStr
     const R *ws = static_cast<const R *>(a.ws), *g = static_cast<const R *>(a.taps);
     R *out = static_cast<R *>(a.out), *state = static_cast<R *>(a.state);
     const bool slide = sliding(a.m, a.hop, a.form);
+    const bool wide = !slide && EPT > 1 && a.hop % EPT == 0 && v.place_vec_ok;
     if (slide) {
         const uint32_t nout = a.nj + a.p - 1;
         v.kc = (nout + kSlide - 1) / kSlide;
@@ -368,36 +299,28 @@ template <typename R, int CPX> int launch_unfold(const pfb_synth_args &a, hipStr
         if (v.threads >> v.lc != a.nc * v.kc)
             return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb synthesis slice too large for one launch");
     } else {
-        const bool wide = EPT > 1 && a.hop % EPT == 0 && v.place_vec_ok;
         if (a.nc > ~0ull / v.len)
             return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb synthesis slice too large for one launch");
         v.threads = a.nc * v.len / (wide ? EPT : 1);
-        const uint64_t blocks = (v.threads + kThreads - 1) / kThreads;
-        if (blocks > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb synthesis slice too large for one launch");
-        const dim3 grid(static_cast<uint32_t>(blocks));
-        if (wide)
-            hipLaunchKernelGGL((sdsp_pfb_synth_unfold<R, CPX, EPT>), grid, dim3(kThreads), 0, stream, v, ws, g, out, state);
-        else
-            hipLaunchKernelGGL((sdsp_pfb_synth_unfold<R, CPX, 1>), grid, dim3(kThreads), 0, stream, v, ws, g, out, state);
-        return SDSP_HIP_OK;
     }
-    const uint64_t blocks = (v.threads + kThreads - 1) / kThreads;
-    if (blocks > 0x7fffffffull)
-        return fail(SDSP_HIP_ERR_UNSUPPORTED, "pfb synthesis slice too large for one launch");
-    hipLaunchKernelGGL((sdsp_pfb_synth_unfold_slide<R, CPX, kSlide>), dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, v,
-                       ws, g, out, state);
+    dim3 grid;
+    if (int rc = grid_for(v.threads, "pfb synthesis slice", &grid))
+        return rc;
+    if (slide)
+        hipLaunchKernelGGL((sdsp_pfb_synth_unfold_slide<R, CPX, kSlide>), grid, dim3(kThreads), 0, stream, v, ws, g, out, state);
+    else if (wide)
+        hipLaunchKernelGGL((sdsp_pfb_synth_unfold<R, CPX, EPT>), grid, dim3(kThreads), 0, stream, v, ws, g, out, state);
+    else
+        hipLaunchKernelGGL((sdsp_pfb_synth_unfold<R, CPX, 1>), grid, dim3(kThreads), 0, stream, v, ws, g, out, state);
     return SDSP_HIP_OK;
 }
 
 template <typename R> int launch(const pfb_synth_args &a, int step, hipStream_t stream)
 {
-    typedef typename ps_vec<R, 2>::type C2;
-    typedef typename ps_vec<R, ps_lanes<R>::value>::type V16;
+    typedef typename cplx_pair<R>::type C2;
+    typedef typename vec16<R>::type V16;
     int rc;
-    if (step == PFB_SYNTH_SEED) {
-        rc = launch_seed<C2>(a, stream);
-    } else if (step == PFB_SYNTH_COPY) {
+    if (step == PFB_SYNTH_COPY) {
         const bool wide = reinterpret_cast<uintptr_t>(a.in) % 16 == 0 && (a.in_stride * sizeof(C2)) % 16 == 0;
         rc = wide ? launch_copy<V16>(a, sizeof(C2), stream) : launch_copy<C2>(a, sizeof(C2), stream);
     } else {
@@ -405,10 +328,7 @@ template <typename R> int launch(const pfb_synth_args &a, int step, hipStream_t 
     }
     if (rc)
         return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(SDSP_HIP_ERR_HIP, std::string("pfb synthesis launch: ") + hipGetErrorString(e));
-    return SDSP_HIP_OK;
+    return launch_status("pfb synthesis");
 }
 } // namespace
 

@@ -266,30 +266,39 @@ struct resample_args {
 int launch_resample(int precision, const resample_args &a, int variant, void *stream);
 // the kernel launch_resample runs for this shape and variant (the same selection function)
 const char *resample_kernel_for(int precision, const resample_args &a, int variant);
-// STFT banks (stft.hip): the launches of one slice around the plan's real-input transform, and the state launch
-enum { STFT_FRAME = 0, STFT_EMIT = 1, STFT_STATE = 2 };
+// carried state of the streaming banks (stream_carry.hip).  elem_bytes: one real or one interleaved complex
+// value of `precision`; `family` labels the error messages ("<family> state too large for one launch", "<family> launch: ...").
+// Both return at once for hist = 0, a null state or no channels.
+// after a call's last frame launch: state (channels x hist, newest first) = the last hist elements of old history + in[.., :samples]
+int carry_history(int precision, uint32_t elem_bytes, const void *in, uint64_t in_stride, void *state, uint64_t channels,
+                  uint64_t samples, uint32_t hist, void *stream, const char *family);
+// before a call's first slice: the pending sums (channels x hist, time order) of the call's first min(hist, samples) positions go to
+// out, the rest move to the front of their row
+int carry_seed(int precision, uint32_t elem_bytes, void *out, uint64_t out_stride, void *state, uint64_t channels, uint64_t samples,
+               uint32_t hist, void *stream, const char *family);
+// STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
+enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
     const void *in;
     void *out;
-    void *state;        // nullable; channels x hist, newest first
+    const void *state;  // nullable; channels x hist, newest first
     const void *window; // device, plan precision, n values
     void *ws;           // units x n reals (windowed frames, then their packed half spectra)
-    uint64_t in_stride, out_stride, channels, samples;
+    uint64_t in_stride, out_stride;
     uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, frame) numbering
     uint32_t units, frames, n, hop, hist;
     int output;         // SDSP_HIP_STFT_*
 };
 int launch_stft(int precision, const stft_args &a, int step, void *stream);
-// inverse STFT banks (istft.hip): the launch that consumes the old pending sums, and the launches of one
-// slice around the plan's reverse real-input transform
-enum { ISTFT_SEED = 0, ISTFT_PACK = 1, ISTFT_OLA = 2 };
+// inverse STFT banks (istft.hip): the launches of one slice around the plan's reverse real-input transform
+enum { ISTFT_PACK = 0, ISTFT_OLA = 1 };
 struct istft_args {
     const void *in;     // complex bins, plan precision
     void *out;
     void *state;        // nullable; channels x hist, time order
     const void *g;      // device, plan precision, n values: the synthesis window
     void *ws;           // units x n reals (packed half spectra, then their frames)
-    uint64_t in_stride, out_stride, channels;
+    uint64_t in_stride, out_stride;
     uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, frame) numbering
     uint32_t units, frames, n, hop, hist;
 };
@@ -316,39 +325,36 @@ struct welch_args {
 };
 int launch_welch(int precision, const welch_args &a, int step, void *stream);
 // polyphase filter-bank channelizers (pfb.hip): the fold launch of one rectangle of (channel, frame) units in
-// front of the plan's transform, and the state launch for complex elements (real banks use the STFT bank's, STFT_STATE)
-enum { PFB_FOLD = 0, PFB_STATE = 1 };
+// front of the plan's transform
 struct pfb_args {
     const void *in;
     const void *state;  // nullable; channels x hist elements, newest first
     const void *taps;   // device, plan precision, p x m reals
-    void *dst;          // fold: frame j of channel c at dst + (c dst_cstride + j m - dst_sub) elements
-    void *state_out;    // state launch
-    uint64_t in_stride, channels, samples; // state launch: the whole call
+    void *dst;          // frame j of channel c at dst + (c dst_cstride + j m - dst_sub) elements
+    uint64_t in_stride;
     uint64_t dst_cstride, dst_sub;
-    uint64_t c0, nc;    // fold: channels [c0, c0 + nc)
-    uint32_t j0, nj;    // fold: frames [j0, j0 + nj) of each
+    uint64_t c0, nc;    // channels [c0, c0 + nc)
+    uint32_t j0, nj;    // frames [j0, j0 + nj) of each
     uint32_t m, p, hop, hist;
     uint32_t shift0;    // TIME: frame j is rotated by (shift0 + j hop) mod m; FRAME: rotate = 0
     int complex_in, rotate;
     int form;           // 0: chosen from hop and m; 1: the plain per-frame form (measurement and cross-checks)
 };
-int launch_pfb(int precision, const pfb_args &a, int step, void *stream);
+int launch_pfb(int precision, const pfb_args &a, void *stream);
 // the fold form a plan of these sizes runs: "sliding" where hop divides m, else "plain"
 const char *pfb_form_for(uint32_t m, uint32_t hop);
 // host_math.cpp: symmetric-window sinc low-pass of `taps` points with cutoff `cutoff` (fraction of Nyquist) and unit DC gain
 int windowed_sinc_lowpass(uint64_t taps, double cutoff, int window_kind, double *h);
-// polyphase synthesis banks (pfb_synth.hip): the seed launch for complex elements (real banks use the inverse
-// STFT bank's, ISTFT_SEED), the copy of one slice's complex spectra into the workspace (real banks pack with ISTFT_PACK), and the
-// unfold launch of one rectangle of (stream, frame) units behind the plan's reverse transform
-enum { PFB_SYNTH_SEED = 0, PFB_SYNTH_COPY = 1, PFB_SYNTH_UNFOLD = 2 };
+// polyphase synthesis banks (pfb_synth.hip): the copy of one slice's complex spectra into the workspace (real
+// banks pack with ISTFT_PACK), and the unfold launch of one rectangle of (stream, frame) units behind the plan's reverse transform
+enum { PFB_SYNTH_COPY = 0, PFB_SYNTH_UNFOLD = 1 };
 struct pfb_synth_args {
     const void *in;     // complex bins, plan precision
     void *out;
     void *state;        // nullable; channels x hist elements of the output kind, time order
     const void *taps;   // device, plan precision, p x m reals
     void *ws;           // the slice's rows of m elements: spectra in, v_j after the transform
-    uint64_t in_stride, out_stride, channels;
+    uint64_t in_stride, out_stride;
     uint64_t g0;        // the slice: units [g0, g0 + units) of the channel-major (channel, frame) numbering
     uint64_t units;
     uint64_t c0, nc;    // unfold: the rectangle's channels ...

@@ -1,44 +1,22 @@
 // stft.hip -- the streaming layer of the STFT bank (sdsp_hip_stft_*).
 //
-// One sdsp_hip_stft_process call runs as slices of frame -> transform -> emit launches over the plan's workspace, then one state
-// launch.  The unit of work is one frame of N reals of one channel; units are numbered channel-major (g = c F + j, F frames per
+// One sdsp_hip_stft_process call runs as slices of frame -> transform -> emit launches over the plan's workspace, then the history
+// update (stream_carry.hip: carry_history).  The unit of work is one frame of N reals of one channel; units are numbered channel-major (g = c F + j, F frames per
 // channel) and a slice is a contiguous range of them, so a slice may start or end inside a channel.
 //
 //   sdsp_stft_frame  x[j hop + i] * w[i] for the slice's frames into the workspace (N reals per unit, 16 B per lane); x is the
 //                    channel's history followed by the block: x[p] = state[c hist + hist - 1 - p] for p < hist, else
 //                    in[c in_stride + p - hist].  Overlapping frames read the same input: consecutive workgroups of a slice are
-//                    placed on one XCD (the dispatcher deals workgroups round-robin over the eight), so those re-reads hit its L2.
+//                    placed on one XCD (stream_dev.h: xcd_block), so those re-reads hit its L2.
 //   (the plan's forward real-input transform of n_real = N, radix 2, in place on the slice: unchanged kernels)
 //   sdsp_stft_emit   the packed half spectrum (Z[0] = (X[0], X[N/2]), Z[k] = X[k]) -> N/2 + 1 output bins per frame: complex,
 //                    re re + im im (no contraction: this file is compiled with -ffp-contract=off) or its square root
-//   sdsp_stft_state  after the last slice: state[c hist + j] = x[hist + S - 1 - j].  For S >= hist every value comes from `in`
-//                    (sdsp_stft_state_flat).  For S < hist the row is the block reversed followed by the old state[0 .. hist - S):
-//                    an in-place shift toward higher indices, done by one workgroup per row walking chunks from the high end down
-//                    with a barrier between each chunk's reads and its writes (sdsp_stft_state_shift).
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
 namespace
 {
-constexpr int kThreads = 256;
-
-template <typename R> struct st_vec;
-template <> struct st_vec<float> {
-    typedef float type __attribute__((ext_vector_type(4)));
-    static constexpr int lanes = 4;
-};
-template <> struct st_vec<double> {
-    typedef double type __attribute__((ext_vector_type(2)));
-    static constexpr int lanes = 2;
-};
-
-template <typename R> struct st_cplx;
-template <> struct st_cplx<float> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct st_cplx<double> { typedef double type __attribute__((ext_vector_type(2))); };
-
 // one slice's view of the call; the slice's first unit is frame j0 of channel c0
 struct st_view {
     uint64_t in_stride, out_stride;
@@ -49,14 +27,6 @@ struct st_view {
     uint32_t lc;         // log2(threads per unit)
     uint32_t vec_ok;     // `in` and in_stride keep 16-B alignment of element offsets that are multiples of the vector width
 };
-
-// workgroup b -> the slice position it works on: the blocks that share an XCD (b mod 8) get one contiguous range, so that the
-// frames that overlap one another are read by workgroups behind the same L2.  A bijection on [0, nb) for every nb.
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb)
-{
-    const uint32_t q = nb / 8, r = nb % 8, x = b % 8;
-    return x * q + min(x, r) + b / 8;
-}
 
 // unit u of the slice -> (channel, frame)
 __device__ __forceinline__ void unit_pos(const st_view &v, uint32_t u, uint64_t &c, uint32_t &j)
@@ -79,8 +49,8 @@ template <typename R>
 __global__ __launch_bounds__(kThreads) void sdsp_stft_frame(st_view v, const R *__restrict__ in, const R *__restrict__ state,
                                                             const R *__restrict__ window, R *__restrict__ ws)
 {
-    using V = typename st_vec<R>::type;
-    constexpr int VEC = st_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     const uint64_t gid = static_cast<uint64_t>(xcd_block(blockIdx.x, gridDim.x)) * kThreads + threadIdx.x;
     const uint64_t u = gid >> v.lc;
     if (u >= v.units)
@@ -110,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void sdsp_stft_frame(st_view v, const R *
 template <typename R, int KIND>
 __global__ __launch_bounds__(kThreads) void sdsp_stft_emit(st_view v, const R *__restrict__ ws, R *__restrict__ out)
 {
-    using C2 = typename st_cplx<R>::type;
+    using C2 = typename cplx_pair<R>::type;
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
     const uint64_t u = gid >> v.lc;
     if (u >= v.units)
@@ -140,104 +110,41 @@ __global__ __launch_bounds__(kThreads) void sdsp_stft_emit(st_view v, const R *_
     }
 }
 
-// S >= hist: the new history is the block's last hist samples, newest first
-template <typename R>
-__global__ __launch_bounds__(kThreads) void sdsp_stft_state_flat(const R *__restrict__ in, R *__restrict__ state, uint64_t in_stride,
-                                                                 uint64_t samples, uint64_t channels, uint32_t hist)
-{
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
-    if (i >= channels * hist)
-        return;
-    const uint64_t c = i / hist, jj = i - c * hist;
-    state[i] = in[c * in_stride + (samples - 1 - jj)];
-}
-
-// S < hist: one workgroup per row; chunk [lo, lo + kThreads) reads old state[j - S] (j >= S) or the block, waits for every lane's
-// read, then writes.  Chunks go from the high end down, so every old value a chunk reads lies below the chunks written before it.
-template <typename R>
-__global__ __launch_bounds__(kThreads) void sdsp_stft_state_shift(const R *__restrict__ in, R *state, uint64_t in_stride,
-                                                                  uint32_t samples, uint32_t hist)
-{
-    const uint64_t c = blockIdx.x;
-    R *row = state + c * hist;
-    const uint32_t chunks = (hist + kThreads - 1) / kThreads;
-    for (uint32_t q = chunks; q-- > 0;) {
-        const uint32_t jj = q * kThreads + threadIdx.x;
-        R val = R(0);
-        if (jj < hist)
-            val = jj < samples ? in[c * in_stride + (samples - 1 - jj)] : row[jj - samples];
-        __syncthreads();
-        if (jj < hist)
-            row[jj] = val;
-        __syncthreads();
-    }
-}
-
-uint32_t log2u(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 template <typename R> int launch(const stft_args &a, int step, hipStream_t stream)
 {
-    constexpr int VEC = st_vec<R>::lanes;
-    const R *in = static_cast<const R *>(a.in);
-    if (step == STFT_STATE) {
-        if (a.hist == 0 || !a.state || a.channels == 0)
-            return SDSP_HIP_OK;
-        if (a.samples >= a.hist) {
-            const uint64_t n = a.channels * a.hist, blocks = (n + kThreads - 1) / kThreads;
-            if (blocks > 0x7fffffffull)
-                return fail(SDSP_HIP_ERR_UNSUPPORTED, "stft state too large for one launch");
-            hipLaunchKernelGGL(sdsp_stft_state_flat<R>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, in,
-                               static_cast<R *>(a.state), a.in_stride, a.samples, a.channels, a.hist);
-        } else {
-            if (a.channels > 0x7fffffffull)
-                return fail(SDSP_HIP_ERR_UNSUPPORTED, "stft state too large for one launch");
-            hipLaunchKernelGGL(sdsp_stft_state_shift<R>, dim3(static_cast<uint32_t>(a.channels)), dim3(kThreads), 0, stream, in,
-                               static_cast<R *>(a.state), a.in_stride, static_cast<uint32_t>(a.samples), a.hist);
-        }
+    constexpr int VEC = vec16<R>::lanes;
+    if (static_cast<uint64_t>(a.frames) + a.units >= (1ull << 32))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "stft slice: too many frames per channel");
+    st_view v{};
+    v.in_stride = a.in_stride;
+    v.out_stride = a.out_stride;
+    v.c0 = a.g0 / a.frames;
+    v.j0 = static_cast<uint32_t>(a.g0 - v.c0 * a.frames);
+    v.frames = a.frames;
+    v.units = a.units;
+    v.n = a.n;
+    v.hop = a.hop;
+    v.hist = a.hist;
+    v.bins = a.n / 2 + 1;
+    v.vec_ok = (reinterpret_cast<uintptr_t>(a.in) % 16 == 0 && (a.in_stride * sizeof(R)) % 16 == 0) ? 1 : 0;
+    v.lc = log2u(step == STFT_FRAME ? a.n / VEC : a.n / 2);
+    dim3 grid;
+    if (int rc = grid_for(static_cast<uint64_t>(a.units) << v.lc, "stft slice", &grid))
+        return rc;
+    R *ws = static_cast<R *>(a.ws);
+    if (step == STFT_FRAME) {
+        hipLaunchKernelGGL(sdsp_stft_frame<R>, grid, dim3(kThreads), 0, stream, v, static_cast<const R *>(a.in),
+                           static_cast<const R *>(a.state), static_cast<const R *>(a.window), ws);
     } else {
-        if (static_cast<uint64_t>(a.frames) + a.units >= (1ull << 32))
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "stft slice: too many frames per channel");
-        st_view v{};
-        v.in_stride = a.in_stride;
-        v.out_stride = a.out_stride;
-        v.c0 = a.g0 / a.frames;
-        v.j0 = static_cast<uint32_t>(a.g0 - v.c0 * a.frames);
-        v.frames = a.frames;
-        v.units = a.units;
-        v.n = a.n;
-        v.hop = a.hop;
-        v.hist = a.hist;
-        v.bins = a.n / 2 + 1;
-        v.vec_ok = (reinterpret_cast<uintptr_t>(a.in) % 16 == 0 && (a.in_stride * sizeof(R)) % 16 == 0) ? 1 : 0;
-        v.lc = log2u(step == STFT_FRAME ? a.n / VEC : a.n / 2);
-        const uint64_t threads = static_cast<uint64_t>(a.units) << v.lc, blocks = (threads + kThreads - 1) / kThreads;
-        if (blocks > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "stft slice too large for one launch");
-        const dim3 grid(static_cast<uint32_t>(blocks));
-        R *ws = static_cast<R *>(a.ws);
-        if (step == STFT_FRAME) {
-            hipLaunchKernelGGL(sdsp_stft_frame<R>, grid, dim3(kThreads), 0, stream, v, in, static_cast<const R *>(a.state),
-                               static_cast<const R *>(a.window), ws);
-        } else {
-            R *out = static_cast<R *>(a.out);
-            if (a.output == SDSP_HIP_STFT_COMPLEX)
-                hipLaunchKernelGGL((sdsp_stft_emit<R, SDSP_HIP_STFT_COMPLEX>), grid, dim3(kThreads), 0, stream, v, ws, out);
-            else if (a.output == SDSP_HIP_STFT_POWER)
-                hipLaunchKernelGGL((sdsp_stft_emit<R, SDSP_HIP_STFT_POWER>), grid, dim3(kThreads), 0, stream, v, ws, out);
-            else
-                hipLaunchKernelGGL((sdsp_stft_emit<R, SDSP_HIP_STFT_MAGNITUDE>), grid, dim3(kThreads), 0, stream, v, ws, out);
-        }
+        R *out = static_cast<R *>(a.out);
+        if (a.output == SDSP_HIP_STFT_COMPLEX)
+            hipLaunchKernelGGL((sdsp_stft_emit<R, SDSP_HIP_STFT_COMPLEX>), grid, dim3(kThreads), 0, stream, v, ws, out);
+        else if (a.output == SDSP_HIP_STFT_POWER)
+            hipLaunchKernelGGL((sdsp_stft_emit<R, SDSP_HIP_STFT_POWER>), grid, dim3(kThreads), 0, stream, v, ws, out);
+        else
+            hipLaunchKernelGGL((sdsp_stft_emit<R, SDSP_HIP_STFT_MAGNITUDE>), grid, dim3(kThreads), 0, stream, v, ws, out);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(SDSP_HIP_ERR_HIP, std::string("stft launch: ") + hipGetErrorString(e));
-    return SDSP_HIP_OK;
+    return launch_status("stft");
 }
 } // namespace
 

@@ -1,7 +1,7 @@
 // welch.hip -- the kernels of the Welch PSD bank (sdsp_hip_welch_*).
 //
 // One sdsp_hip_welch_process call runs as slices of frame -> transform -> run -> combine launches over the plan's workspace, then
-// the STFT bank's state launch (stft.hip, hist = N - 1).  The unit of work is one segment of N reals of one channel; units are
+// the history update (stream_carry.hip: carry_history, hist = N - 1).  The unit of work is one segment of N reals of one channel; units are
 // numbered channel-major (g = c F + j, F segments per channel in the call) and a slice is a contiguous range of them.
 //
 //   sdsp_welch_frame    detrended, windowed segment j of channel c into the workspace (N reals per unit).  x is the channel's
@@ -12,7 +12,8 @@
 //                       double in (q, lane) order, the lanes of a unit add theirs in an xor butterfly (masks 1, 2, 4 .. 32), and
 //                       units wider than a wave add the waves' sums in ascending order through LDS; then the subtract-and-window
 //                       pass runs from registers (nq <= 8, template K = nq) or re-reads the segment, which the first pass left in
-//                       the caches (K = 0).  Workgroups are ordered so that neighbouring units, which overlap, share an XCD.
+//                       the caches (K = 0).  Workgroups are ordered so that neighbouring units, which overlap, share an XCD
+//                       (stream_dev.h: xcd_block).
 //   (the plan's forward real-input transform of n_real = N, radix 2, in place on the slice: unchanged kernels)
 //   sdsp_welch_run      one thread per (run, packed bin k < N/2): a run is up to R consecutive segments of one channel in the slice;
 //                       it sums p = re re + im im in double in ascending segment order (k = 0: re^2 for bin 0 and im^2 for N/2)
@@ -21,30 +22,13 @@
 //                       then one addition into acc.  No atomics: every acc element has one owner per slice.
 //   sdsp_welch_finalize out = round_p(acc c_k), elementwise.
 // This file is compiled with -ffp-contract=off: every product and sum above is rounded on its own.
-#include "sdsp_hip_internal.h"
-
-#include <hip/hip_runtime.h>
+#include "stream_dev.h"
 
 namespace sdsp_hip
 {
 namespace
 {
-constexpr int kThreads = 256;
 constexpr int kBatch = 8; // run and combine stages: loads in flight per thread
-
-template <typename R> struct wl_vec;
-template <> struct wl_vec<float> {
-    typedef float type __attribute__((ext_vector_type(4)));
-    static constexpr int lanes = 4;
-};
-template <> struct wl_vec<double> {
-    typedef double type __attribute__((ext_vector_type(2)));
-    static constexpr int lanes = 2;
-};
-
-template <typename R> struct wl_cplx;
-template <> struct wl_cplx<float> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct wl_cplx<double> { typedef double type __attribute__((ext_vector_type(2))); };
 
 // one slice's view of the call; the slice's first unit is segment j0 of channel c0
 struct wl_view {
@@ -65,14 +49,6 @@ struct wl_runs {
     uint32_t frames, j0, first_end, jend, run, rpc, runs_first, runs_last, last_cc, bins, half, lk;
 };
 
-// workgroup b -> the slice position it works on: the blocks that share an XCD (b mod 8) get one contiguous range.  A bijection on
-// [0, nb) for every nb (the STFT bank's placement).
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb)
-{
-    const uint32_t q = nb / 8, r = nb % 8, x = b % 8;
-    return x * q + min(x, r) + b / 8;
-}
-
 template <typename R>
 __device__ __forceinline__ R load_x(const wl_view &v, const R *in, const R *state, uint64_t c, uint64_t p)
 {
@@ -82,10 +58,10 @@ __device__ __forceinline__ R load_x(const wl_view &v, const R *in, const R *stat
 }
 
 template <typename R>
-__device__ __forceinline__ typename wl_vec<R>::type load_vec(const wl_view &v, const R *in, const R *state, uint64_t c, uint64_t p0)
+__device__ __forceinline__ typename vec16<R>::type load_vec(const wl_view &v, const R *in, const R *state, uint64_t c, uint64_t p0)
 {
-    using V = typename wl_vec<R>::type;
-    constexpr int VEC = wl_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     V x;
     const uint64_t off = c * v.in_stride + (p0 - v.hist);
     if (v.vec_ok && p0 >= v.hist && off % VEC == 0) {
@@ -102,8 +78,8 @@ template <typename R, int DT, int K>
 __global__ __launch_bounds__(kThreads) void sdsp_welch_frame(wl_view v, const R *__restrict__ in, const R *__restrict__ state,
                                                              const R *__restrict__ window, R *__restrict__ ws)
 {
-    using V = typename wl_vec<R>::type;
-    constexpr int VEC = wl_vec<R>::lanes;
+    using V = typename vec16<R>::type;
+    constexpr int VEC = vec16<R>::lanes;
     const uint32_t tpu = 1u << v.lc;
     const uint64_t u = (static_cast<uint64_t>(xcd_block(blockIdx.x, gridDim.x)) << (8 - v.lc)) + (threadIdx.x >> v.lc);
     const uint32_t t = threadIdx.x & (tpu - 1);
@@ -215,7 +191,7 @@ __global__ __launch_bounds__(kThreads) void sdsp_welch_frame(wl_view v, const R 
 template <typename R>
 __global__ __launch_bounds__(kThreads) void sdsp_welch_run(wl_runs r, const R *__restrict__ ws, double *__restrict__ part)
 {
-    using C2 = typename wl_cplx<R>::type;
+    using C2 = typename cplx_pair<R>::type;
     const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
     const uint64_t rid = gid >> r.lk;
     if (rid >= r.runs)
@@ -319,14 +295,6 @@ __global__ __launch_bounds__(kThreads) void sdsp_welch_finalize(const double *__
     out[c * out_stride + k] = static_cast<R>(acc[c * acc_stride + k] * ck);
 }
 
-uint32_t log2u(uint64_t v)
-{
-    uint32_t l = 0;
-    while ((1ull << l) < v)
-        l++;
-    return l;
-}
-
 uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 template <typename R, int DT> void frame_launch(int K, dim3 grid, const wl_view &v, const R *in, const R *st, const R *w, R *ws,
@@ -364,13 +332,13 @@ wl_runs slice_runs(const welch_args &a)
 
 template <typename R> int launch(const welch_args &a, int step, hipStream_t stream)
 {
-    constexpr int VEC = wl_vec<R>::lanes;
+    constexpr int VEC = vec16<R>::lanes;
+    dim3 grid;
     if (step == WELCH_FINALIZE) {
-        const uint64_t n = a.channels * (a.n / 2 + 1), blocks = ceil_div(n, kThreads);
-        if (blocks > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "welch finalize too large for one launch");
-        hipLaunchKernelGGL(sdsp_welch_finalize<R>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, a.acc,
-                           static_cast<R *>(a.out), a.acc_stride, a.out_stride, a.channels, a.n / 2 + 1, a.c_edge, a.c_mid);
+        if (int rc = grid_for(a.channels * (a.n / 2 + 1), "welch finalize", &grid))
+            return rc;
+        hipLaunchKernelGGL(sdsp_welch_finalize<R>, grid, dim3(kThreads), 0, stream, a.acc, static_cast<R *>(a.out), a.acc_stride,
+                           a.out_stride, a.channels, a.n / 2 + 1, a.c_edge, a.c_mid);
     } else if (step == WELCH_FRAME) {
         if (static_cast<uint64_t>(a.frames) + a.units >= (1ull << 32))
             return fail(SDSP_HIP_ERR_UNSUPPORTED, "welch slice: too many segments per channel");
@@ -389,10 +357,8 @@ template <typename R> int launch(const welch_args &a, int step, hipStream_t stre
         v.denom = static_cast<double>(a.n) * (static_cast<double>(a.n) * a.n - 1.0) / 12.0; // exact: N (N^2 - 1) is a multiple of 12
         const uint32_t nq = a.n / (VEC << v.lc);
         const int K = nq <= 8 ? static_cast<int>(nq) : 0;
-        const uint64_t blocks = ceil_div(a.units, kThreads >> v.lc);
-        if (blocks > 0x7fffffffull)
-            return fail(SDSP_HIP_ERR_UNSUPPORTED, "welch slice too large for one launch");
-        const dim3 grid(static_cast<uint32_t>(blocks));
+        if (int rc = grid_of_blocks(ceil_div(a.units, kThreads >> v.lc), "welch slice", &grid))
+            return rc;
         const R *in = static_cast<const R *>(a.in), *st = static_cast<const R *>(a.state), *w = static_cast<const R *>(a.window);
         R *ws = static_cast<R *>(a.ws);
         if (a.detrend == SDSP_HIP_DETREND_NONE) // one pass: nothing to keep in registers
@@ -404,23 +370,18 @@ template <typename R> int launch(const welch_args &a, int step, hipStream_t stre
     } else {
         const wl_runs r = slice_runs(a);
         if (step == WELCH_RUN) {
-            const uint64_t blocks = ceil_div(r.runs << r.lk, kThreads);
-            if (blocks > 0x7fffffffull)
-                return fail(SDSP_HIP_ERR_UNSUPPORTED, "welch slice too large for one launch");
-            hipLaunchKernelGGL(sdsp_welch_run<R>, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, r,
-                               static_cast<const R *>(a.ws), a.part);
+            if (int rc = grid_for(r.runs << r.lk, "welch slice", &grid))
+                return rc;
+            hipLaunchKernelGGL(sdsp_welch_run<R>, grid, dim3(kThreads), 0, stream, r, static_cast<const R *>(a.ws), a.part);
         } else {
-            const uint64_t nch = r.last_cc + 1ull, blocks = ceil_div(nch * r.bins, kThreads);
-            if (blocks > 0x7fffffffull)
-                return fail(SDSP_HIP_ERR_UNSUPPORTED, "welch slice too large for one launch");
-            hipLaunchKernelGGL(sdsp_welch_combine, dim3(static_cast<uint32_t>(blocks)), dim3(kThreads), 0, stream, r, nch,
-                               a.g0 / a.frames, static_cast<const double *>(a.part), a.acc, a.acc_stride);
+            const uint64_t nch = r.last_cc + 1ull;
+            if (int rc = grid_for(nch * r.bins, "welch slice", &grid))
+                return rc;
+            hipLaunchKernelGGL(sdsp_welch_combine, grid, dim3(kThreads), 0, stream, r, nch, a.g0 / a.frames,
+                               static_cast<const double *>(a.part), a.acc, a.acc_stride);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return fail(SDSP_HIP_ERR_HIP, std::string("welch launch: ") + hipGetErrorString(e));
-    return SDSP_HIP_OK;
+    return launch_status("welch");
 }
 } // namespace
 
