@@ -746,6 +746,94 @@ typedef struct {
 } sdsp_hip_welch_plan_info;
 int sdsp_hip_welch_plan_get_info(const sdsp_hip_welch_plan *plan, sdsp_hip_welch_plan_info *info);
 
+/* ------------------------------------------------------------------ cross-spectral density and coherence banks */
+
+/*
+ * Welch cross-spectral density and magnitude-squared coherence of pairs of `channels` real streams, accumulated across calls
+ * (DESIGN.md section 5.18): scipy.signal.csd(x_a, x_b, fs, window, nperseg = N, noverlap = N - hop, detrend, scaling) and
+ * scipy.signal.coherence(x_a, x_b, ...) for a list of `npairs` channel pairs (a_i, b_i) fixed at plan creation.  a_i == b_i is
+ * allowed and a pair may appear more than once.  N, hop, bins = N / 2 + 1 and hist = N - 1 are the Welch bank's, and so are
+ *   - the segments and `position` (sdsp_hip_welch_frames counts the segments of a call), the history (state[c hist + j] =
+ *     x_c[position - 1 - j], plan precision, NULL only at position 0), the detrended, windowed segment value round_p(d_n w_n) with its
+ *     sum order, and the transform (the library's forward real-input plan of n_real = N, radix 2, unchanged).
+ *   - cross power: with X_a = (ar, ai) and Y_b = (br, bi) the plan-precision spectra of one segment at bin k, widened to double,
+ *     re = ar br + ai bi and im = ar bi - ai br (scipy's conj(X) Y), every product and sum rounded on its own, no FMA contraction.
+ *     Bins 0 and N / 2 come from the packed slot 0: bin 0 has re = ar br, bin N / 2 has re = ai bi, both with im = +0.0.
+ *   - accumulators, doubles owned by the caller: acc_xy[i acc_xy_stride + 2 k + {0, 1}] = re, im of pair i, k < bins; acc_auto[c
+ *     acc_auto_stride + k] = the sum of re re + im im of channel c (the Welch bank's acc), optional: NULL skips the auto spectra, and
+ *     coherence then cannot be finalized.
+ *   - slices and sum order: a call runs in slices, each a range [ja, jb) of the call's segments of ALL channels; a slice of u segment
+ *     columns takes u column_bytes of the workspace, column_bytes = channels N size(precision) + (2 npairs + channels) (N / 2 + 1) 8
+ *     (segments, then one partial row per pair and per channel), so jb - ja <= workspace_bytes / column_bytes.  Per (pair or channel,
+ *     bin) and slice: runs of R consecutive segments are summed in ascending order, then the runs in ascending order, then one
+ *     addition into the accumulator; R is the Welch bank's run length for jb - ja segments.  Every
+ *     accumulator element has one owner per launch: no atomics.
+ *   Consequences: identical calls give identical bits; a call that counts one segment adds one product with a single rounding, so
+ *   acc_auto and the real part of a pair (c, c) then equal the Welch bank's acc bit for bit; pair (b, a) is the exact complex
+ *   conjugate of pair (a, b) for any slicing; pair (c, c) has im == 0 exactly and its real part has the bits of acc_auto[c];
+ *   block-by-block calls agree with one long call to rounding.
+ *   - finalize, one launch.  SDSP_HIP_CSD_CROSS: out[i out_stride + 2 k + {0, 1}] = round_p(re c_k), round_p(im c_k), c_k the Welch
+ *     bank's host double m_k scale / frames_total.  SDSP_HIP_CSD_COHERENCE: out[i out_stride + k] = round_p((re re + im im) /
+ *     (A_a A_b)) with A from acc_auto, a plain IEEE division in double: scale and frame count cancel and are not applied, 0 / 0 is NaN
+ *     as in scipy, nothing is clamped.
+ *   - strides count real elements (doubles for the accumulators, plan precision for in and out).  `in` is never written; nothing
+ *     past each row's 2 bins (acc_xy, CROSS out) or bins (acc_auto, COHERENCE out) elements is.
+ */
+#define SDSP_HIP_CSD_CROSS 0
+#define SDSP_HIP_CSD_COHERENCE 1
+typedef struct sdsp_hip_csd_plan sdsp_hip_csd_plan;
+/* n_fft, hop, window, detrend, scaling, fs, precision: as sdsp_hip_welch_plan_create.  channels: fixed per plan, since a slice holds
+ * the same segments of every channel.  pairs: npairs x 2 host channel indices (a_i, b_i).  workspace_bytes: the slice budget (0 = the
+ * default, 256 MiB), used in whole columns.  Errors: those of sdsp_hip_welch_plan_create; channels == 0 or npairs == 0:
+ * SDSP_HIP_ERR_INVALID_SIZE; pairs NULL or an index >= channels: SDSP_HIP_ERR_INVALID_ARG; a budget below one column, or sizes whose
+ * column does not fit 64 bits: SDSP_HIP_ERR_UNSUPPORTED. */
+int sdsp_hip_csd_plan_create(sdsp_hip_csd_plan **plan, uint32_t n_fft, uint32_t hop, const double *window, int detrend, int scaling,
+                             double fs, int precision, uint64_t channels, uint64_t npairs, const uint32_t *pairs,
+                             uint64_t workspace_bytes, int device);
+int sdsp_hip_csd_plan_destroy(sdsp_hip_csd_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples), the plan's `channels` rows.  state: DEVICE pointer (or NULL at
+ * position 0).  acc_xy: DEVICE doubles, pair i = acc_xy[i acc_xy_stride .. + 2 bins).  acc_auto: DEVICE doubles, channel c =
+ * acc_auto[c acc_auto_stride .. + bins), or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable as a linear chain of
+ * launches); one call per plan in flight.  Errors: a null plan, in or acc_xy, state NULL with position > 0, in_stride < samples with
+ * more than one channel, acc_xy_stride < 2 bins with more than one pair, acc_auto_stride < bins with more than one channel, `in`
+ * overlapping state or an accumulator, the accumulators overlapping each other, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG; more
+ * than 2^32 - 1 samples between the first and the last segment of one call: SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_csd_process(sdsp_hip_csd_plan *plan, const void *in, uint64_t in_stride, uint64_t samples, uint64_t position, void *state,
+                         double *acc_xy, uint64_t acc_xy_stride, double *acc_auto, uint64_t acc_auto_stride, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_csd_process_host(sdsp_hip_csd_plan *plan, const void *host_in, uint64_t in_stride, uint64_t samples, uint64_t position,
+                              void *host_state, double *host_acc_xy, uint64_t acc_xy_stride, double *host_acc_auto,
+                              uint64_t acc_auto_stride);
+/* mode: SDSP_HIP_CSD_CROSS (out: npairs rows of 2 bins plan-precision values) or SDSP_HIP_CSD_COHERENCE (npairs rows of bins values);
+ * out: DEVICE pointer.  frames_total: the segments the accumulators hold.  Asynchronous, one launch.  Errors: frames_total == 0:
+ * SDSP_HIP_ERR_INVALID_SIZE; a null plan, acc_xy or out, an unknown mode, COHERENCE with acc_auto NULL, strides below the row with more
+ * than one row, out overlapping an accumulator, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG.  acc_auto is not read in CROSS mode. */
+int sdsp_hip_csd_finalize(sdsp_hip_csd_plan *plan, int mode, const double *acc_xy, uint64_t acc_xy_stride, const double *acc_auto,
+                          uint64_t acc_auto_stride, uint64_t frames_total, void *out, uint64_t out_stride, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_csd_finalize_host(sdsp_hip_csd_plan *plan, int mode, const double *host_acc_xy, uint64_t acc_xy_stride,
+                               const double *host_acc_auto, uint64_t acc_auto_stride, uint64_t frames_total, void *host_out,
+                               uint64_t out_stride);
+/* bytes of the plan's state buffer: (n_fft - 1) channels element size */
+int sdsp_hip_csd_state_bytes(const sdsp_hip_csd_plan *plan, uint64_t *bytes);
+/* kernel launches of one process call of `samples` per channel at `position` with a state buffer (frame, transform, run and combine
+ * launches per slice, plus the state launch when samples > 0); finalize is one more */
+int sdsp_hip_csd_plan_launches(const sdsp_hip_csd_plan *plan, uint64_t samples, uint64_t position, uint64_t *launches);
+typedef struct {
+    uint32_t n_fft, hop, bins, hist;
+    int detrend, scaling;
+    double fs;
+    int precision, device;
+    uint64_t channels, npairs;
+    uint64_t column_bytes;    /* workspace bytes of one segment column (the formula above) */
+    uint64_t slice_columns;   /* segment columns per slice: workspace_bytes / column_bytes */
+    uint64_t workspace_bytes; /* slice_columns column_bytes */
+    char kernel[64];          /* the inner transform's kernel */
+} sdsp_hip_csd_plan_info;
+int sdsp_hip_csd_plan_get_info(const sdsp_hip_csd_plan *plan, sdsp_hip_csd_plan_info *info);
+
 /* ------------------------------------------------------------------ polyphase filter-bank channelizer banks */
 
 /*

@@ -6,7 +6,7 @@ the library or without a HIP device raises (there is no CPU path here).
 """
 from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP, IIR_HP, IIR_BP, FILTER_NONE,
                    FILTER_LOW_PASS, FILTER_HIGH_PASS, FILTER_BAND_PASS, FILTER_BAND_STOP, FIR_DIRECT, FIR_FFT, PAD_NONE, PAD_ODD, PAD_EVEN,
-                   PAD_CONSTANT, DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR, SCALING_DENSITY, SCALING_SPECTRUM, PFB_REAL, PFB_COMPLEX,
+                   PAD_CONSTANT, DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR, SCALING_DENSITY, SCALING_SPECTRUM, CSD_CROSS, CSD_COHERENCE, PFB_REAL, PFB_COMPLEX,
                    PFB_PHASE_FRAME, PFB_PHASE_TIME,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
@@ -18,6 +18,7 @@ from .stft import stft_bank, stft_window
 from .istft import istft_bank, synthesis_window as istft_synthesis_window
 from .filtfilt import filtfilt_plan, sosfiltfilt, steady_state as iir_steady_state, default_padlen as filtfilt_default_padlen
 from .welch import welch_bank, welch
+from .csd import csd_bank, csd, coherence
 from .pfb import pfb_bank, pfb_prototype
 from .pfb_synth import pfb_synthesis_bank, pfb_dual_prototype
 

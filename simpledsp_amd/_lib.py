@@ -100,6 +100,15 @@ class WelchPlanInfo(C.Structure):
     ]
 
 
+class CsdPlanInfo(C.Structure):
+    _fields_ = [
+        ("n_fft", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32), ("detrend", C.c_int),
+        ("scaling", C.c_int), ("fs", C.c_double), ("precision", C.c_int), ("device", C.c_int), ("channels", C.c_uint64),
+        ("npairs", C.c_uint64), ("column_bytes", C.c_uint64), ("slice_columns", C.c_uint64), ("workspace_bytes", C.c_uint64),
+        ("kernel", C.c_char * 64),
+    ]
+
+
 class PfbPlanInfo(C.Structure):
     _fields_ = [
         ("channels_m", C.c_uint32), ("taps_per_channel", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("hist", C.c_uint32),
@@ -122,6 +131,7 @@ PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
 
 DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR = 0, 1, 2
 SCALING_DENSITY, SCALING_SPECTRUM = 0, 1
+CSD_CROSS, CSD_COHERENCE = 0, 1
 
 
 # name -> (restype, argtypes); every symbol include/sdsp_hip.h declares
@@ -231,6 +241,15 @@ SIGNATURES = {
     "sdsp_hip_welch_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_welch_plan_launches": (_i, [_vp, _u64, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_welch_plan_get_info": (_i, [_vp, C.POINTER(WelchPlanInfo)]),
+    "sdsp_hip_csd_plan_create": (_i, [_pp, _u32, _u32, _vp, _i, _i, _d, _i, _u64, _u64, _vp, _u64, _i]),
+    "sdsp_hip_csd_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_csd_process": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "sdsp_hip_csd_process_host": (_i, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u64]),
+    "sdsp_hip_csd_finalize": (_i, [_vp, _i, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp]),
+    "sdsp_hip_csd_finalize_host": (_i, [_vp, _i, _vp, _u64, _vp, _u64, _u64, _vp, _u64]),
+    "sdsp_hip_csd_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_csd_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_csd_plan_get_info": (_i, [_vp, C.POINTER(CsdPlanInfo)]),
     "sdsp_hip_pfb_prototype": (_i, [_i, _u32, _u32, _vp]),
     "sdsp_hip_pfb_frames": (_i, [_u32, _u64, C.POINTER(_u64)]),
     "sdsp_hip_pfb_plan_create": (_i, [_pp, _u32, _u32, _u32, _vp, _i, _i, _i, _u64, _i]),

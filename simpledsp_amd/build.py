@@ -49,6 +49,7 @@ SOURCES = {
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA
+    "csd.hip": ["-ffp-contract=off"],  # cross power: four products, a sum and a difference, each rounded on its own, never an FMA
     "pfb.hip": ["-ffp-contract=off"],  # the fold: fl(x h) then one addition per tap, never an FMA
     "pfb_synth.hip": ["-ffp-contract=off"],  # the unfold: fl(g v) then one addition per frame, never an FMA
     "stream_carry.hip": [],  # the banks' carried state: copies only, no arithmetic to pin

@@ -5,6 +5,8 @@
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
@@ -93,8 +95,8 @@ struct host_stage {
         bool copy_back; // `host` is writable where this is set
     };
     const char *family;
-    item items[3] = {};
-    void *dev[3] = {};
+    item items[4] = {};
+    void *dev[4] = {};
     size_t n = 0;
 
     host_stage(const char *family_, std::initializer_list<item> list) : family(family_)
@@ -454,6 +456,20 @@ struct sdsp_hip_welch_plan {
     void *ws = nullptr;                 // ws_units x n reals (the slice's segments, transformed in place), then the run partials
     double *part = nullptr;             // inside ws: up to ws_units x bins doubles
     uint64_t ws_units = 0, workspace_bytes = 0;
+};
+
+struct sdsp_hip_csd_plan {
+    uint32_t n = 0, hop = 0, hist = 0, bins = 0; // hist = n - 1, bins = n / 2 + 1
+    int detrend = 0, scaling = 0, precision = 0, device = 0;
+    double fs = 1.0, scale = 1.0;       // scale: as the Welch plan's
+    uint64_t channels = 0, npairs = 0;
+    sdsp_hip_fft_plan *inner = nullptr; // forward real-input plan of n_real = n, radix 2
+    void *window = nullptr;             // n values, plan precision
+    void *ws = nullptr;                 // channels x ws_cols x n reals (the slice's segments, transformed in place), then the partials
+    double *part_xy = nullptr;          // inside ws: npairs x ws_cols x bins complex doubles
+    double *part_auto = nullptr;        // inside ws: channels x ws_cols x bins doubles
+    uint32_t *tables = nullptr;         // device: the pairs (2 npairs), the run order with auto entries (3 (npairs + channels)), without
+    uint64_t ws_cols = 0, column_bytes = 0, workspace_bytes = 0;
 };
 
 struct sdsp_hip_pfb_plan {
@@ -3279,6 +3295,379 @@ int sdsp_hip_welch_finalize_host(sdsp_hip_welch_plan *p, const double *host_acc,
     if (!rc)
         rc = welch_finalize_run(p, static_cast<const double *>(st.dev[0]), acc_stride, frames_total, st.dev[1], out_stride, channels,
                                 nullptr);
+    return st.out(rc);
+}
+
+// ------------------------------------------------------------------ cross-spectral density banks (csd.hip)
+
+namespace
+{
+// the bytes of the first element through the last of `rows` rows of `row` elements `stride` apart
+uint64_t rows_bytes(uint64_t rows, uint64_t stride, uint64_t row, uint64_t element_bytes)
+{
+    return rows ? ((rows - 1) * stride + row) * element_bytes : 0;
+}
+
+int csd_run(sdsp_hip_csd_plan *p, const void *in, uint64_t in_stride, uint64_t samples, uint64_t position, void *state, double *acc_xy,
+            uint64_t acc_xy_stride, double *acc_auto, uint64_t acc_auto_stride, hipStream_t stream)
+{
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_welch_frames(p->n, p->hop, position, samples, &frames))
+        return rc;
+    const uint64_t first = position < p->n ? 0 : (position - p->n) / p->hop + 1; // the call's first segment
+    const uint64_t off0 = first * p->hop + p->hist - position;                  // in [0, max(N - 1, hop - 1)]
+    if (frames && off0 + (frames - 1) * p->hop > 0xffffffffull)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many samples for one call");
+    welch_args w{};
+    w.in = in;
+    w.state = state;
+    w.window = p->window;
+    w.ws = p->ws;
+    w.in_stride = in_stride;
+    w.channels = p->channels;
+    w.n = p->n;
+    w.hop = p->hop;
+    w.detrend = p->detrend;
+    w.g0 = 0;
+    csd_args a{};
+    a.ws = p->ws;
+    a.part_xy = p->part_xy;
+    a.part_auto = p->part_auto;
+    a.acc_xy = acc_xy;
+    a.acc_auto = acc_auto;
+    a.acc_xy_stride = acc_xy_stride;
+    a.acc_auto_stride = acc_auto_stride;
+    a.npairs = static_cast<uint32_t>(p->npairs);
+    a.nentries = static_cast<uint32_t>(acc_auto ? p->npairs + p->channels : p->npairs);
+    a.table = p->tables + 2 * p->npairs + (acc_auto ? 0 : 3 * (p->npairs + p->channels));
+    a.n = p->n;
+    for (uint64_t ja = 0; ja < frames; ja += p->ws_cols) {
+        const uint64_t cols = std::min(p->ws_cols, frames - ja);
+        // the Welch bank's frame stage on the rectangle of every channel's segments [ja, ja + cols): units in channel-major order
+        w.frames = static_cast<uint32_t>(cols);
+        w.units = static_cast<uint32_t>(p->channels * cols);
+        w.off0 = static_cast<uint32_t>(off0 + ja * p->hop);
+        if (int rc = launch_welch(p->precision, w, WELCH_FRAME, stream))
+            return rc;
+        if (int rc = fft_exec_pieces(p->inner, p->ws, w.units, stream, p->inner->variant))
+            return rc;
+        a.frames = w.frames;
+        a.run = welch_run_length(cols, cols);
+        if (int rc = launch_csd(p->precision, a, CSD_RUN, stream))
+            return rc;
+        if (int rc = launch_csd(p->precision, a, CSD_COMBINE, stream))
+            return rc;
+    }
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    // after every frame launch: they may read the old history (the label keeps the message texts of the STFT bank's launch)
+    return carry_history(p->precision, real_size(p->precision), in, in_stride, state, p->channels, samples, p->hist, stream, "stft");
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int csd_check(const sdsp_hip_csd_plan *p, const void *in, uint64_t in_stride, uint64_t samples, uint64_t position, const void *state,
+              const double *acc_xy, uint64_t acc_xy_stride, const double *acc_auto, uint64_t acc_auto_stride)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_welch_frames(p->n, p->hop, position, samples, &frames))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !acc_xy)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or acc_xy is null");
+    if (!state && position > 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "state may be null only at position 0");
+    if (p->channels > 1 && (in_stride < samples || (acc_auto && acc_auto_stride < p->bins)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and acc_auto_stride >= bins");
+    if (p->npairs > 1 && acc_xy_stride < 2ull * p->bins)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc_xy_stride must be >= 2 bins");
+    return SDSP_HIP_OK;
+}
+
+int csd_finalize_check(const sdsp_hip_csd_plan *p, int mode, const double *acc_xy, uint64_t acc_xy_stride, const double *acc_auto,
+                       uint64_t acc_auto_stride, uint64_t frames_total, const void *out, uint64_t out_stride)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (mode != SDSP_HIP_CSD_CROSS && mode != SDSP_HIP_CSD_COHERENCE)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mode must be SDSP_HIP_CSD_CROSS or _COHERENCE");
+    if (frames_total == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "frames_total must be >= 1");
+    if (!acc_xy || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc_xy or out is null");
+    if (mode == SDSP_HIP_CSD_COHERENCE && !acc_auto)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "coherence needs acc_auto");
+    const uint64_t row = mode == SDSP_HIP_CSD_CROSS ? 2ull * p->bins : p->bins;
+    if (p->npairs > 1 && (acc_xy_stride < 2ull * p->bins || out_stride < row))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc_xy_stride must be >= 2 bins and out_stride >= the output row");
+    if (mode == SDSP_HIP_CSD_COHERENCE && p->channels > 1 && acc_auto_stride < p->bins)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc_auto_stride must be >= bins");
+    return SDSP_HIP_OK;
+}
+
+uint64_t csd_out_row(const sdsp_hip_csd_plan *p, int mode) { return mode == SDSP_HIP_CSD_CROSS ? 2ull * p->bins : p->bins; }
+
+int csd_finalize_run(const sdsp_hip_csd_plan *p, int mode, const double *acc_xy, uint64_t acc_xy_stride, const double *acc_auto,
+                     uint64_t acc_auto_stride, uint64_t frames_total, void *out, uint64_t out_stride, hipStream_t stream)
+{
+    csd_args a{};
+    a.table = p->tables;
+    a.acc_xy = const_cast<double *>(acc_xy);
+    a.acc_auto = const_cast<double *>(acc_auto);
+    a.acc_xy_stride = acc_xy_stride;
+    a.acc_auto_stride = acc_auto_stride;
+    a.out = out;
+    a.out_stride = out_stride;
+    a.npairs = static_cast<uint32_t>(p->npairs);
+    a.n = p->n;
+    a.mode = mode;
+    a.c_edge = p->scale / static_cast<double>(frames_total);
+    a.c_mid = 2.0 * p->scale / static_cast<double>(frames_total);
+    return launch_csd(p->precision, a, CSD_FINALIZE, stream);
+}
+} // namespace
+
+int sdsp_hip_csd_plan_create(sdsp_hip_csd_plan **out, uint32_t n_fft, uint32_t hop, const double *window, int detrend, int scaling,
+                             double fs, int precision, uint64_t channels, uint64_t npairs, const uint32_t *pairs,
+                             uint64_t workspace_bytes, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (int rc = check_frame_shape(n_fft, hop, window, precision))
+        return rc;
+    if (detrend != SDSP_HIP_DETREND_NONE && detrend != SDSP_HIP_DETREND_CONSTANT && detrend != SDSP_HIP_DETREND_LINEAR)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "detrend must be SDSP_HIP_DETREND_NONE, _CONSTANT or _LINEAR");
+    if (scaling != SDSP_HIP_SCALING_DENSITY && scaling != SDSP_HIP_SCALING_SPECTRUM)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scaling must be SDSP_HIP_SCALING_DENSITY or _SPECTRUM");
+    if (!(fs > 0.0) || !std::isfinite(fs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "fs must be finite and > 0");
+    if (int rc = check_real_input_range(n_fft, precision))
+        return rc;
+    if (channels == 0 || npairs == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels and npairs must be >= 1");
+    if (!pairs)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "pairs is null");
+    if (channels >= (1ull << 30) || npairs >= (1ull << 30))
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "too many channels or pairs");
+    for (uint64_t i = 0; i < 2 * npairs; i++)
+        if (pairs[i] >= channels)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "pair " + std::to_string(i / 2) + " names channel " + std::to_string(pairs[i]) +
+                                                      " of " + std::to_string(channels));
+    // one column: every channel's segment, and one partial row per pair (complex) and per channel
+    const uint64_t bins = n_fft / 2 + 1;
+    const uint64_t column_bytes = channels * n_fft * real_size(precision) + (2 * npairs + channels) * bins * 8;
+    const uint64_t budget = workspace_bytes ? workspace_bytes : kWelchDefaultBudget;
+    if (budget < column_bytes)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "workspace_bytes holds no segment column: one takes " + std::to_string(column_bytes) +
+                                                  " bytes");
+    // the window rounded once to the plan precision; the scale sums run over those values
+    std::vector<double> wr(window, window + n_fft);
+    if (precision == SDSP_HIP_F32)
+        for (double &v : wr)
+            v = static_cast<double>(static_cast<float>(v));
+    double sw = 0.0, sw2 = 0.0;
+    for (double v : wr) {
+        sw += v;
+        sw2 += v * v;
+    }
+    // the tables: the pairs as given; the run stage's order (sorted by a, then b, channel c's auto entry behind the pairs with a = c)
+    // with and without the auto entries
+    std::vector<std::array<uint32_t, 3>> order;
+    for (uint64_t i = 0; i < npairs; i++)
+        order.push_back({ pairs[2 * i], pairs[2 * i + 1], static_cast<uint32_t>(i) });
+    std::stable_sort(order.begin(), order.end(), [](const auto &x, const auto &y) { return x[0] != y[0] ? x[0] < y[0] : x[1] < y[1]; });
+    std::vector<uint32_t> tab(pairs, pairs + 2 * npairs);
+    size_t at = 0;
+    for (uint64_t c = 0; c < channels; c++) {
+        for (; at < order.size() && order[at][0] == c; at++)
+            tab.insert(tab.end(), order[at].begin(), order[at].end());
+        tab.insert(tab.end(), { static_cast<uint32_t>(c), static_cast<uint32_t>(c), static_cast<uint32_t>(npairs + c) });
+    }
+    for (const auto &e : order)
+        tab.insert(tab.end(), e.begin(), e.end());
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_csd_plan();
+    p->n = n_fft;
+    p->hop = hop;
+    p->hist = n_fft - 1;
+    p->bins = n_fft / 2 + 1;
+    p->detrend = detrend;
+    p->scaling = scaling;
+    p->fs = fs;
+    p->scale = scaling == SDSP_HIP_SCALING_DENSITY ? 1.0 / (fs * sw2) : 1.0 / (sw * sw);
+    p->precision = precision;
+    p->device = device;
+    p->channels = channels;
+    p->npairs = npairs;
+    p->column_bytes = column_bytes;
+    p->ws_cols = std::min<uint64_t>(budget / column_bytes, (1ull << 30) / channels); // a slice's units are counted in 32 bits
+    p->workspace_bytes = p->ws_cols * column_bytes;
+    int rc = fft_plan_create(&p->inner, n_fft / 2, 2, SDSP_HIP_FORWARD, precision, channels * p->ws_cols, device, 1);
+    if (!rc) {
+        hipError_t e = hipMalloc(&p->ws, p->workspace_bytes);
+        if (e == hipSuccess) {
+            p->part_xy = reinterpret_cast<double *>(static_cast<char *>(p->ws) + channels * p->ws_cols * n_fft * real_size(precision));
+            p->part_auto = p->part_xy + 2 * npairs * p->ws_cols * bins;
+            e = upload_reals(wr.data(), n_fft, precision, &p->window); // wr holds the rounded values: converting them again is exact
+        }
+        if (e == hipSuccess)
+            e = hipMalloc(reinterpret_cast<void **>(&p->tables), tab.size() * sizeof(uint32_t));
+        if (e == hipSuccess)
+            e = hipMemcpy(p->tables, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            rc = plan_fail(e, "csd");
+    }
+    if (rc) {
+        sdsp_hip_csd_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_csd_plan_destroy(sdsp_hip_csd_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->tables);
+    free_bank(p->device, p->ws, p->window, p->inner);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_csd_state_bytes(const sdsp_hip_csd_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * p->channels * real_size(p->precision);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_csd_plan_get_info(const sdsp_hip_csd_plan *p, sdsp_hip_csd_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->n_fft = p->n;
+    info->hop = p->hop;
+    info->bins = p->bins;
+    info->hist = p->hist;
+    info->detrend = p->detrend;
+    info->scaling = p->scaling;
+    info->fs = p->fs;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->channels = p->channels;
+    info->npairs = p->npairs;
+    info->column_bytes = p->column_bytes;
+    info->slice_columns = p->ws_cols;
+    info->workspace_bytes = p->workspace_bytes;
+    std::strncpy(info->kernel, select_kernel(p->inner, p->inner->variant).name, sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_csd_plan_launches(const sdsp_hip_csd_plan *p, uint64_t samples, uint64_t position, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t frames = 0;
+    if (int rc = sdsp_hip_welch_frames(p->n, p->hop, position, samples, &frames))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    // a slice of `cols` columns is channels cols units of the transform
+    *launches = slice_launch_count(p->inner, p->channels * frames, p->channels * p->ws_cols, 3) + 1;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_csd_process(sdsp_hip_csd_plan *p, const void *in, uint64_t in_stride, uint64_t samples, uint64_t position, void *state,
+                         double *acc_xy, uint64_t acc_xy_stride, double *acc_auto, uint64_t acc_auto_stride, void *stream)
+{
+    if (int rc = csd_check(p, in, in_stride, samples, position, state, acc_xy, acc_xy_stride, acc_auto, acc_auto_stride))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t rs = real_size(p->precision);
+    const uint64_t in_bytes = rows_bytes(p->channels, in_stride, samples, rs);
+    const uint64_t xy_bytes = rows_bytes(p->npairs, acc_xy_stride, 2ull * p->bins, 8);
+    const uint64_t auto_bytes = rows_bytes(p->channels, acc_auto_stride, p->bins, 8);
+    if (ranges_overlap(in, in_bytes, state, p->channels * p->hist * rs) || ranges_overlap(in, in_bytes, acc_xy, xy_bytes) ||
+        ranges_overlap(in, in_bytes, acc_auto, auto_bytes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in overlaps state or an accumulator");
+    if (ranges_overlap(acc_xy, xy_bytes, acc_auto, auto_bytes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "acc_xy and acc_auto overlap");
+    if (misaligned(in, rs) || misaligned(state, rs) || misaligned(acc_xy, 8) || misaligned(acc_auto, 8))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, state and the accumulators must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return csd_run(p, in, in_stride, samples, position, state, acc_xy, acc_xy_stride, acc_auto, acc_auto_stride,
+                   reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_csd_process_host(sdsp_hip_csd_plan *p, const void *host_in, uint64_t in_stride, uint64_t samples, uint64_t position,
+                              void *host_state, double *host_acc_xy, uint64_t acc_xy_stride, double *host_acc_auto,
+                              uint64_t acc_auto_stride)
+{
+    if (int rc = csd_check(p, host_in, in_stride, samples, position, host_state, host_acc_xy, acc_xy_stride, host_acc_auto,
+                           acc_auto_stride))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = real_size(p->precision);
+    host_stage st("csd", { { host_in, rows_bytes(p->channels, in_stride, samples, rs), false },
+                           { host_acc_xy, rows_bytes(p->npairs, acc_xy_stride, 2ull * p->bins, 8), true },
+                           { host_state, p->channels * p->hist * rs, true },
+                           { host_acc_auto, rows_bytes(p->channels, acc_auto_stride, p->bins, 8), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = csd_run(p, st.dev[0], in_stride, samples, position, st.dev[2], static_cast<double *>(st.dev[1]), acc_xy_stride,
+                     static_cast<double *>(st.dev[3]), acc_auto_stride, nullptr);
+    return st.out(rc);
+}
+
+int sdsp_hip_csd_finalize(sdsp_hip_csd_plan *p, int mode, const double *acc_xy, uint64_t acc_xy_stride, const double *acc_auto,
+                          uint64_t acc_auto_stride, uint64_t frames_total, void *out, uint64_t out_stride, void *stream)
+{
+    if (int rc = csd_finalize_check(p, mode, acc_xy, acc_xy_stride, acc_auto, acc_auto_stride, frames_total, out, out_stride))
+        return rc;
+    const uint64_t rs = real_size(p->precision);
+    const uint64_t out_bytes = rows_bytes(p->npairs, out_stride, csd_out_row(p, mode), rs);
+    if (ranges_overlap(acc_xy, rows_bytes(p->npairs, acc_xy_stride, 2ull * p->bins, 8), out, out_bytes) ||
+        (mode == SDSP_HIP_CSD_COHERENCE && ranges_overlap(acc_auto, rows_bytes(p->channels, acc_auto_stride, p->bins, 8), out, out_bytes)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "an accumulator and out overlap");
+    if (misaligned(acc_xy, 8) || misaligned(out, rs) || (mode == SDSP_HIP_CSD_COHERENCE && misaligned(acc_auto, 8)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the accumulators and out must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return csd_finalize_run(p, mode, acc_xy, acc_xy_stride, acc_auto, acc_auto_stride, frames_total, out, out_stride,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_csd_finalize_host(sdsp_hip_csd_plan *p, int mode, const double *host_acc_xy, uint64_t acc_xy_stride,
+                               const double *host_acc_auto, uint64_t acc_auto_stride, uint64_t frames_total, void *host_out,
+                               uint64_t out_stride)
+{
+    if (int rc = csd_finalize_check(p, mode, host_acc_xy, acc_xy_stride, host_acc_auto, acc_auto_stride, frames_total, host_out,
+                                    out_stride))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    const bool coh = mode == SDSP_HIP_CSD_COHERENCE;
+    host_stage st("csd", { { host_acc_xy, rows_bytes(p->npairs, acc_xy_stride, 2ull * p->bins, 8), false },
+                           { host_out, rows_bytes(p->npairs, out_stride, csd_out_row(p, mode), real_size(p->precision)), true },
+                           { coh ? host_acc_auto : nullptr, rows_bytes(p->channels, acc_auto_stride, p->bins, 8), false } });
+    int rc = st.in();
+    if (!rc)
+        rc = csd_finalize_run(p, mode, static_cast<const double *>(st.dev[0]), acc_xy_stride, static_cast<const double *>(st.dev[2]),
+                              acc_auto_stride, frames_total, st.dev[1], out_stride, nullptr);
     return st.out(rc);
 }
 

@@ -324,6 +324,27 @@ struct welch_args {
     double c_edge, c_mid; // finalize: c_k for k = 0, N / 2 and for the bins between
 };
 int launch_welch(int precision, const welch_args &a, int step, void *stream);
+// cross-spectral density banks (csd.hip): the run and combine launches of one slice [ja, jb) of every channel's
+// segments, behind the Welch bank's frame launch (WELCH_FRAME with frames = jb - ja, g0 = 0) and the plan's transform; and finalize
+enum { CSD_RUN = 0, CSD_COMBINE = 1, CSD_FINALIZE = 2 };
+struct csd_args {
+    const void *ws;        // [channel][segment of the slice] packed half spectra, n reals each
+    const uint32_t *table; // device.  run: `nentries` triples (a, b, dst) in launch order, dst < npairs a pair's index, else npairs +
+                           // the channel of an auto entry; finalize: the plan's `npairs` pairs (a, b) in the caller's order
+    double *part_xy;       // the slice's run partials of the pairs: [pair][run][n / 2 + 1] complex doubles
+    double *part_auto;     // ... and of the auto spectra: [channel][run][n / 2 + 1] doubles
+    double *acc_xy;        // acc_xy[i acc_xy_stride + 2 k + {0, 1}]
+    double *acc_auto;      // acc_auto[c acc_auto_stride + k]; null without auto spectra (then nentries == npairs)
+    void *out;             // finalize: plan precision
+    uint64_t acc_xy_stride, acc_auto_stride, out_stride;
+    uint32_t nentries, npairs;
+    uint32_t frames;       // segments per channel in the slice (jb - ja)
+    uint32_t run;          // R: segments per run
+    uint32_t n;
+    int mode;              // finalize: SDSP_HIP_CSD_*
+    double c_edge, c_mid;  // finalize, CROSS: c_k for k = 0, N / 2 and for the bins between
+};
+int launch_csd(int precision, const csd_args &a, int step, void *stream);
 // polyphase filter-bank channelizers (pfb.hip): the fold launch of one rectangle of (channel, frame) units in
 // front of the plan's transform
 struct pfb_args {
