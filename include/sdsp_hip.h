@@ -989,6 +989,94 @@ typedef struct {
 } sdsp_hip_pfb_synth_plan_info;
 int sdsp_hip_pfb_synth_plan_get_info(const sdsp_hip_pfb_synth_plan *plan, sdsp_hip_pfb_synth_plan_info *info);
 
+/* ------------------------------------------------------------------ digital down-converter banks */
+
+/*
+ * Digital down-converter (DDC) bank: from `channels` independent input streams, `nb` bands at arbitrary centre
+ * frequencies are shifted to baseband, low-pass filtered with one real T-tap filter h and decimated by D, with the oscillator phase
+ * continuous across calls.  A band is (src, fcw, phase0): the input channel and two 32-bit phase words, frequency = fcw / 2^32 cycles
+ * per sample (fcw >= 2^31 is a negative frequency), phase0 / 2^32 cycles.  A call takes S samples per channel, S a multiple of D, and
+ * writes exactly S / D interleaved complex outputs per BAND: out[i out_stride + m].  `position` is the number of samples of the stream
+ * that earlier calls consumed.  With x = history followed by the block and n = position + m D, output m of band i is, mathematically,
+ *     y_i[m] = sum over k < T of h[k] x_src[n - k] e^(-2 pi i (phase0_i + fcw_i (n - k)) / 2^32)
+ * (mix, FIR, keep every D-th sample).  It is computed in the factored form, which is the bit-level definition:
+ *   - band taps, host, at plan creation: g_i[k] = h[k] e^(+2 pi i (k fcw_i mod 2^32) / 2^32) -- the integer reduction is exact, cos and
+ *     sin are taken in double, the two products (sdsp_hip_ddc_band_taps) are rounded once to the plan precision.
+ *   - oscillator tables, host, double, rounded once to the plan precision (sdsp_hip_ddc_oscillator):
+ *     C[a] = e^(-2 pi i a / 65536), F[b] = e^(-2 pi i b / 2^32), a, b < 65536.
+ *   - phase index of an output: j = (phase0_i + fcw_i n) mod 2^32 in unsigned integers, exact at any stream position.
+ *   - oscillator value w = C[j >> 16] (x) F[j & 0xffff], where (a (x) b).re = a.re b.re - a.im b.im and (a (x) b).im = a.re b.im + a.im b.re:
+ *     two products and one sum or difference, each rounded on its own, never contracted.
+ *   - filter sum z = sum over k of g_i[k] x[n - k] in ascending k, accumulators starting at +0.  REAL: per tap zr += gr x, zi += gi x.
+ *     COMPLEX: per tap, in this order, zr += gr xr, zr -= gi xi, zi += gr xi, zi += gi xr.  Every step is one fmaf in f32 and a multiply
+ *     then an add, each rounded, in f64 (the resampler's rule).
+ *   - output y = z (x) w.
+ *   - history: H = T - 1 elements of the input kind per INPUT CHANNEL (not per band), state[c H + j] = x_c[-1 - j] (newest first); read at
+ *     entry, written at exit; NULL = zero history, final history dropped.
+ *   - block-by-block calls equal one long call bit for bit for any split into multiples of D when the caller advances `position`
+ *     (blocks shorter than H and blocks of 0 samples included); position and position + 2^32 give the same bits.
+ *   - input kinds: REAL = samples of the plan precision; COMPLEX = interleaved I/Q (one complex sample is one element, as in the PFB bank).
+ *   - strides count elements.  `in` is never written; nothing past each band's S / D outputs is.
+ * Limits: 1 <= T <= SDSP_HIP_FIR_MAX_TAPS, 1 <= D <= SDSP_HIP_RESAMPLE_MAX_FACTOR, 1 <= nb <= 65536, channels >= 1.  The bands, the taps
+ * and D are fixed at plan creation.  sdsp_hip_resample_design(T, 1, D, h) is the matching anti-aliasing low-pass for D >= 2.
+ */
+#define SDSP_HIP_DDC_REAL 0
+#define SDSP_HIP_DDC_COMPLEX 1
+#define SDSP_HIP_DDC_MAX_BANDS 65536
+typedef struct sdsp_hip_ddc_plan sdsp_hip_ddc_plan;
+typedef struct {
+    uint32_t src;    /* input channel */
+    uint32_t fcw;    /* frequency, cycles per sample in units of 2^-32 */
+    uint32_t phase0; /* phase at stream position 0, cycles in units of 2^-32 */
+} sdsp_hip_ddc_band;
+/* round(f 2^32) mod 2^32 for f in [-0.5, 0.5] (ties to the even word), host only; anything else (NaN included) or fcw NULL:
+ * SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_ddc_phase_word(double cycles_per_sample, uint32_t *fcw);
+/* the band taps before rounding to a plan precision, host only: g[2 k], g[2 k + 1] = h[k] cos, h[k] sin of 2 pi (k fcw mod 2^32) / 2^32.
+ * taps out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_ddc_band_taps(uint32_t taps, const double *h, uint32_t fcw, double *g);
+/* the oscillator tables before rounding, host only: 2 x 65536 doubles each (interleaved re, im).  The values on the axes are exact
+ * (C[32768] = (-1, +0)). */
+int sdsp_hip_ddc_oscillator(double *coarse, double *fine);
+/* outputs per band of one call of `samples` per channel (S / D), host only.  down out of range or samples % down != 0:
+ * SDSP_HIP_ERR_INVALID_SIZE; out NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_ddc_out_samples(uint32_t down, uint64_t samples, uint64_t *out);
+/* h: taps host doubles; bands: nb entries.  The plan rounds the products of sdsp_hip_ddc_band_taps and sdsp_hip_ddc_oscillator to its
+ * precision.  Errors: taps, down, channels = 0, nb = 0 or nb > SDSP_HIP_DDC_MAX_BANDS: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, a
+ * band with src >= channels, an unknown input kind, a precision other than F32 / F64: SDSP_HIP_ERR_INVALID_ARG; no device:
+ * SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_ddc_plan_create(sdsp_hip_ddc_plan **plan, uint32_t taps, const double *h, uint32_t down, uint32_t channels, uint32_t nb,
+                             const sdsp_hip_ddc_band *bands, int input_kind, int precision, int device);
+int sdsp_hip_ddc_plan_destroy(sdsp_hip_ddc_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples) elements of the input kind.  out: DEVICE pointer, band i = out[i out_stride
+ * .. + S / D) complex elements.  state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one
+ * call per plan in flight.  Errors: samples % down != 0: SDSP_HIP_ERR_INVALID_SIZE; null plan, in or out, in_stride < samples with more
+ * than one channel, out_stride < S / D with more than one band, overlapping in and out ranges, misaligned pointers:
+ * SDSP_HIP_ERR_INVALID_ARG; a grid that does not fit one launch: SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_ddc_process(sdsp_hip_ddc_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples,
+                         uint64_t position, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_ddc_process_host(sdsp_hip_ddc_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t samples, uint64_t position, void *host_state);
+/* bytes of the plan's state buffer: H channels element size (0 when T = 1) */
+int sdsp_hip_ddc_state_bytes(const sdsp_hip_ddc_plan *plan, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_ddc_kernel, the fused form (each channel's block staged in LDS once for all
+ * of its bands); 1 = sdsp_ddc_plain_kernel, one output per thread from global memory (the cross-check). */
+int sdsp_hip_ddc_plan_set_variant(sdsp_hip_ddc_plan *plan, int variant);
+/* kernel launches of one process call of `samples` per channel with a state buffer: the band kernel, and one for the new history
+ * when T > 1; 0 for samples == 0 */
+int sdsp_hip_ddc_plan_launches(const sdsp_hip_ddc_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t taps, down, channels, bands;
+    uint32_t hist;      /* H = taps - 1 */
+    uint32_t block_out; /* outputs per band one workgroup of sdsp_ddc_kernel produces from one LDS block (block_out down inputs) */
+    int input_kind, precision, device;
+    char kernel[64];    /* the kernel the plan's variant runs */
+} sdsp_hip_ddc_plan_info;
+int sdsp_hip_ddc_plan_get_info(const sdsp_hip_ddc_plan *plan, sdsp_hip_ddc_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

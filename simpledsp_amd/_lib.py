@@ -125,6 +125,19 @@ class PfbSynthPlanInfo(C.Structure):
     ]
 
 
+class DdcBand(C.Structure):
+    _fields_ = [("src", C.c_uint32), ("fcw", C.c_uint32), ("phase0", C.c_uint32)]
+
+
+class DdcPlanInfo(C.Structure):
+    _fields_ = [
+        ("taps", C.c_uint32), ("down", C.c_uint32), ("channels", C.c_uint32), ("bands", C.c_uint32), ("hist", C.c_uint32),
+        ("block_out", C.c_uint32), ("input_kind", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
+DDC_REAL, DDC_COMPLEX = 0, 1
+DDC_MAX_BANDS = 65536
 PFB_REAL, PFB_COMPLEX = 0, 1
 PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
 PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
@@ -271,6 +284,18 @@ SIGNATURES = {
     "sdsp_hip_pfb_synth_plan_set_unfold_form": (_i, [_vp, _i]),
     "sdsp_hip_pfb_synth_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_pfb_synth_plan_get_info": (_i, [_vp, C.POINTER(PfbSynthPlanInfo)]),
+    "sdsp_hip_ddc_phase_word": (_i, [_d, C.POINTER(_u32)]),
+    "sdsp_hip_ddc_band_taps": (_i, [_u32, _vp, _u32, _vp]),
+    "sdsp_hip_ddc_oscillator": (_i, [_vp, _vp]),
+    "sdsp_hip_ddc_out_samples": (_i, [_u32, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_ddc_plan_create": (_i, [_pp, _u32, _vp, _u32, _u32, _u32, _vp, _i, _i, _i]),
+    "sdsp_hip_ddc_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_ddc_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_ddc_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_ddc_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_ddc_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_ddc_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_ddc_plan_get_info": (_i, [_vp, C.POINTER(DdcPlanInfo)]),
 }
 
 _lib = None

@@ -626,6 +626,81 @@ int sdsp_hip_resample_out_samples(uint32_t up, uint32_t down, uint64_t samples, 
     *out = samples / q * (up / a);
     return SDSP_HIP_OK;
 }
+// e^(+2 pi i a / 2^32) for a 32-bit phase word.  The reduction is in integers: the quadrant is a's top two bits, and inside the
+// quadrant the angle is folded to [0, pi / 4] before libm sees it, so the four axis values are exact and every other value has
+// the relative accuracy of libm on a small argument.
+static void ddc_unit_phase(uint32_t a, double *re, double *im)
+{
+    const uint32_t quadrant = a >> 30, r = a & 0x3fffffffu;
+    const double scale = 2 * M_PI / 4294967296.0;
+    double c, s;
+    if (r <= 0x20000000u) {
+        c = std::cos(scale * r);
+        s = std::sin(scale * r);
+    } else { // cos(pi / 2 - t) = sin(t)
+        c = std::sin(scale * (0x40000000u - r));
+        s = std::cos(scale * (0x40000000u - r));
+    }
+    switch (quadrant) {
+    case 0: *re = c; *im = s; break;
+    case 1: *re = -s; *im = c; break;
+    case 2: *re = -c; *im = -s; break;
+    default: *re = s; *im = -c; break;
+    }
+}
+int sdsp_hip_ddc_phase_word(double cycles_per_sample, uint32_t *fcw)
+{
+    if (!fcw)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *fcw = 0;
+    if (!(cycles_per_sample >= -0.5 && cycles_per_sample <= 0.5)) // NaN included
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "frequency must be in [-0.5, 0.5] cycles per sample");
+    // the scaling is exact; ties go to the even word (Python's round); -2^31 .. 2^31 wraps to the 32-bit word
+    const int64_t w = static_cast<int64_t>(std::nearbyint(cycles_per_sample * 4294967296.0));
+    *fcw = static_cast<uint32_t>(static_cast<uint64_t>(w) & 0xffffffffull);
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_ddc_band_taps(uint32_t taps, const double *h, uint32_t fcw, double *g)
+{
+    if (!h || !g)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null pointer");
+    if (taps == 0 || taps > SDSP_HIP_FIR_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_FIR_MAX_TAPS]");
+    for (uint32_t k = 0; k < taps; k++) {
+        double c, s;
+        ddc_unit_phase(k * fcw, &c, &s); // k fcw mod 2^32: unsigned wrap-around
+        g[2 * k] = h[k] * c;
+        g[2 * k + 1] = h[k] * s;
+    }
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_ddc_oscillator(double *coarse, double *fine)
+{
+    if (!coarse || !fine)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    for (uint32_t a = 0; a < 65536; a++) { // the conjugates: e^(-2 pi i a / 65536) and e^(-2 pi i a / 2^32)
+        double c, s;
+        ddc_unit_phase(a << 16, &c, &s);
+        coarse[2 * a] = c;
+        coarse[2 * a + 1] = -s;
+        ddc_unit_phase(a, &c, &s);
+        fine[2 * a] = c;
+        fine[2 * a + 1] = -s;
+    }
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_ddc_out_samples(uint32_t down, uint64_t samples, uint64_t *out)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *out = 0;
+    if (down == 0 || down > SDSP_HIP_RESAMPLE_MAX_FACTOR)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "down must be in [1, SDSP_HIP_RESAMPLE_MAX_FACTOR]");
+    if (samples % down)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be a multiple of down");
+    *out = samples / down;
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_stft_window(int kind, uint32_t n, double *w)
 {
     if (!w)

@@ -276,6 +276,26 @@ int carry_history(int precision, uint32_t elem_bytes, const void *in, uint64_t i
 // out, the rest move to the front of their row
 int carry_seed(int precision, uint32_t elem_bytes, void *out, uint64_t out_stride, void *state, uint64_t channels, uint64_t samples,
                uint32_t hist, void *stream, const char *family);
+// digital down-converter banks (ddc.hip): the one launch of a call, in front of carry_history
+struct ddc_args {
+    const void *in;
+    void *out;
+    const void *state;     // nullable; channels x (taps - 1) elements of the input kind, newest first
+    const void *g;         // device, plan precision: [band in table order][tap] interleaved complex band taps
+    const void *coarse;    // device, plan precision: C[a], F[b], 65536 interleaved complex values each
+    const void *fine;
+    const uint32_t *csr;   // device: channels + 1 offsets into the table (the bands sorted by src)
+    const uint32_t *bands; // device: 4 words per band in table order: output row, src, fcw, phase0
+    uint64_t samples, in_stride, out_stride, position;
+    uint32_t taps, down, channels, nb;
+    int complex_in;
+};
+int launch_ddc(int precision, const ddc_args &a, int variant, void *stream);
+const char *ddc_kernel_for(int variant);
+// once per device and instantiation, at plan creation: the fused kernel's dynamic-LDS limit, large enough for every plan
+int ddc_prepare(int precision, int complex_in);
+// outputs per band and LDS block of sdsp_ddc_kernel for these sizes
+uint32_t ddc_block_out(int precision, int complex_in, uint32_t taps, uint32_t down);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
