@@ -1077,6 +1077,88 @@ typedef struct {
 } sdsp_hip_ddc_plan_info;
 int sdsp_hip_ddc_plan_get_info(const sdsp_hip_ddc_plan *plan, sdsp_hip_ddc_plan_info *info);
 
+/* ------------------------------------------------------------------ digital up-converter banks */
+
+/*
+ * Digital up-converter (DUC) bank, the mirror of the DDC bank: `nb` baseband complex band streams, all at the
+ * same low rate, are interpolated by U through one real T-tap low-pass h in polyphase form, shifted up to their centre frequencies
+ * and summed into `channels` output streams, with the oscillator phase continuous across calls.  A band is (dst, fcw, phase0): the
+ * output channel and the DDC's two 32-bit phase words (sdsp_hip_ddc_phase_word).  A call takes S input samples per BAND (any S >= 0, no
+ * multiple required) and writes exactly S U outputs per CHANNEL: out[c out_stride + r].  `position` is the number of input samples
+ * per band that earlier calls consumed.  With x = a band's history followed by its block, output r of the call has m = r div U,
+ * p = r mod U and the stream index n = position U + r; mathematically
+ *     out_c[r] = sum over the bands i with dst_i = c of e^(+2 pi i (phase0_i + fcw_i n) / 2^32) sum over q of h[q U + p] x_i[m - q].
+ * The bit-level definition:
+ *   - filter sum, per band: z = sum of h[q U + p] x[m - q] over the q >= 0 with q U + p < T, in ascending q, accumulators starting at
+ *     +0; per tap zr += h xr, then zi += h xi; every step is one fmaf in f32 and a multiply then an add, each rounded, in f64 (the
+ *     resampler's rule).  A phase without taps (T <= p) has z = (+0, +0); no phase is padded with zero taps.
+ *   - oscillator: j = (phase0 + fcw n) mod 2^32 in unsigned integers, w = conj(C[j >> 16] (x) F[j & 0xffff]) with C, F and (x) exactly
+ *     the DDC's: the tables of sdsp_hip_ddc_oscillator rounded once to the plan precision; two products and one sum or difference,
+ *     each rounded on its own, never contracted.  The conjugate is the sign flip of the imaginary part, which is exact: a DUC and a
+ *     DDC with the same words turn by exactly conjugate values.
+ *   - band value y = z (x) w.
+ *   - sum: for each output element the channel's bands are taken in ascending band index; COMPLEX: acc_r += y.re and acc_i += y.im
+ *     from +0, one rounded add each; REAL: only y.re = zr wr - zi wi is formed and summed.  A channel that no band names is written
+ *     as +0 over all S U outputs.
+ *   - history: H = floor((T - 1) / U) complex elements per BAND, state[i H + j] = x_i[-1 - j] (newest first); read at entry, written
+ *     at exit; NULL = zero history, final history dropped.
+ *   - block-by-block calls equal one long call bit for bit for any split into blocks when the caller advances `position` (blocks of 0
+ *     samples and blocks shorter than H included); position and position + 2^32 give the same bits.
+ *   - output kinds: COMPLEX = interleaved I/Q; REAL = the real part only.  The input is always interleaved complex of the plan
+ *     precision (one complex sample is one element, as in the PFB and DDC banks).
+ *   - strides count elements.  `in` is never written; nothing past each channel's S U outputs is.
+ * Limits: 1 <= T <= SDSP_HIP_FIR_MAX_TAPS, 1 <= U <= SDSP_HIP_RESAMPLE_MAX_FACTOR, 1 <= nb <= 65536, channels >= 1, any number of
+ * bands per channel.  The bands, the taps and U are fixed at plan creation.  sdsp_hip_resample_design(T, U, 1, h) is the matching
+ * anti-imaging low-pass (gain U) for U >= 2.
+ */
+#define SDSP_HIP_DUC_REAL 0
+#define SDSP_HIP_DUC_COMPLEX 1
+#define SDSP_HIP_DUC_MAX_BANDS 65536
+typedef struct sdsp_hip_duc_plan sdsp_hip_duc_plan;
+typedef struct {
+    uint32_t dst;    /* output channel */
+    uint32_t fcw;    /* frequency, cycles per OUTPUT sample in units of 2^-32 */
+    uint32_t phase0; /* phase at output stream index 0, cycles in units of 2^-32 */
+} sdsp_hip_duc_band;
+/* outputs per channel of one call of `samples` per band (S U), host only.  up out of range, or S U >= 2^62: SDSP_HIP_ERR_INVALID_SIZE;
+ * out NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_duc_out_samples(uint32_t up, uint64_t samples, uint64_t *out);
+/* h: taps host doubles; bands: nb entries.  The plan rounds h and the tables of sdsp_hip_ddc_oscillator to its precision.  Errors:
+ * taps, up, channels = 0, nb = 0 or nb > SDSP_HIP_DUC_MAX_BANDS: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, a band with dst >=
+ * channels, an unknown output kind, a precision other than F32 / F64: SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_duc_plan_create(sdsp_hip_duc_plan **plan, uint32_t taps, const double *h, uint32_t up, uint32_t channels, uint32_t nb,
+                             const sdsp_hip_duc_band *bands, int output_kind, int precision, int device);
+int sdsp_hip_duc_plan_destroy(sdsp_hip_duc_plan *plan);
+/*
+ * in: DEVICE pointer, band i = in[i in_stride .. + samples) complex elements.  out: DEVICE pointer, channel c = out[c out_stride ..
+ * + S U) elements of the output kind.  state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing
+ * (stream-capturable); one call per plan in flight.  Errors: null plan, in or out, in_stride < samples with more than one band,
+ * out_stride < S U with more than one channel, overlapping in and out ranges, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG; a grid
+ * that does not fit one launch: SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_duc_process(sdsp_hip_duc_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples,
+                         uint64_t position, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_duc_process_host(sdsp_hip_duc_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t samples, uint64_t position, void *host_state);
+/* bytes of the plan's state buffer: H nb complex elements (0 when T <= U) */
+int sdsp_hip_duc_state_bytes(const sdsp_hip_duc_plan *plan, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_duc_kernel, the fused form (h and each band's block staged in LDS, the
+ * sums over all of a channel's bands kept in registers, every output written once); 1 = sdsp_duc_plain_kernel, one output per
+ * thread from global memory (the cross-check). */
+int sdsp_hip_duc_plan_set_variant(sdsp_hip_duc_plan *plan, int variant);
+/* kernel launches of one process call of `samples` per band with a state buffer: the band kernel, and one for the new history
+ * when H > 0; 0 for samples == 0 */
+int sdsp_hip_duc_plan_launches(const sdsp_hip_duc_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t taps, up, channels, bands;
+    uint32_t hist;     /* H = floor((taps - 1) / up) */
+    uint32_t block_in; /* input positions per band one workgroup of sdsp_duc_kernel turns into block_in up outputs of its channel */
+    int output_kind, precision, device;
+    char kernel[64];   /* the kernel the plan's variant runs */
+} sdsp_hip_duc_plan_info;
+int sdsp_hip_duc_plan_get_info(const sdsp_hip_duc_plan *plan, sdsp_hip_duc_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,8 +136,21 @@ class DdcPlanInfo(C.Structure):
     ]
 
 
+class DucBand(C.Structure):
+    _fields_ = [("dst", C.c_uint32), ("fcw", C.c_uint32), ("phase0", C.c_uint32)]
+
+
+class DucPlanInfo(C.Structure):
+    _fields_ = [
+        ("taps", C.c_uint32), ("up", C.c_uint32), ("channels", C.c_uint32), ("bands", C.c_uint32), ("hist", C.c_uint32),
+        ("block_in", C.c_uint32), ("output_kind", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
 DDC_REAL, DDC_COMPLEX = 0, 1
 DDC_MAX_BANDS = 65536
+DUC_REAL, DUC_COMPLEX = 0, 1
+DUC_MAX_BANDS = 65536
 PFB_REAL, PFB_COMPLEX = 0, 1
 PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
 PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
@@ -296,6 +309,15 @@ SIGNATURES = {
     "sdsp_hip_ddc_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_ddc_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_ddc_plan_get_info": (_i, [_vp, C.POINTER(DdcPlanInfo)]),
+    "sdsp_hip_duc_out_samples": (_i, [_u32, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_duc_plan_create": (_i, [_pp, _u32, _vp, _u32, _u32, _u32, _vp, _i, _i, _i]),
+    "sdsp_hip_duc_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_duc_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_duc_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_duc_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_duc_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_duc_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_duc_plan_get_info": (_i, [_vp, C.POINTER(DucPlanInfo)]),
 }
 
 _lib = None

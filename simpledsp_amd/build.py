@@ -47,6 +47,7 @@ SOURCES = {
     "fir_fft.hip": [],
     "fir_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64: multiply then add per tap, as fir.hip
     "ddc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps and the two complex products: multiply then add, never an FMA
+    "duc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: f64 taps, the complex products and the band sum never contract
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA

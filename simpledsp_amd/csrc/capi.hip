@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, ddc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -497,6 +497,14 @@ struct sdsp_hip_ddc_plan {
     void *g = nullptr;        // [band in table order][tap] interleaved complex band taps, plan precision
     void *osc = nullptr;      // C then F: 2 x 65536 interleaved complex values, plan precision
     uint32_t *table = nullptr; // channels + 1 offsets (the bands sorted by src), then 4 words per band: output row, src, fcw, phase0
+};
+
+struct sdsp_hip_duc_plan {
+    uint32_t taps = 0, up = 1, hist = 0, channels = 0, nb = 0; // hist = floor((taps - 1) / up)
+    int kind = 0, precision = 0, device = 0, variant = 0;
+    void *h = nullptr;         // the taps, plan precision
+    void *osc = nullptr;       // the DDC's C then F: 2 x 65536 interleaved complex values, plan precision
+    uint32_t *table = nullptr; // channels + 1 offsets (the bands sorted by dst), then 4 words per band: input row, dst, fcw, phase0
 };
 
 struct sdsp_hip_filtfilt_plan {
@@ -4473,6 +4481,237 @@ int sdsp_hip_ddc_process_host(sdsp_hip_ddc_plan *p, const void *host_in, uint64_
     int rc = st.in();
     if (!rc)
         rc = ddc_run(p, st.dev[0], in_stride, st.dev[1], out_stride, samples, position, st.dev[2], nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ digital up-converter banks (duc.hip)
+
+namespace
+{
+uint64_t duc_out_esize(const sdsp_hip_duc_plan *p)
+{
+    return p->kind == SDSP_HIP_DUC_COMPLEX ? esize(p->precision) : real_size(p->precision);
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int duc_check(const sdsp_hip_duc_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride, uint64_t samples,
+              uint64_t *outs)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (int rc = sdsp_hip_duc_out_samples(p->up, samples, outs))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if ((p->nb > 1 && in_stride < samples) || (p->channels > 1 && out_stride < *outs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= samples * up");
+    return SDSP_HIP_OK;
+}
+
+int duc_run(sdsp_hip_duc_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples, uint64_t position,
+            void *state, hipStream_t stream)
+{
+    duc_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = p->hist ? state : nullptr;
+    a.h = p->h;
+    a.coarse = p->osc;
+    a.fine = static_cast<char *>(p->osc) + 65536 * esize(p->precision);
+    a.csr = p->table;
+    a.bands = p->table + p->channels + 1;
+    a.samples = samples;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.position = position;
+    a.taps = p->taps;
+    a.up = p->up;
+    a.channels = p->channels;
+    a.nb = p->nb;
+    a.real_out = p->kind == SDSP_HIP_DUC_REAL;
+    if (int rc = launch_duc(p->precision, a, p->variant, stream))
+        return rc;
+    // behind the band kernel: it reads the old history
+    return carry_history(p->precision, static_cast<uint32_t>(esize(p->precision)), in, in_stride, state, p->nb, samples, p->hist, stream,
+                         "duc");
+}
+} // namespace
+
+int sdsp_hip_duc_plan_create(sdsp_hip_duc_plan **out, uint32_t taps, const double *h, uint32_t up, uint32_t channels, uint32_t nb,
+                             const sdsp_hip_duc_band *bands, int output_kind, int precision, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (taps == 0 || taps > SDSP_HIP_FIR_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_FIR_MAX_TAPS]");
+    if (up == 0 || up > SDSP_HIP_RESAMPLE_MAX_FACTOR)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "up must be in [1, SDSP_HIP_RESAMPLE_MAX_FACTOR]");
+    if (channels == 0 || channels > 0x7fffffffu)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be in [1, 2^31)");
+    if (nb == 0 || nb > SDSP_HIP_DUC_MAX_BANDS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "the band count must be in [1, SDSP_HIP_DUC_MAX_BANDS]");
+    if (!h || !bands)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "coefficient or band pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (output_kind != SDSP_HIP_DUC_REAL && output_kind != SDSP_HIP_DUC_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "output_kind must be SDSP_HIP_DUC_REAL or SDSP_HIP_DUC_COMPLEX");
+    for (uint32_t i = 0; i < nb; i++)
+        if (bands[i].dst >= channels)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "a band names an output channel the plan does not have");
+    if (int rc = use_device(device))
+        return rc;
+    if (int rc = duc_prepare(precision, output_kind == SDSP_HIP_DUC_REAL))
+        return rc;
+    // the bands sorted by output channel (stable: equal channels keep the caller's order, which is the order of the sum), and where
+    // each channel's run starts.  Running out of host memory for the tables is an error code, not an exception
+    std::vector<uint32_t> order, table;
+    std::vector<double> osc;
+    try {
+        order.resize(nb);
+        table.assign(static_cast<size_t>(channels) + 1 + 4 * static_cast<size_t>(nb), 0);
+        osc.resize(4 * 65536);
+    } catch (const std::bad_alloc &) {
+        return fail(SDSP_HIP_ERR_NOMEM, "duc plan: out of host memory for the band tables");
+    }
+    for (uint32_t i = 0; i < nb; i++)
+        order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return bands[a].dst < bands[b].dst; });
+    for (uint32_t s = 0; s < nb; s++) {
+        const sdsp_hip_duc_band &b = bands[order[s]];
+        table[b.dst + 1]++;
+        uint32_t *e = &table[static_cast<size_t>(channels) + 1 + 4 * static_cast<size_t>(s)];
+        e[0] = order[s];
+        e[1] = b.dst;
+        e[2] = b.fcw;
+        e[3] = b.phase0;
+    }
+    for (uint32_t c = 0; c < channels; c++)
+        table[c + 1] += table[c];
+    sdsp_hip_ddc_oscillator(osc.data(), osc.data() + 2 * 65536);
+    auto *p = new sdsp_hip_duc_plan();
+    p->taps = taps;
+    p->up = up;
+    p->hist = (taps - 1) / up;
+    p->channels = channels;
+    p->nb = nb;
+    p->kind = output_kind;
+    p->precision = precision;
+    p->device = device;
+    hipError_t e = upload_reals(h, taps, precision, &p->h);
+    if (e == hipSuccess)
+        e = upload_reals(osc.data(), osc.size(), precision, &p->osc);
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&p->table), table.size() * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(p->table, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        sdsp_hip_duc_plan_destroy(p);
+        return plan_fail(e, "duc");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_duc_plan_destroy(sdsp_hip_duc_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->h);
+        (void)hipFree(p->osc);
+        (void)hipFree(p->table);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_duc_state_bytes(const sdsp_hip_duc_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * p->nb * esize(p->precision);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_duc_plan_set_variant(sdsp_hip_duc_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_duc_plan_launches(const sdsp_hip_duc_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t outs = 0;
+    if (int rc = sdsp_hip_duc_out_samples(p->up, samples, &outs))
+        return rc;
+    if (samples)
+        *launches = 1 + (p->hist ? 1 : 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_duc_plan_get_info(const sdsp_hip_duc_plan *p, sdsp_hip_duc_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->taps = p->taps;
+    info->up = p->up;
+    info->channels = p->channels;
+    info->bands = p->nb;
+    info->hist = p->hist;
+    info->block_in = duc_block_in(p->precision, p->taps, p->up);
+    info->output_kind = p->kind;
+    info->precision = p->precision;
+    info->device = p->device;
+    std::strncpy(info->kernel, duc_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_duc_process(sdsp_hip_duc_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples,
+                         uint64_t position, void *state, void *stream)
+{
+    uint64_t outs = 0;
+    if (int rc = duc_check(p, in, in_stride, out, out_stride, samples, &outs))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t ies = esize(p->precision), oes = duc_out_esize(p);
+    if (int rc = check_out_of_place(in, ((p->nb - 1) * in_stride + samples) * ies, ies, out, ((p->channels - 1) * out_stride + outs) * oes,
+                                    oes, state, ies, "in and out ranges overlap (the up-converter runs out of place)"))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    return duc_run(p, in, in_stride, out, out_stride, samples, position, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_duc_process_host(sdsp_hip_duc_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t samples, uint64_t position, void *host_state)
+{
+    uint64_t outs = 0;
+    if (int rc = duc_check(p, host_in, in_stride, host_out, out_stride, samples, &outs))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t in_bytes = ((p->nb - 1) * in_stride + samples) * esize(p->precision);
+    const size_t out_bytes = ((p->channels - 1) * out_stride + outs) * duc_out_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_duc_state_bytes(p, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    host_stage st("duc", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                       { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = duc_run(p, st.dev[0], in_stride, st.dev[1], out_stride, samples, position, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

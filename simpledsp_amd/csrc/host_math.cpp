@@ -701,6 +701,18 @@ int sdsp_hip_ddc_out_samples(uint32_t down, uint64_t samples, uint64_t *out)
     *out = samples / down;
     return SDSP_HIP_OK;
 }
+int sdsp_hip_duc_out_samples(uint32_t up, uint64_t samples, uint64_t *out)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *out = 0;
+    if (up == 0 || up > SDSP_HIP_RESAMPLE_MAX_FACTOR)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "up must be in [1, SDSP_HIP_RESAMPLE_MAX_FACTOR]");
+    if (samples > (1ull << 62) / up)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples times up must stay below 2^62");
+    *out = samples * up;
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_stft_window(int kind, uint32_t n, double *w)
 {
     if (!w)

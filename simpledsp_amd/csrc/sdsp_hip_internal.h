@@ -296,6 +296,26 @@ const char *ddc_kernel_for(int variant);
 int ddc_prepare(int precision, int complex_in);
 // outputs per band and LDS block of sdsp_ddc_kernel for these sizes
 uint32_t ddc_block_out(int precision, int complex_in, uint32_t taps, uint32_t down);
+// digital up-converter banks (duc.hip): the one launch of a call, in front of carry_history
+struct duc_args {
+    const void *in;        // nb rows of interleaved complex elements
+    void *out;             // channels rows: interleaved complex, or reals when real_out
+    const void *state;     // nullable; nb x floor((taps - 1) / up) complex elements, newest first
+    const void *h;         // device, plan precision, `taps` values
+    const void *coarse;    // device, plan precision: the DDC's C[a], F[b], 65536 interleaved complex values each
+    const void *fine;
+    const uint32_t *csr;   // device: channels + 1 offsets into the table (the bands sorted by dst)
+    const uint32_t *bands; // device: 4 words per band in table order: input row, dst, fcw, phase0
+    uint64_t samples, in_stride, out_stride, position;
+    uint32_t taps, up, channels, nb;
+    int real_out;
+};
+int launch_duc(int precision, const duc_args &a, int variant, void *stream);
+const char *duc_kernel_for(int variant);
+// once per device and instantiation, at plan creation: the fused kernel's dynamic-LDS limit, large enough for every plan
+int duc_prepare(int precision, int real_out);
+// input positions per workgroup of sdsp_duc_kernel for these sizes
+uint32_t duc_block_in(int precision, uint32_t taps, uint32_t up);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
