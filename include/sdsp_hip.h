@@ -1159,6 +1159,88 @@ typedef struct {
 } sdsp_hip_duc_plan_info;
 int sdsp_hip_duc_plan_get_info(const sdsp_hip_duc_plan *plan, sdsp_hip_duc_plan_info *info);
 
+/* ------------------------------------------------------------------ arbitrary-ratio polyphase resampler banks */
+
+/*
+ * Arbitrary-ratio polyphase resampler bank: every channel is resampled by any ratio in [1 / 1024, 1024],
+ * which may change from call to call, through a prototype low-pass h of L T taps split into L phases of T taps (L a power of two,
+ * phase p, tap k = h[k L + p]: the upfirdn layout), taking the nearest phase or interpolating linearly between two.  The channel
+ * count is given per call, as in sdsp_hip_resample_process.
+ * Time is unsigned Q32.32 in units of input samples.  `step` is input samples per output sample, 2^22 <= step <= max_step <= 2^42;
+ * `time` is the instant of the call's first output relative to the call's first input sample, any value < 2^63.  A call takes
+ * S < 2^31 samples per channel.  Output m of the call sits at t = time + m step, i = t >> 32, f = t & 0xffffffff, and the call
+ * produces every m with i < S: n_out = 0 if time >= S 2^32, else ceil((S 2^32 - time) / step); the next call's time is
+ * time + n_out step - S 2^32 (sdsp_hip_arb_out_samples).  All of it is exact integer arithmetic, so any split of a stream into
+ * calls gives the same samples bit for bit (empty calls, calls shorter than the history and calls without an output included).
+ * Value, the bit-level definition: lb = log2 L, p = f >> (32 - lb) (0 for L = 1), r = f & (2^(32 - lb) - 1),
+ *   - mu = fl(r) 2^-(32 - lb), fl the unsigned-to-float conversion of the plan precision, round to nearest even (exact in f64).
+ *   - tables, host, double, rounded once to the plan precision (sdsp_hip_arb_tables): H[p][k] = h[k L + p],
+ *     Dt[p][k] = hext[k L + p + 1] - h[k L + p] with hext = h followed by zeros (the row after phase L - 1 is phase 0 one tap later).
+ *   - with x = the history followed by the block: a = H[p][0] x[i], a plain multiply; then for k = 1 .. T - 1
+ *     a = fmaf(H[p][k], x[i - k], a) in f32, a multiply then an add, each rounded, in f64 (the resampler's rule).  b: the same over Dt.
+ *   - NEAREST: y = a.  LINEAR: y = fmaf(mu, b, a) in f32, a + mu b with two roundings in f64.
+ *   - COMPLEX input (interleaved I/Q, one pair is one element, real taps): the two planes independently by the same steps.
+ *   - history: H = T - 1 elements of the input kind per channel, state[c H + j] = x_c[-1 - j] (newest first); read at entry, written
+ *     at exit (also when n_out = 0); NULL = zero history, final history dropped.
+ *   - strides count elements.  `in` is never written; nothing past each row's n_out outputs is.
+ */
+#define SDSP_HIP_ARB_REAL 0
+#define SDSP_HIP_ARB_COMPLEX 1
+#define SDSP_HIP_ARB_NEAREST 0
+#define SDSP_HIP_ARB_LINEAR 1
+#define SDSP_HIP_ARB_MAX_PHASES 1024
+#define SDSP_HIP_ARB_MIN_STEP (1ull << 22)
+#define SDSP_HIP_ARB_MAX_STEP (1ull << 42)
+typedef struct sdsp_hip_arb_plan sdsp_hip_arb_plan;
+/* round(in_per_out 2^32), ties to even, for in_per_out in [1 / 1024, 1024], host only; anything else (NaN included) or step NULL:
+ * SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_arb_step(double in_per_out, uint64_t *step);
+/* n_out and the next call's time of one call, host only (next_time may be NULL).  step outside [2^22, 2^42], time >= 2^63,
+ * samples >= 2^31 or n_out >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; n_out NULL: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_arb_out_samples(uint64_t step, uint64_t time, uint64_t samples, uint64_t *n_out, uint64_t *next_time);
+/* the matching prototype, host only: a Hamming-windowed sinc of phases * taps taps with cutoff min(1, 1 / max_in_per_out) / phases
+ * of the L-times rate's Nyquist and gain phases, which is phases * scipy.signal.firwin(phases * taps, cutoff).  phases = 1 with a
+ * ratio <= 1 has no band to protect: SDSP_HIP_ERR_INVALID_ARG; sizes out of range: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_arb_design(uint32_t phases, uint32_t taps, double max_in_per_out, double *h);
+/* the two tables before rounding, host only: table_h[p taps + k] = H[p][k], table_d[p taps + k] = Dt[p][k] */
+int sdsp_hip_arb_tables(uint32_t phases, uint32_t taps, const double *h, double *table_h, double *table_d);
+/* h: phases * taps host doubles.  Errors: phases not a power of two in [1, SDSP_HIP_ARB_MAX_PHASES], taps = 0, phases * taps >
+ * SDSP_HIP_FIR_MAX_TAPS, max_step outside [2^22, 2^42]: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an unknown input kind or
+ * interpolation mode, a precision other than F32 / F64: SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_arb_plan_create(sdsp_hip_arb_plan **plan, uint32_t phases, uint32_t taps, const double *h, uint64_t max_step,
+                             int input_kind, int interp, int precision, int device);
+int sdsp_hip_arb_plan_destroy(sdsp_hip_arb_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples) elements of the input kind.  out: DEVICE pointer, channel c =
+ * out[c out_stride .. + n_out) elements of the same kind.  state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing
+ * (stream-capturable); one call per plan in flight.  Errors: step outside [2^22, max_step], time >= 2^63, samples >= 2^31, n_out >=
+ * 2^31: SDSP_HIP_ERR_INVALID_SIZE; null plan, in or out, in_stride < samples or out_stride < n_out with more than one channel,
+ * overlapping in and out ranges, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG; a grid that does not fit one launch:
+ * SDSP_HIP_ERR_UNSUPPORTED.  channels == 0 or samples == 0: nothing to do.
+ */
+int sdsp_hip_arb_process(sdsp_hip_arb_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                         uint64_t samples, uint64_t step, uint64_t time, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_arb_process_host(sdsp_hip_arb_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, uint64_t step, uint64_t time, void *host_state);
+/* bytes of a state buffer for `channels` channels: H channels element size (0 when T = 1) */
+int sdsp_hip_arb_state_bytes(const sdsp_hip_arb_plan *plan, uint64_t channels, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_arb_kernel, the fused form (the tap tables and each block's input span
+ * staged in LDS); 1 = sdsp_arb_plain_kernel, one output per thread from global memory (the cross-check). */
+int sdsp_hip_arb_plan_set_variant(sdsp_hip_arb_plan *plan, int variant);
+/* kernel launches of one process call with a state buffer: the resampling kernel when n_out > 0, and one for the new history when
+ * T > 1; 0 for samples == 0 */
+int sdsp_hip_arb_plan_launches(const sdsp_hip_arb_plan *plan, uint64_t step, uint64_t time, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t phases, taps; /* L, T */
+    uint32_t hist;         /* H = taps - 1 */
+    uint32_t block_out;    /* outputs one workgroup of sdsp_arb_kernel produces from one staged input span */
+    uint64_t max_step;
+    int input_kind, interp, precision, device;
+    char kernel[64];       /* the kernel the plan's variant runs */
+} sdsp_hip_arb_plan_info;
+int sdsp_hip_arb_plan_get_info(const sdsp_hip_arb_plan *plan, sdsp_hip_arb_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,16 @@ class DucPlanInfo(C.Structure):
     ]
 
 
+class ArbPlanInfo(C.Structure):
+    _fields_ = [
+        ("phases", C.c_uint32), ("taps", C.c_uint32), ("hist", C.c_uint32), ("block_out", C.c_uint32), ("max_step", C.c_uint64),
+        ("input_kind", C.c_int), ("interp", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
+ARB_REAL, ARB_COMPLEX = 0, 1
+ARB_NEAREST, ARB_LINEAR = 0, 1
+ARB_MAX_PHASES, ARB_MIN_STEP, ARB_MAX_STEP = 1024, 1 << 22, 1 << 42
 DDC_REAL, DDC_COMPLEX = 0, 1
 DDC_MAX_BANDS = 65536
 DUC_REAL, DUC_COMPLEX = 0, 1
@@ -297,6 +307,18 @@ SIGNATURES = {
     "sdsp_hip_pfb_synth_plan_set_unfold_form": (_i, [_vp, _i]),
     "sdsp_hip_pfb_synth_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_pfb_synth_plan_get_info": (_i, [_vp, C.POINTER(PfbSynthPlanInfo)]),
+    "sdsp_hip_arb_step": (_i, [_d, C.POINTER(_u64)]),
+    "sdsp_hip_arb_out_samples": (_i, [_u64, _u64, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "sdsp_hip_arb_design": (_i, [_u32, _u32, _d, _vp]),
+    "sdsp_hip_arb_tables": (_i, [_u32, _u32, _vp, _vp, _vp]),
+    "sdsp_hip_arb_plan_create": (_i, [_pp, _u32, _u32, _vp, _u64, _i, _i, _i, _i]),
+    "sdsp_hip_arb_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_arb_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_arb_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_arb_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_arb_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_arb_plan_launches": (_i, [_vp, _u64, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_arb_plan_get_info": (_i, [_vp, C.POINTER(ArbPlanInfo)]),
     "sdsp_hip_ddc_phase_word": (_i, [_d, C.POINTER(_u32)]),
     "sdsp_hip_ddc_band_taps": (_i, [_u32, _vp, _u32, _vp]),
     "sdsp_hip_ddc_oscillator": (_i, [_vp, _vp]),

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -505,6 +505,14 @@ struct sdsp_hip_duc_plan {
     void *h = nullptr;         // the taps, plan precision
     void *osc = nullptr;       // the DDC's C then F: 2 x 65536 interleaved complex values, plan precision
     uint32_t *table = nullptr; // channels + 1 offsets (the bands sorted by dst), then 4 words per band: input row, dst, fcw, phase0
+};
+
+struct sdsp_hip_arb_plan {
+    uint32_t phases = 1, taps = 0, hist = 0; // hist = taps - 1
+    uint32_t block_out = 0;                  // outputs per block of sdsp_arb_kernel, fixed here from max_step
+    uint64_t max_step = 0;
+    int kind = 0, interp = 0, precision = 0, device = 0, variant = 0;
+    void *table = nullptr; // [phase][tap] values H (nearest) or interleaved pairs (H, Dt) (linear), plan precision
 };
 
 struct sdsp_hip_filtfilt_plan {
@@ -4712,6 +4720,218 @@ int sdsp_hip_duc_process_host(sdsp_hip_duc_plan *p, const void *host_in, uint64_
     int rc = st.in();
     if (!rc)
         rc = duc_run(p, st.dev[0], in_stride, st.dev[1], out_stride, samples, position, st.dev[2], nullptr);
+    return st.out(rc);
+}
+
+// ------------------------------------------------------------------ arbitrary-ratio resampler banks (arb_resample.hip)
+
+namespace
+{
+uint64_t arb_esize(const sdsp_hip_arb_plan *p) { return p->kind == SDSP_HIP_ARB_COMPLEX ? esize(p->precision) : real_size(p->precision); }
+
+// argument checks shared by process and process_host (device pointers or not)
+int arb_check(const sdsp_hip_arb_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride, uint64_t channels,
+              uint64_t samples, uint64_t step, uint64_t time, uint64_t *outs)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (step > p->max_step)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "step must be in [2^22, the plan's max_step]");
+    if (int rc = sdsp_hip_arb_out_samples(step, time, samples, outs, nullptr))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || (*outs && !out))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < *outs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= the call's outputs per channel");
+    return SDSP_HIP_OK;
+}
+
+int arb_run(sdsp_hip_arb_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels, uint64_t samples,
+            uint64_t step, uint64_t time, uint64_t outs, void *state, hipStream_t stream)
+{
+    if (outs) {
+        arb_args a{};
+        a.in = in;
+        a.out = out;
+        a.state = p->hist ? state : nullptr;
+        a.table = p->table;
+        a.channels = channels;
+        a.samples = samples;
+        a.in_stride = in_stride;
+        a.out_stride = out_stride;
+        a.step = step;
+        a.time = time;
+        a.n_out = outs;
+        a.block_out = p->block_out;
+        a.phases = p->phases;
+        a.taps = p->taps;
+        a.complex_in = p->kind == SDSP_HIP_ARB_COMPLEX;
+        a.linear = p->interp == SDSP_HIP_ARB_LINEAR;
+        if (int rc = launch_arb(p->precision, a, p->variant, stream))
+            return rc;
+    }
+    // behind the resampling kernel: it reads the old history.  Also when the call made no output
+    return carry_history(p->precision, static_cast<uint32_t>(arb_esize(p)), in, in_stride, state, channels, samples, p->hist, stream, "arb");
+}
+} // namespace
+
+int sdsp_hip_arb_plan_create(sdsp_hip_arb_plan **out, uint32_t phases, uint32_t taps, const double *h, uint64_t max_step, int input_kind,
+                             int interp, int precision, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (phases == 0 || phases > SDSP_HIP_ARB_MAX_PHASES || (phases & (phases - 1)))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "phases must be a power of 2 in [1, SDSP_HIP_ARB_MAX_PHASES]");
+    if (taps == 0 || static_cast<uint64_t>(phases) * taps > SDSP_HIP_FIR_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps per phase must be >= 1 and phases * taps <= SDSP_HIP_FIR_MAX_TAPS");
+    if (max_step < SDSP_HIP_ARB_MIN_STEP || max_step > SDSP_HIP_ARB_MAX_STEP)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "max_step must be in [2^22, 2^42]");
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "coefficient pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (input_kind != SDSP_HIP_ARB_REAL && input_kind != SDSP_HIP_ARB_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input_kind must be SDSP_HIP_ARB_REAL or SDSP_HIP_ARB_COMPLEX");
+    if (interp != SDSP_HIP_ARB_NEAREST && interp != SDSP_HIP_ARB_LINEAR)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "interp must be SDSP_HIP_ARB_NEAREST or SDSP_HIP_ARB_LINEAR");
+    if (int rc = use_device(device))
+        return rc;
+    if (int rc = arb_prepare(precision, input_kind == SDSP_HIP_ARB_COMPLEX, interp == SDSP_HIP_ARB_LINEAR))
+        return rc;
+    const uint32_t block_out = arb_block_out(precision, input_kind == SDSP_HIP_ARB_COMPLEX, interp == SDSP_HIP_ARB_LINEAR, phases, taps, max_step);
+    if (block_out == 0)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "arb plan: the line of one output does not fit the LDS next to the table");
+    const size_t n = static_cast<size_t>(phases) * taps;
+    std::vector<double> th(n), td(n), tab;
+    sdsp_hip_arb_tables(phases, taps, h, th.data(), td.data());
+    if (interp == SDSP_HIP_ARB_LINEAR) {
+        tab.resize(2 * n);
+        for (size_t i = 0; i < n; i++) {
+            tab[2 * i] = th[i];
+            tab[2 * i + 1] = td[i];
+        }
+    } else {
+        tab = th;
+    }
+    auto *p = new sdsp_hip_arb_plan();
+    p->phases = phases;
+    p->taps = taps;
+    p->hist = taps - 1;
+    p->max_step = max_step;
+    p->block_out = block_out;
+    p->kind = input_kind;
+    p->interp = interp;
+    p->precision = precision;
+    p->device = device;
+    const hipError_t e = upload_reals(tab.data(), tab.size(), precision, &p->table);
+    if (e != hipSuccess) {
+        sdsp_hip_arb_plan_destroy(p);
+        return plan_fail(e, "arb");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_arb_plan_destroy(sdsp_hip_arb_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->table);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_arb_state_bytes(const sdsp_hip_arb_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * arb_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_arb_plan_set_variant(sdsp_hip_arb_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_arb_plan_launches(const sdsp_hip_arb_plan *p, uint64_t step, uint64_t time, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    if (step > p->max_step)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "step must be in [2^22, the plan's max_step]");
+    uint64_t outs = 0;
+    if (int rc = sdsp_hip_arb_out_samples(step, time, samples, &outs, nullptr))
+        return rc;
+    if (samples)
+        *launches = (outs ? 1 : 0) + (p->hist ? 1 : 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_arb_plan_get_info(const sdsp_hip_arb_plan *p, sdsp_hip_arb_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->phases = p->phases;
+    info->taps = p->taps;
+    info->hist = p->hist;
+    info->block_out = p->block_out;
+    info->max_step = p->max_step;
+    info->input_kind = p->kind;
+    info->interp = p->interp;
+    info->precision = p->precision;
+    info->device = p->device;
+    std::strncpy(info->kernel, arb_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_arb_process(sdsp_hip_arb_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                         uint64_t samples, uint64_t step, uint64_t time, void *state, void *stream)
+{
+    uint64_t outs = 0;
+    if (int rc = arb_check(p, in, in_stride, out, out_stride, channels, samples, step, time, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = arb_esize(p);
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + samples) * es, es, outs ? out : nullptr,
+                                    ((channels - 1) * out_stride + outs) * es, es, state, es,
+                                    "in and out ranges overlap (the resampler runs out of place)"))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    return arb_run(p, in, in_stride, out, out_stride, channels, samples, step, time, outs, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_arb_process_host(sdsp_hip_arb_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, uint64_t step, uint64_t time, void *host_state)
+{
+    uint64_t outs = 0;
+    if (int rc = arb_check(p, host_in, in_stride, host_out, out_stride, channels, samples, step, time, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * arb_esize(p);
+    const size_t out_bytes = ((channels - 1) * out_stride + outs) * arb_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_arb_state_bytes(p, channels, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    host_stage st("arb", { { host_in, in_bytes, false }, { outs ? host_out : nullptr, out_bytes, true },
+                       { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = arb_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, step, time, outs, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

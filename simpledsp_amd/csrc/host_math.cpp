@@ -713,6 +713,80 @@ int sdsp_hip_duc_out_samples(uint32_t up, uint64_t samples, uint64_t *out)
     *out = samples * up;
     return SDSP_HIP_OK;
 }
+// arbitrary-ratio resampler banks: L a power of two in [1, 1024] and L T <= SDSP_HIP_FIR_MAX_TAPS
+static int arb_check_shape(uint32_t phases, uint32_t taps)
+{
+    if (phases == 0 || phases > SDSP_HIP_ARB_MAX_PHASES || (phases & (phases - 1)))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "phases must be a power of 2 in [1, SDSP_HIP_ARB_MAX_PHASES]");
+    if (taps == 0 || static_cast<uint64_t>(phases) * taps > SDSP_HIP_FIR_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps per phase must be >= 1 and phases * taps <= SDSP_HIP_FIR_MAX_TAPS");
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_arb_step(double in_per_out, uint64_t *step)
+{
+    if (!step)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *step = 0;
+    if (!(in_per_out >= 1.0 / 1024 && in_per_out <= 1024.0)) // NaN included
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input samples per output sample must be in [1 / 1024, 1024]");
+    // the scaling is exact; ties go to the even word (Python's round)
+    *step = static_cast<uint64_t>(std::nearbyint(in_per_out * 4294967296.0));
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_arb_out_samples(uint64_t step, uint64_t time, uint64_t samples, uint64_t *n_out, uint64_t *next_time)
+{
+    if (!n_out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *n_out = 0;
+    if (next_time)
+        *next_time = 0;
+    if (step < SDSP_HIP_ARB_MIN_STEP || step > SDSP_HIP_ARB_MAX_STEP)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "step must be in [2^22, 2^42]");
+    if (time >= (1ull << 63))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "time must be below 2^63");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    const uint64_t end = samples << 32; // < 2^63
+    uint64_t n = 0, next = time - end;
+    if (time < end) {
+        n = (end - time + step - 1) / step; // < 2^63 + 2^42
+        next = time + n * step - end;       // < step: n step < end - time + step
+    }
+    if (n >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "the call would produce 2^31 or more outputs per channel");
+    *n_out = n;
+    if (next_time)
+        *next_time = next;
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_arb_design(uint32_t phases, uint32_t taps, double max_in_per_out, double *h)
+{
+    if (int rc = arb_check_shape(phases, taps))
+        return rc;
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    if (!(max_in_per_out >= 1.0 / 1024 && max_in_per_out <= 1024.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input samples per output sample must be in [1 / 1024, 1024]");
+    if (phases == 1 && max_in_per_out <= 1.0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "one phase and a ratio <= 1 change no rate downwards: there is no band to protect");
+    const double cutoff = (max_in_per_out > 1.0 ? 1.0 / max_in_per_out : 1.0) / phases;
+    return design_fir(phases * taps, SDSP_HIP_FILTER_LOW_PASS, cutoff, 2.0, 0.0, static_cast<double>(phases), h);
+}
+int sdsp_hip_arb_tables(uint32_t phases, uint32_t taps, const double *h, double *table_h, double *table_d)
+{
+    if (int rc = arb_check_shape(phases, taps))
+        return rc;
+    if (!h || !table_h || !table_d)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null pointer");
+    const uint64_t n = static_cast<uint64_t>(phases) * taps;
+    for (uint32_t p = 0; p < phases; p++)
+        for (uint32_t k = 0; k < taps; k++) {
+            const uint64_t i = static_cast<uint64_t>(k) * phases + p;
+            table_h[static_cast<uint64_t>(p) * taps + k] = h[i];
+            table_d[static_cast<uint64_t>(p) * taps + k] = (i + 1 < n ? h[i + 1] : 0.0) - h[i];
+        }
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_stft_window(int kind, uint32_t n, double *w)
 {
     if (!w)

@@ -316,6 +316,26 @@ const char *duc_kernel_for(int variant);
 int duc_prepare(int precision, int real_out);
 // input positions per workgroup of sdsp_duc_kernel for these sizes
 uint32_t duc_block_in(int precision, uint32_t taps, uint32_t up);
+// arbitrary-ratio resampler banks (arb_resample.hip): the one launch of a call with n_out > 0, in front of
+// carry_history
+struct arb_args {
+    const void *in;
+    void *out;
+    const void *state;  // nullable; channels x (taps - 1) elements of the input kind, newest first
+    const void *table;  // device, plan precision: [phase][tap] values H (nearest) or pairs (H, Dt) (linear)
+    uint64_t channels, samples, in_stride, out_stride;
+    uint64_t step, time, n_out; // n_out in [1, 2^31): sdsp_hip_arb_out_samples of step, time, samples
+    uint32_t phases, taps;
+    uint32_t block_out; // the plan's: arb_block_out at its max_step
+    int complex_in, linear;
+};
+int launch_arb(int precision, const arb_args &a, int variant, void *stream);
+const char *arb_kernel_for(int variant);
+// once per device and instantiation, at plan creation: the fused kernel's dynamic-LDS limit, large enough for every plan
+int arb_prepare(int precision, int complex_in, int linear);
+// outputs per workgroup and staged span of sdsp_arb_kernel for these sizes, computed once per plan; 0: the line of one output does
+// not fit (no plan within the documented limits)
+uint32_t arb_block_out(int precision, int complex_in, int linear, uint32_t phases, uint32_t taps, uint64_t max_step);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
