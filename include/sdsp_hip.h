@@ -1241,6 +1241,104 @@ typedef struct {
 } sdsp_hip_arb_plan_info;
 int sdsp_hip_arb_plan_get_info(const sdsp_hip_arb_plan *plan, sdsp_hip_arb_plan_info *info);
 
+/* ------------------------------------------------------------------ CIC decimator banks for integer sample streams */
+
+/*
+ * Cascaded integrator-comb (Hogenauer) decimator bank: every channel, a stream of 16- or 32-bit integer
+ * samples, real or interleaved I/Q, goes through N integrators at the input rate, keeps every R-th sample, and through N combs of
+ * differential delay M at the output rate.  No multiplies, no coefficients, exact in modular integer arithmetic: the contract is
+ * bit-exact for every input.  The channel count is given per call, as in sdsp_hip_arb_process.
+ * Parameters: order 1 <= N <= 8, decimation 2 <= R <= 16384, delay M in {1, 2}, hist = N M R <= SDSP_HIP_CIC_MAX_HISTORY.
+ * in_bits is the number of significant bits of a sample, 2 .. 16 for I16 and 2 .. 32 for I32; growth = bit_length((R M)^N - 1) in
+ * exact integers (sdsp_hip_cic_growth).  The register width is W = 32 if in_bits + growth <= 32, else 64; in_bits + growth > 64 is
+ * SDSP_HIP_ERR_UNSUPPORTED.
+ * `position` is the number of samples earlier calls consumed.  A call takes any S < 2^31 samples per channel, not only multiples
+ * of R, and writes n_out = floor((position + S) / R) - floor(position / R) outputs per channel (sdsp_hip_cic_out_samples): one at
+ * each stream index n with n mod R == R - 1.
+ * Value, the bit-level definition: all registers are W-bit two's complement and wrap, and are zero at the start of the stream.
+ *   - for each input sample (sign-extended to W bits), in cascade order, integrator s adds the value in front of it to its register
+ *     and passes the sum on.
+ *   - at a due index, comb s outputs (its input - its input M outputs earlier), each difference wrapped.
+ *   - the last comb's value, sign-extended, is y.  This holds for any input values, also ones wider than in_bits: the definition
+ *     is modular.  It equals the FIR form, boxcar(R M) convolved N times (sdsp_hip_cic_taps) applied mod 2^W, so an output depends
+ *     on the N (R M - 1) + 1 <= hist newest inputs only.
+ *   - OUT_INT writes y as int32 when W = 32 and as int64 when W = 64.  OUT_F32 writes (float)((double)y * scale), each conversion
+ *     and the product rounded to nearest even; `scale` is the plan's, and 1 / (double)(R M)^N (sdsp_hip_cic_unity_scale) gives
+ *     unity gain at DC.
+ *   - COMPLEX input (interleaved I/Q, one pair is one element): the two planes independently by the same steps; the outputs are
+ *     interleaved pairs likewise.
+ *   - history: hist elements of the input kind and type per channel, state[c hist + j] = x_c[-1 - j] (newest first); read at
+ *     entry, written at exit (also when n_out = 0); NULL = zero history, final history dropped.
+ *   - any split of a stream into calls gives the same bits when the caller advances `position` (empty calls, calls shorter than
+ *     hist and calls without an output included); `position` and `position + k R` give the same bits.
+ *   - strides count elements.  `in` is never written; nothing past each row's n_out outputs is.  Pointers need only element
+ *     alignment (2 bytes for I16 real).
+ */
+#define SDSP_HIP_CIC_REAL 0
+#define SDSP_HIP_CIC_COMPLEX 1
+#define SDSP_HIP_CIC_I16 0
+#define SDSP_HIP_CIC_I32 1
+#define SDSP_HIP_CIC_OUT_INT 0
+#define SDSP_HIP_CIC_OUT_F32 1
+#define SDSP_HIP_CIC_MAX_ORDER 8
+#define SDSP_HIP_CIC_MAX_DOWN 16384
+#define SDSP_HIP_CIC_MAX_HISTORY 65536
+typedef struct sdsp_hip_cic_plan sdsp_hip_cic_plan;
+/* The four helpers below are host only and need no device.  order outside [1, 8], down outside [2, 16384], delay outside {1, 2} or
+ * order * delay * down > SDSP_HIP_CIC_MAX_HISTORY: SDSP_HIP_ERR_INVALID_SIZE; a null output pointer: SDSP_HIP_ERR_INVALID_ARG. */
+/* bits = bit_length((down * delay)^order - 1), up to 104 */
+int sdsp_hip_cic_growth(uint32_t order, uint32_t down, uint32_t delay, uint32_t *bits);
+/* n_out of one call; position may be any 64-bit value.  down outside [2, 16384] or samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE */
+int sdsp_hip_cic_out_samples(uint32_t down, uint64_t position, uint64_t samples, uint64_t *n_out);
+/* scale = 1.0 / (double)(down * delay)^order, the integer converted with one rounding */
+int sdsp_hip_cic_unity_scale(uint32_t order, uint32_t down, uint32_t delay, double *scale);
+/* h: the order * (down * delay - 1) + 1 coefficients of boxcar(down * delay) convolved `order` times, each reduced mod 2^64 */
+int sdsp_hip_cic_taps(uint32_t order, uint32_t down, uint32_t delay, uint64_t *h);
+/* Errors: the sizes above: SDSP_HIP_ERR_INVALID_SIZE; in_bits outside 2 .. 16 (I16) or 2 .. 32 (I32): SDSP_HIP_ERR_INVALID_SIZE; a
+ * null pointer, an unknown input type, input kind or output kind, a scale that is not finite: SDSP_HIP_ERR_INVALID_ARG; in_bits +
+ * growth > 64: SDSP_HIP_ERR_UNSUPPORTED, the message names in_bits, growth and their sum; no device: SDSP_HIP_ERR_NO_DEVICE.
+ * `scale` is used by OUT_F32 only. */
+int sdsp_hip_cic_plan_create(sdsp_hip_cic_plan **plan, uint32_t order, uint32_t down, uint32_t delay, int in_type, uint32_t in_bits,
+                             int input_kind, int out_kind, double scale, int device);
+int sdsp_hip_cic_plan_destroy(sdsp_hip_cic_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples) elements of the input kind and type.  out: DEVICE pointer, channel
+ * c = out[c out_stride .. + n_out) elements of the output kind (real or pairs of int32 / int64 / float).  state: DEVICE pointer
+ * or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one call per plan in flight.  Errors: samples >= 2^31:
+ * SDSP_HIP_ERR_INVALID_SIZE; null plan, in or out, in_stride < samples or out_stride < n_out with more than one channel,
+ * overlapping in and out ranges, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG; a grid that does not fit one launch:
+ * SDSP_HIP_ERR_UNSUPPORTED.  channels == 0 or samples == 0: nothing to do.
+ */
+int sdsp_hip_cic_process(sdsp_hip_cic_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                         uint64_t samples, uint64_t position, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_cic_process_host(sdsp_hip_cic_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, uint64_t position, void *host_state);
+/* bytes of a state buffer for `channels` channels: hist * channels * the input element size */
+int sdsp_hip_cic_state_bytes(const sdsp_hip_cic_plan *plan, uint64_t channels, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_cic_kernel, the fused form (integrators as workgroup scans chunk by
+ * chunk, combs in LDS); 1 = sdsp_cic_plain_kernel, one output per thread as the direct sum of h[k] x[n - k] mod 2^W over global
+ * memory (the cross-check; it shares no logic with the scan). */
+int sdsp_hip_cic_plan_set_variant(sdsp_hip_cic_plan *plan, int variant);
+/* chunks of input per workgroup of the fused kernel: 0 = automatic, else exactly `chunks` (< 2^20).  The
+ * bits do not depend on it. */
+int sdsp_hip_cic_plan_set_segment(sdsp_hip_cic_plan *plan, uint32_t chunks);
+/* kernel launches of one process call with a state buffer: the decimating kernel when n_out > 0, and one for the new history;
+ * 0 for samples == 0 */
+int sdsp_hip_cic_plan_launches(const sdsp_hip_cic_plan *plan, uint64_t position, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t order, down, delay; /* N, R, M */
+    uint32_t hist;               /* N M R */
+    uint32_t in_bits, growth;    /* growth = bit_length((R M)^N - 1) */
+    uint32_t reg_bits;           /* W: 32 or 64 */
+    uint32_t chunk;              /* input elements one workgroup of sdsp_cic_kernel scans per pass */
+    uint32_t segment;            /* sdsp_hip_cic_plan_set_segment's value, 0 = automatic */
+    int in_type, input_kind, out_kind, device;
+    double scale;
+    char kernel[64];             /* the kernel the plan's variant runs */
+} sdsp_hip_cic_plan_info;
+int sdsp_hip_cic_plan_get_info(const sdsp_hip_cic_plan *plan, sdsp_hip_cic_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ the library or without a HIP device raises (there is no CPU path here).
 from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP, IIR_HP, IIR_BP, FILTER_NONE,
                    FILTER_LOW_PASS, FILTER_HIGH_PASS, FILTER_BAND_PASS, FILTER_BAND_STOP, FIR_DIRECT, FIR_FFT, PAD_NONE, PAD_ODD, PAD_EVEN,
                    PAD_CONSTANT, DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR, SCALING_DENSITY, SCALING_SPECTRUM, CSD_CROSS, CSD_COHERENCE, PFB_REAL, PFB_COMPLEX,
-                   PFB_PHASE_FRAME, PFB_PHASE_TIME, DDC_REAL, DDC_COMPLEX, ARB_REAL, ARB_COMPLEX, ARB_NEAREST, ARB_LINEAR, DUC_REAL, DUC_COMPLEX,
+                   PFB_PHASE_FRAME, PFB_PHASE_TIME, DDC_REAL, DDC_COMPLEX, ARB_REAL, ARB_COMPLEX, ARB_NEAREST, ARB_LINEAR, CIC_REAL, CIC_COMPLEX, CIC_I16, CIC_I32, CIC_OUT_INT, CIC_OUT_F32, DUC_REAL, DUC_COMPLEX,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -23,6 +23,7 @@ from .pfb import pfb_bank, pfb_prototype
 from .pfb_synth import pfb_synthesis_bank, pfb_dual_prototype
 from .ddc import ddc_bank, ddc_phase_word
 from .arb_resample import arb_resampler, arb_step
+from .cic import cic_decimator, cic_growth, cic_unity_scale, cic_taps
 from .duc import duc_bank
 
 

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -513,6 +513,15 @@ struct sdsp_hip_arb_plan {
     uint64_t max_step = 0;
     int kind = 0, interp = 0, precision = 0, device = 0, variant = 0;
     void *table = nullptr; // [phase][tap] values H (nearest) or interleaved pairs (H, Dt) (linear), plan precision
+};
+
+struct sdsp_hip_cic_plan {
+    uint32_t order = 0, down = 0, delay = 0, hist = 0; // hist = order * delay * down
+    uint32_t in_bits = 0, growth = 0, reg_bits = 0;
+    uint32_t segment = 0;                              // chunks per workgroup of sdsp_cic_kernel, 0 = automatic
+    int in_type = 0, kind = 0, out_kind = 0, device = 0, variant = 0;
+    double scale = 0.0;
+    uint64_t *taps = nullptr; // boxcar(down * delay)^order mod 2^64, for the plain variant
 };
 
 struct sdsp_hip_filtfilt_plan {
@@ -4932,6 +4941,232 @@ int sdsp_hip_arb_process_host(sdsp_hip_arb_plan *p, const void *host_in, uint64_
     int rc = st.in();
     if (!rc)
         rc = arb_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, step, time, outs, st.dev[2], nullptr);
+    return st.out(rc);
+}
+
+// ------------------------------------------------------------------ CIC decimator banks (cic.hip)
+
+namespace
+{
+uint64_t cic_in_esize(const sdsp_hip_cic_plan *p)
+{
+    return (p->in_type == SDSP_HIP_CIC_I32 ? 4u : 2u) * (p->kind == SDSP_HIP_CIC_COMPLEX ? 2u : 1u);
+}
+uint64_t cic_out_esize(const sdsp_hip_cic_plan *p)
+{
+    return (p->out_kind == SDSP_HIP_CIC_OUT_INT && p->reg_bits == 64 ? 8u : 4u) * (p->kind == SDSP_HIP_CIC_COMPLEX ? 2u : 1u);
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int cic_check(const sdsp_hip_cic_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride, uint64_t channels,
+              uint64_t samples, uint64_t position, uint64_t *outs)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (int rc = sdsp_hip_cic_out_samples(p->down, position, samples, outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || (*outs && !out))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < *outs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= the call's outputs per channel");
+    return SDSP_HIP_OK;
+}
+
+int cic_run(sdsp_hip_cic_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels, uint64_t samples,
+            uint64_t position, uint64_t outs, void *state, hipStream_t stream)
+{
+    if (outs) {
+        cic_args a{};
+        a.in = in;
+        a.out = out;
+        a.state = state;
+        a.taps = p->taps;
+        a.channels = channels;
+        a.samples = samples;
+        a.in_stride = in_stride;
+        a.out_stride = out_stride;
+        a.position = position;
+        a.n_out = outs;
+        a.order = p->order;
+        a.down = p->down;
+        a.delay = p->delay;
+        a.segment = p->segment;
+        a.in32 = p->in_type == SDSP_HIP_CIC_I32;
+        a.complex_in = p->kind == SDSP_HIP_CIC_COMPLEX;
+        a.reg64 = p->reg_bits == 64;
+        a.out_f32 = p->out_kind == SDSP_HIP_CIC_OUT_F32;
+        a.scale = p->scale;
+        if (int rc = launch_cic(a, p->variant, stream))
+            return rc;
+    }
+    // behind the decimating kernel: it reads the old history.  Also when the call made no output.  Integer elements of 4 and 8
+    // bytes move as the f32 ones do
+    return carry_history(SDSP_HIP_F32, static_cast<uint32_t>(cic_in_esize(p)), in, in_stride, state, channels, samples, p->hist, stream,
+                         "cic");
+}
+} // namespace
+
+int sdsp_hip_cic_plan_create(sdsp_hip_cic_plan **out, uint32_t order, uint32_t down, uint32_t delay, int in_type, uint32_t in_bits,
+                             int input_kind, int out_kind, double scale, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    uint32_t growth = 0;
+    if (int rc = sdsp_hip_cic_growth(order, down, delay, &growth)) // the size checks
+        return rc;
+    if (in_type != SDSP_HIP_CIC_I16 && in_type != SDSP_HIP_CIC_I32)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_type must be SDSP_HIP_CIC_I16 or SDSP_HIP_CIC_I32");
+    if (input_kind != SDSP_HIP_CIC_REAL && input_kind != SDSP_HIP_CIC_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input_kind must be SDSP_HIP_CIC_REAL or SDSP_HIP_CIC_COMPLEX");
+    if (out_kind != SDSP_HIP_CIC_OUT_INT && out_kind != SDSP_HIP_CIC_OUT_F32)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "out_kind must be SDSP_HIP_CIC_OUT_INT or SDSP_HIP_CIC_OUT_F32");
+    if (in_bits < 2 || in_bits > (in_type == SDSP_HIP_CIC_I32 ? 32u : 16u))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "in_bits must be in [2, 16] for I16 and [2, 32] for I32");
+    if (!std::isfinite(scale))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scale must be finite");
+    if (in_bits + growth > 64)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "cic plan: in_bits " + std::to_string(in_bits) + " + growth " + std::to_string(growth) + " = " +
+                                                  std::to_string(in_bits + growth) + " bits exceed the 64-bit registers");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_cic_plan();
+    p->order = order;
+    p->down = down;
+    p->delay = delay;
+    p->hist = order * delay * down;
+    p->in_bits = in_bits;
+    p->growth = growth;
+    p->reg_bits = in_bits + growth <= 32 ? 32 : 64;
+    p->in_type = in_type;
+    p->kind = input_kind;
+    p->out_kind = out_kind;
+    p->scale = scale;
+    p->device = device;
+    std::vector<uint64_t> h(static_cast<size_t>(order) * (down * delay - 1) + 1);
+    sdsp_hip_cic_taps(order, down, delay, h.data());
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->taps), h.size() * sizeof(uint64_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(p->taps, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        sdsp_hip_cic_plan_destroy(p);
+        return plan_fail(e, "cic");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_plan_destroy(sdsp_hip_cic_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->taps);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_state_bytes(const sdsp_hip_cic_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * cic_in_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_plan_set_variant(sdsp_hip_cic_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_plan_set_segment(sdsp_hip_cic_plan *p, uint32_t chunks)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (chunks >= (1u << 20))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "chunks per segment must be below 2^20");
+    p->segment = chunks;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_plan_launches(const sdsp_hip_cic_plan *p, uint64_t position, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t outs = 0;
+    if (int rc = sdsp_hip_cic_out_samples(p->down, position, samples, &outs))
+        return rc;
+    if (samples)
+        *launches = (outs ? 1 : 0) + 1;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_plan_get_info(const sdsp_hip_cic_plan *p, sdsp_hip_cic_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->order = p->order;
+    info->down = p->down;
+    info->delay = p->delay;
+    info->hist = p->hist;
+    info->in_bits = p->in_bits;
+    info->growth = p->growth;
+    info->reg_bits = p->reg_bits;
+    info->chunk = cic_chunk();
+    info->segment = p->segment;
+    info->in_type = p->in_type;
+    info->input_kind = p->kind;
+    info->out_kind = p->out_kind;
+    info->device = p->device;
+    info->scale = p->scale;
+    std::strncpy(info->kernel, cic_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_process(sdsp_hip_cic_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                         uint64_t samples, uint64_t position, void *state, void *stream)
+{
+    uint64_t outs = 0;
+    if (int rc = cic_check(p, in, in_stride, out, out_stride, channels, samples, position, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t ies = cic_in_esize(p), oes = cic_out_esize(p);
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + samples) * ies, ies, outs ? out : nullptr,
+                                    ((channels - 1) * out_stride + outs) * oes, oes, state, ies,
+                                    "in and out ranges overlap (the decimator runs out of place)"))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    return cic_run(p, in, in_stride, out, out_stride, channels, samples, position, outs, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_cic_process_host(sdsp_hip_cic_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                              uint64_t channels, uint64_t samples, uint64_t position, void *host_state)
+{
+    uint64_t outs = 0;
+    if (int rc = cic_check(p, host_in, in_stride, host_out, out_stride, channels, samples, position, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * cic_in_esize(p);
+    const size_t out_bytes = ((channels - 1) * out_stride + outs) * cic_out_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_cic_state_bytes(p, channels, &state_bytes);
+    host_stage st("cic", { { host_in, in_bytes, false }, { outs ? host_out : nullptr, out_bytes, true },
+                       { host_state, state_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = cic_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, position, outs, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

@@ -787,6 +787,99 @@ int sdsp_hip_arb_tables(uint32_t phases, uint32_t taps, const double *h, double 
         }
     return SDSP_HIP_OK;
 }
+// CIC decimator banks: 1 <= N <= 8, 2 <= R <= 16384, M in {1, 2}, N M R <= SDSP_HIP_CIC_MAX_HISTORY
+static int cic_check_shape(uint32_t order, uint32_t down, uint32_t delay)
+{
+    if (order == 0 || order > SDSP_HIP_CIC_MAX_ORDER)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "order must be in [1, SDSP_HIP_CIC_MAX_ORDER]");
+    if (down < 2 || down > SDSP_HIP_CIC_MAX_DOWN)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "down must be in [2, SDSP_HIP_CIC_MAX_DOWN]");
+    if (delay != 1 && delay != 2)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "delay must be 1 or 2");
+    if (static_cast<uint64_t>(order) * down * delay > SDSP_HIP_CIC_MAX_HISTORY)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "order * delay * down must be <= SDSP_HIP_CIC_MAX_HISTORY");
+    return SDSP_HIP_OK;
+}
+// (R M)^N in exact integers: at most 8192^8 = 2^104 within the history limit
+static unsigned __int128 cic_gain(uint32_t order, uint32_t down, uint32_t delay)
+{
+    unsigned __int128 g = 1;
+    for (uint32_t s = 0; s < order; s++)
+        g *= static_cast<uint64_t>(down) * delay;
+    return g;
+}
+int sdsp_hip_cic_growth(uint32_t order, uint32_t down, uint32_t delay, uint32_t *bits)
+{
+    if (!bits)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *bits = 0;
+    if (int rc = cic_check_shape(order, down, delay))
+        return rc;
+    uint32_t b = 0;
+    for (unsigned __int128 v = cic_gain(order, down, delay) - 1; v; v >>= 1)
+        b++;
+    *bits = b;
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_cic_out_samples(uint32_t down, uint64_t position, uint64_t samples, uint64_t *n_out)
+{
+    if (!n_out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *n_out = 0;
+    if (down < 2 || down > SDSP_HIP_CIC_MAX_DOWN)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "down must be in [2, SDSP_HIP_CIC_MAX_DOWN]");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    *n_out = (position % down + samples) / down; // floor((position + S) / R) - floor(position / R) without the sum's overflow
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_cic_unity_scale(uint32_t order, uint32_t down, uint32_t delay, double *scale)
+{
+    if (!scale)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *scale = 0.0;
+    if (int rc = cic_check_shape(order, down, delay))
+        return rc;
+    const unsigned __int128 g = cic_gain(order, down, delay);
+    // (double)g with one rounding: g has at most 105 bits; its top 64 bits, with a sticky bit for the rest, round to 53 bits as the
+    // whole does, and the power-of-two scaling back is exact
+    uint32_t shift = 0;
+    unsigned __int128 top = g;
+    bool sticky = false;
+    while (top >> 64) {
+        sticky = sticky || (top & 1);
+        top >>= 1;
+        shift++;
+    }
+    uint64_t t = static_cast<uint64_t>(top);
+    if (sticky)
+        t |= 1; // shift > 0 means t has 64 significant bits: bit 0 lies below the rounding position and its half-way bit
+    *scale = 1.0 / std::ldexp(static_cast<double>(t), static_cast<int>(shift));
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_cic_taps(uint32_t order, uint32_t down, uint32_t delay, uint64_t *h)
+{
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    if (int rc = cic_check_shape(order, down, delay))
+        return rc;
+    const uint64_t box = static_cast<uint64_t>(down) * delay;
+    uint64_t len = 1;
+    h[0] = 1;
+    std::vector<uint64_t> sum; // running sums of the stage before, sum[k] = h[0] + .. + h[k - 1], mod 2^64
+    for (uint32_t s = 0; s < order; s++) {
+        sum.assign(len + 1, 0);
+        for (uint64_t k = 0; k < len; k++)
+            sum[k + 1] = sum[k] + h[k];
+        const uint64_t next = len + box - 1;
+        for (uint64_t k = 0; k < next; k++) { // h'[k] = h[k - box + 1] + .. + h[k] over the indices that exist
+            const uint64_t hi = k + 1 < len ? k + 1 : len, lo = k + 1 > box ? k + 1 - box : 0;
+            h[k] = sum[hi] - sum[lo];
+        }
+        len = next;
+    }
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_stft_window(int kind, uint32_t n, double *w)
 {
     if (!w)

@@ -336,6 +336,23 @@ int arb_prepare(int precision, int complex_in, int linear);
 // outputs per workgroup and staged span of sdsp_arb_kernel for these sizes, computed once per plan; 0: the line of one output does
 // not fit (no plan within the documented limits)
 uint32_t arb_block_out(int precision, int complex_in, int linear, uint32_t phases, uint32_t taps, uint64_t max_step);
+// CIC decimator banks (cic.hip): the one launch of a call with n_out > 0, in front of carry_history
+struct cic_args {
+    const void *in;
+    void *out;
+    const void *state; // nullable; channels x hist elements of the input kind and type, newest first
+    const void *taps;  // device, order * (down * delay - 1) + 1 values of 64 bits (variant 1 only)
+    uint64_t channels, samples, in_stride, out_stride;
+    uint64_t position, n_out; // n_out in [1, 2^31): sdsp_hip_cic_out_samples of down, position, samples
+    uint32_t order, down, delay;
+    uint32_t segment;  // chunks per workgroup of the fused kernel, 0 = automatic
+    int in32, complex_in, reg64, out_f32;
+    double scale;
+};
+int launch_cic(const cic_args &a, int variant, void *stream);
+const char *cic_kernel_for(int variant);
+// input elements one workgroup of sdsp_cic_kernel scans per pass
+uint32_t cic_chunk();
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {

@@ -114,6 +114,8 @@ int seed(void *out, uint64_t out_stride, void *state, uint64_t channels, uint64_
 template <typename F> int with_element(int precision, uint32_t elem_bytes, F f)
 {
     const bool f64 = precision == SDSP_HIP_F64;
+    if (elem_bytes == 2u) // one 16-bit integer sample (the CIC banks' real I16 rows); their wider elements move as the f32 ones do
+        return f(uint16_t());
     if (elem_bytes == (f64 ? 8u : 4u))
         return f64 ? f(double()) : f(float());
     if (elem_bytes == (f64 ? 16u : 8u))
