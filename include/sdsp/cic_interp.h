@@ -1,0 +1,172 @@
+// sdsp/cic_interp.h -- CIC (Hogenauer) interpolator bank for integer sample streams on the MI355X engine (sdsp_hip_cic_interp_*,
+// DESIGN.md section 5.23).
+//
+// Every channel, a stream of 16- or 32-bit integer samples (real, or interleaved I/Q), goes through `order` combs of differential
+// delay `delay`, is zero-stuffed by `up`, and goes through `order` integrators: no multiplies, exact in modular arithmetic,
+// bit-exact for every input.  Mirrors sdsp::cic_decimator_bank (sdsp/cic.h): RAII plan and device-resident per-channel history,
+// process() on device pointers, process_host() for host buffers; a call of S samples writes up * S outputs, and calls of any length
+// chain into one stream (there is no stream position: every call starts on an input boundary).  in_t is std::int16_t or
+// std::int32_t; out_t is std::int32_t (32-bit registers), std::int64_t (64-bit registers) or float, and the constructor checks
+// that it matches the plan.  No reference counterpart: pinned to the serial Hogenauer form.  There is no CPU path.
+#ifndef SDSP_MI355X_CIC_INTERP_H
+#define SDSP_MI355X_CIC_INTERP_H
+
+#include <cstddef>
+#include <cstdint>
+#include <type_traits>
+#include <vector>
+
+#include "detail/hip_runtime.h"
+
+namespace sdsp
+{
+// bit_length(up^(order-1) * delay^order - 1): the bits the registers need above the input's
+inline std::uint32_t cic_interp_growth(std::uint32_t order, std::uint32_t up, std::uint32_t delay = 1)
+{
+    std::uint32_t b = 0;
+    detail::check(sdsp_hip_cic_interp_growth(order, up, delay, &b));
+    return b;
+}
+// 1 / (double)(up^(order-1) * delay^order): unity gain at DC
+inline double cic_interp_unity_scale(std::uint32_t order, std::uint32_t up, std::uint32_t delay = 1)
+{
+    double s = 0.0;
+    detail::check(sdsp_hip_cic_interp_unity_scale(order, up, delay, &s));
+    return s;
+}
+
+template <typename in_t = std::int16_t, typename out_t = std::int64_t> class cic_interpolator_bank {
+    static_assert(std::is_same<in_t, std::int16_t>::value || std::is_same<in_t, std::int32_t>::value, "in_t: int16_t or int32_t");
+    static_assert(std::is_same<out_t, std::int32_t>::value || std::is_same<out_t, std::int64_t>::value || std::is_same<out_t, float>::value,
+                  "out_t: int32_t, int64_t or float");
+
+public:
+    // in_bits: significant bits of a sample (0: the width of in_t); complex_input: rows of interleaved I/Q pairs (one pair is one
+    // sample); scale (float output only): 0 means unity gain at DC.  Throws when out_t is an integer of another width than the
+    // registers in_bits + growth ask for.
+    cic_interpolator_bank(std::uint32_t order, std::uint32_t up, std::uint32_t delay, std::uint64_t channels, bool complex_input = false,
+                          std::uint32_t in_bits = 0, double scale = 0.0, int device = 0)
+        : m_order(order), m_up(up), m_delay(delay), m_in_bits(in_bits ? in_bits : static_cast<std::uint32_t>(8 * sizeof(in_t))),
+          m_channels(channels), m_complex(complex_input), m_device(device)
+    {
+        const std::uint32_t bits = m_in_bits + cic_interp_growth(order, up, delay);
+        const bool is_float = std::is_same<out_t, float>::value;
+        if (!is_float && bits <= 64 && (bits <= 32 ? 4u : 8u) != sizeof(out_t))
+            throw hip_error(SDSP_HIP_ERR_INVALID_ARG, "sdsp_hip: out_t must be int32_t for 32-bit registers and int64_t for 64-bit ones");
+        m_scale = is_float ? (scale != 0.0 ? scale : cic_interp_unity_scale(order, up, delay)) : 1.0;
+        m_hist = order * delay;
+    }
+    ~cic_interpolator_bank()
+    {
+        if (m_plan)
+            sdsp_hip_cic_interp_plan_destroy(m_plan);
+        if (m_state)
+            sdsp_hip_free(m_state, m_device);
+    }
+    cic_interpolator_bank(const cic_interpolator_bank &) = delete;
+    cic_interpolator_bank &operator=(const cic_interpolator_bank &) = delete;
+
+    // forget the history
+    void reset()
+    {
+        if (m_state)
+            zero_state();
+    }
+
+    // outputs per channel of a call of `samples`
+    std::uint64_t out_samples(std::uint64_t samples) const noexcept { return samples * m_up; }
+
+    // device pointers (channel-major rows of samples or I/Q pairs), strides in elements, asynchronous on `stream`; continues every
+    // channel's stream and returns the outputs written per channel
+    std::uint64_t process(const in_t *device_in, std::uint64_t in_stride, out_t *device_out, std::uint64_t out_stride, std::uint64_t samples,
+                          void *stream = nullptr)
+    {
+        ensure_plan();
+        ensure_state();
+        detail::check(sdsp_hip_cic_interp_process(m_plan, device_in, in_stride, device_out, out_stride, m_channels, samples, m_state, stream));
+        return out_samples(samples);
+    }
+    // host pointers: in = channels x samples elements, out = channels x out_samples(samples) elements, both contiguous
+    std::uint64_t process_host(const in_t *host_in, out_t *host_out, std::uint64_t samples)
+    {
+        ensure_plan();
+        ensure_state();
+        if (samples == 0)
+            return 0;
+        const std::uint64_t n = out_samples(samples);
+        const std::size_t width = m_complex ? 2u : 1u;
+        const std::size_t in_bytes = static_cast<std::size_t>(m_channels * samples) * width * sizeof(in_t);
+        const std::size_t out_bytes = static_cast<std::size_t>(m_channels * n) * width * sizeof(out_t);
+        void *di = nullptr, *dout = nullptr;
+        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
+        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
+        if (!rc)
+            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
+        if (!rc)
+            rc = sdsp_hip_cic_interp_process(m_plan, di, samples, dout, n, m_channels, samples, m_state, nullptr);
+        if (!rc)
+            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
+        sdsp_hip_free(di, m_device);
+        if (dout)
+            sdsp_hip_free(dout, m_device);
+        detail::check(rc);
+        return n;
+    }
+    std::uint64_t channels() const noexcept { return m_channels; }
+    std::uint32_t history() const noexcept { return m_hist; }
+    double scale() const noexcept { return m_scale; }
+    // 0 = the scan kernel, 1 = the plain cross-check kernel
+    void set_variant(int variant)
+    {
+        ensure_plan();
+        detail::check(sdsp_hip_cic_interp_plan_set_variant(m_plan, variant));
+    }
+    // chunks of output per workgroup of the scan kernel, 0 = automatic
+    void set_segment(std::uint32_t chunks)
+    {
+        ensure_plan();
+        detail::check(sdsp_hip_cic_interp_plan_set_segment(m_plan, chunks));
+    }
+    sdsp_hip_cic_interp_plan_info info()
+    {
+        ensure_plan();
+        sdsp_hip_cic_interp_plan_info i{};
+        detail::check(sdsp_hip_cic_interp_plan_get_info(m_plan, &i));
+        return i;
+    }
+
+private:
+    void ensure_plan()
+    {
+        if (!m_plan)
+            detail::check(sdsp_hip_cic_interp_plan_create(&m_plan, m_order, m_up, m_delay, sizeof(in_t) == 4 ? SDSP_HIP_CIC_I32 : SDSP_HIP_CIC_I16,
+                                                          m_in_bits, m_complex ? SDSP_HIP_CIC_COMPLEX : SDSP_HIP_CIC_REAL,
+                                                          std::is_same<out_t, float>::value ? SDSP_HIP_CIC_OUT_F32 : SDSP_HIP_CIC_OUT_INT,
+                                                          m_scale, m_device));
+    }
+    void zero_state()
+    {
+        const std::size_t bytes = static_cast<std::size_t>(m_hist) * static_cast<std::size_t>(m_channels) * (m_complex ? 2u : 1u) * sizeof(in_t);
+        if (!m_state)
+            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
+        const std::vector<unsigned char> host(bytes, 0);
+        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), bytes, m_device));
+    }
+    void ensure_state()
+    {
+        if (!m_state)
+            zero_state();
+    }
+
+    std::uint32_t m_order, m_up, m_delay, m_in_bits;
+    std::uint64_t m_channels;
+    bool m_complex;
+    int m_device;
+    std::uint32_t m_hist{ 0 };
+    double m_scale{ 1.0 };
+    sdsp_hip_cic_interp_plan *m_plan{ nullptr };
+    void *m_state{ nullptr };
+};
+} // namespace sdsp
+
+#endif // SDSP_MI355X_CIC_INTERP_H

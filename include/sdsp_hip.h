@@ -1339,6 +1339,86 @@ typedef struct {
 } sdsp_hip_cic_plan_info;
 int sdsp_hip_cic_plan_get_info(const sdsp_hip_cic_plan *plan, sdsp_hip_cic_plan_info *info);
 
+/* ------------------------------------------------------------------ CIC interpolator banks for integer sample streams */
+
+/*
+ * Cascaded integrator-comb (Hogenauer) interpolator bank, the transmit-side mirror of the decimator above:
+ * every channel, a stream of 16- or 32-bit integer samples, real or interleaved I/Q, goes through N combs of differential delay M
+ * at the input rate, is zero-stuffed by R, and goes through N integrators at the output rate.  No multiplies, no coefficients,
+ * exact in modular integer arithmetic: the contract is bit-exact for every input.  Kinds, types and output kinds are the
+ * decimator's SDSP_HIP_CIC_* constants; the channel count is given per call.
+ * Parameters: order 1 <= N <= 8, up-sampling 2 <= R <= 16384, delay M in {1, 2}, N M R <= SDSP_HIP_CIC_MAX_HISTORY.
+ * in_bits is the number of significant bits of a sample, 2 .. 16 for I16 and 2 .. 32 for I32; growth = bit_length(R^(N-1) M^N - 1)
+ * in exact integers (sdsp_hip_cic_interp_growth).  The register width is W = 32 if in_bits + growth <= 32, else 64; in_bits +
+ * growth > 64 is SDSP_HIP_ERR_UNSUPPORTED.
+ * A call takes S samples per channel and writes exactly R S outputs per channel, R S < 2^31.  There is no stream position: the
+ * filter is time-invariant at the input rate, and every call starts on an input boundary.
+ * Value, the bit-level definition: all registers are W-bit two's complement and wrap, and are zero at the start of the stream.
+ *   - combs at the input rate: c_0 = x (sign-extended to W bits), c_k[m] = c_{k-1}[m] - c_{k-1}[m - M], k = 1 .. N.
+ *   - zero-stuffing: u[m R] = c_N[m], u[n] = 0 otherwise.
+ *   - integrators at the output rate: I_0 = u, I_k[n] = I_k[n - 1] + I_{k-1}[n] (inclusive), k = 1 .. N; y = I_N, sign-extended.
+ *     This holds for any input values, also ones wider than in_bits: the definition is modular.  It equals the polyphase FIR form
+ *     y[m R + p] = sum_j h[p + j R] x[m - j] mod 2^W with h = boxcar(R M) convolved N times (sdsp_hip_cic_taps), so an output
+ *     depends on the N M newest inputs only.  Every branch p sums to R^(N-1) M^N, the gain at DC.
+ *   - OUT_INT writes y as int32 when W = 32 and as int64 when W = 64.  OUT_F32 writes (float)((double)y * scale), each conversion
+ *     and the product rounded to nearest even; `scale` is the plan's, and sdsp_hip_cic_interp_unity_scale gives unity gain at DC.
+ *   - COMPLEX input (interleaved I/Q, one pair is one element): the two planes independently by the same steps; the outputs are
+ *     interleaved pairs likewise.
+ *   - history: N M elements of the input kind and type per channel, state[c N M + j] = x_c[-1 - j] (newest first); read at entry,
+ *     written at exit (also by calls shorter than N M); NULL = zero history, final history dropped.
+ *   - any split of a stream into calls gives the same bits (empty and one-sample calls included).
+ *   - strides count elements.  `in` is never written; nothing past each row's R S outputs is.  Pointers need only element
+ *     alignment (2 bytes for I16 real).
+ */
+typedef struct sdsp_hip_cic_interp_plan sdsp_hip_cic_interp_plan;
+/* The two helpers below are host only and need no device.  order outside [1, 8], up outside [2, 16384], delay outside {1, 2} or
+ * order * delay * up > SDSP_HIP_CIC_MAX_HISTORY: SDSP_HIP_ERR_INVALID_SIZE; a null output pointer: SDSP_HIP_ERR_INVALID_ARG. */
+/* bits = bit_length(up^(order-1) * delay^order - 1), up to 92 */
+int sdsp_hip_cic_interp_growth(uint32_t order, uint32_t up, uint32_t delay, uint32_t *bits);
+/* scale = 1.0 / (double)(up^(order-1) * delay^order), the integer converted with one rounding */
+int sdsp_hip_cic_interp_unity_scale(uint32_t order, uint32_t up, uint32_t delay, double *scale);
+/* Errors: as sdsp_hip_cic_plan_create, with `up` in the place of `down` and the interpolator's growth. */
+int sdsp_hip_cic_interp_plan_create(sdsp_hip_cic_interp_plan **plan, uint32_t order, uint32_t up, uint32_t delay, int in_type,
+                                    uint32_t in_bits, int input_kind, int out_kind, double scale, int device);
+int sdsp_hip_cic_interp_plan_destroy(sdsp_hip_cic_interp_plan *plan);
+/*
+ * in: DEVICE pointer, channel c = in[c in_stride .. + samples) elements of the input kind and type.  out: DEVICE pointer, channel
+ * c = out[c out_stride .. + up * samples) elements of the output kind (real or pairs of int32 / int64 / float).  state: DEVICE
+ * pointer or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one call per plan in flight.  Errors:
+ * up * samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; null plan, in or out, in_stride < samples or out_stride < up * samples with more
+ * than one channel, overlapping in and out ranges, misaligned pointers: SDSP_HIP_ERR_INVALID_ARG; a grid that does not fit one
+ * launch: SDSP_HIP_ERR_UNSUPPORTED.  channels == 0 or samples == 0: nothing to do.
+ */
+int sdsp_hip_cic_interp_process(sdsp_hip_cic_interp_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                                uint64_t channels, uint64_t samples, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_cic_interp_process_host(sdsp_hip_cic_interp_plan *plan, const void *host_in, uint64_t in_stride, void *host_out,
+                                     uint64_t out_stride, uint64_t channels, uint64_t samples, void *host_state);
+/* bytes of a state buffer for `channels` channels: order * delay * channels * the input element size */
+int sdsp_hip_cic_interp_state_bytes(const sdsp_hip_cic_interp_plan *plan, uint64_t channels, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_cic_interp_kernel, the time-parallel form (the first integrator as a
+ * hold of comb sums, the others as workgroup scans chunk by chunk); 1 = sdsp_cic_interp_plain_kernel, one output per thread as the
+ * direct polyphase sum of h[p + j R] x[m - j] mod 2^W over global memory (the cross-check; it shares no logic with the scan). */
+int sdsp_hip_cic_interp_plan_set_variant(sdsp_hip_cic_interp_plan *plan, int variant);
+/* chunks of output per workgroup of the scan kernel: 0 = automatic, else exactly `chunks` (< 2^20).  The
+ * bits do not depend on it. */
+int sdsp_hip_cic_interp_plan_set_segment(sdsp_hip_cic_interp_plan *plan, uint32_t chunks);
+/* kernel launches of one process call with a state buffer: the interpolating kernel and one for the new history; 0 for
+ * samples == 0.  up * samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE */
+int sdsp_hip_cic_interp_plan_launches(const sdsp_hip_cic_interp_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t order, up, delay;   /* N, R, M */
+    uint32_t hist;               /* N M */
+    uint32_t in_bits, growth;    /* growth = bit_length(R^(N-1) M^N - 1) */
+    uint32_t reg_bits;           /* W: 32 or 64 */
+    uint32_t chunk;              /* output elements one workgroup of sdsp_cic_interp_kernel scans per pass */
+    uint32_t segment;            /* sdsp_hip_cic_interp_plan_set_segment's value, 0 = automatic */
+    int in_type, input_kind, out_kind, device;
+    double scale;
+    char kernel[64];             /* the kernel the plan's variant runs */
+} sdsp_hip_cic_interp_plan_info;
+int sdsp_hip_cic_interp_plan_get_info(const sdsp_hip_cic_interp_plan *plan, sdsp_hip_cic_interp_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ from .pfb_synth import pfb_synthesis_bank, pfb_dual_prototype
 from .ddc import ddc_bank, ddc_phase_word
 from .arb_resample import arb_resampler, arb_step
 from .cic import cic_decimator, cic_growth, cic_unity_scale, cic_taps
+from .cic_interp import cic_interpolator, cic_interp_growth, cic_interp_unity_scale
 from .duc import duc_bank
 
 

@@ -162,6 +162,14 @@ class CicPlanInfo(C.Structure):
     ]
 
 
+class CicInterpPlanInfo(C.Structure):
+    _fields_ = [
+        ("order", C.c_uint32), ("up", C.c_uint32), ("delay", C.c_uint32), ("hist", C.c_uint32), ("in_bits", C.c_uint32),
+        ("growth", C.c_uint32), ("reg_bits", C.c_uint32), ("chunk", C.c_uint32), ("segment", C.c_uint32), ("in_type", C.c_int),
+        ("input_kind", C.c_int), ("out_kind", C.c_int), ("device", C.c_int), ("scale", C.c_double), ("kernel", C.c_char * 64),
+    ]
+
+
 CIC_REAL, CIC_COMPLEX = 0, 1
 CIC_I16, CIC_I32 = 0, 1
 CIC_OUT_INT, CIC_OUT_F32 = 0, 1
@@ -344,6 +352,17 @@ SIGNATURES = {
     "sdsp_hip_cic_plan_set_segment": (_i, [_vp, _u32]),
     "sdsp_hip_cic_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_cic_plan_get_info": (_i, [_vp, C.POINTER(CicPlanInfo)]),
+    "sdsp_hip_cic_interp_growth": (_i, [_u32, _u32, _u32, C.POINTER(_u32)]),
+    "sdsp_hip_cic_interp_unity_scale": (_i, [_u32, _u32, _u32, C.POINTER(_d)]),
+    "sdsp_hip_cic_interp_plan_create": (_i, [_pp, _u32, _u32, _u32, _i, _u32, _i, _i, _d, _i]),
+    "sdsp_hip_cic_interp_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_cic_interp_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_cic_interp_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp]),
+    "sdsp_hip_cic_interp_state_bytes": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_cic_interp_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_cic_interp_plan_set_segment": (_i, [_vp, _u32]),
+    "sdsp_hip_cic_interp_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_cic_interp_plan_get_info": (_i, [_vp, C.POINTER(CicInterpPlanInfo)]),
     "sdsp_hip_ddc_phase_word": (_i, [_d, C.POINTER(_u32)]),
     "sdsp_hip_ddc_band_taps": (_i, [_u32, _vp, _u32, _vp]),
     "sdsp_hip_ddc_oscillator": (_i, [_vp, _vp]),

@@ -48,6 +48,7 @@ SOURCES = {
     "fir_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64: multiply then add per tap, as fir.hip
     "arb_resample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps and a + mu b: multiply then add, never an FMA
     "cic.hip": [],  # integer arithmetic mod 2^W; the one float step is a product with nothing to contract
+    "cic_interp.hip": [],  # as cic.hip
     "ddc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps and the two complex products: multiply then add, never an FMA
     "duc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: f64 taps, the complex products and the band sum never contract
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -522,6 +522,15 @@ struct sdsp_hip_cic_plan {
     int in_type = 0, kind = 0, out_kind = 0, device = 0, variant = 0;
     double scale = 0.0;
     uint64_t *taps = nullptr; // boxcar(down * delay)^order mod 2^64, for the plain variant
+};
+
+struct sdsp_hip_cic_interp_plan {
+    uint32_t order = 0, up = 0, delay = 0, hist = 0; // hist = order * delay
+    uint32_t in_bits = 0, growth = 0, reg_bits = 0;
+    uint32_t segment = 0;                            // chunks per workgroup of sdsp_cic_interp_kernel, 0 = automatic
+    int in_type = 0, kind = 0, out_kind = 0, device = 0, variant = 0;
+    double scale = 0.0;
+    uint64_t *taps = nullptr; // boxcar(up * delay)^order mod 2^64, for the plain variant
 };
 
 struct sdsp_hip_filtfilt_plan {
@@ -5167,6 +5176,236 @@ int sdsp_hip_cic_process_host(sdsp_hip_cic_plan *p, const void *host_in, uint64_
     int rc = st.in();
     if (!rc)
         rc = cic_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, position, outs, st.dev[2], nullptr);
+    return st.out(rc);
+}
+
+// ------------------------------------------------------------------ CIC interpolator banks (cic_interp.hip)
+
+namespace
+{
+uint64_t cic_interp_in_esize(const sdsp_hip_cic_interp_plan *p)
+{
+    return (p->in_type == SDSP_HIP_CIC_I32 ? 4u : 2u) * (p->kind == SDSP_HIP_CIC_COMPLEX ? 2u : 1u);
+}
+uint64_t cic_interp_out_esize(const sdsp_hip_cic_interp_plan *p)
+{
+    return (p->out_kind == SDSP_HIP_CIC_OUT_INT && p->reg_bits == 64 ? 8u : 4u) * (p->kind == SDSP_HIP_CIC_COMPLEX ? 2u : 1u);
+}
+
+// outputs per channel of a call: up * samples, below 2^31
+int cic_interp_outs(const sdsp_hip_cic_interp_plan *p, uint64_t samples, uint64_t *outs)
+{
+    *outs = 0;
+    if (samples >= (1ull << 31) || samples * p->up >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "up * samples must be below 2^31");
+    *outs = samples * p->up;
+    return SDSP_HIP_OK;
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int cic_interp_check(const sdsp_hip_cic_interp_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride,
+                     uint64_t channels, uint64_t samples, uint64_t *outs)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (int rc = cic_interp_outs(p, samples, outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if (channels > 1 && (in_stride < samples || out_stride < *outs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride must be >= samples and out_stride >= the call's outputs per channel");
+    return SDSP_HIP_OK;
+}
+
+int cic_interp_run(sdsp_hip_cic_interp_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t channels,
+                   uint64_t samples, void *state, hipStream_t stream)
+{
+    cic_interp_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = state;
+    a.taps = p->taps;
+    a.channels = channels;
+    a.samples = samples;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.order = p->order;
+    a.up = p->up;
+    a.delay = p->delay;
+    a.segment = p->segment;
+    a.in32 = p->in_type == SDSP_HIP_CIC_I32;
+    a.complex_in = p->kind == SDSP_HIP_CIC_COMPLEX;
+    a.reg64 = p->reg_bits == 64;
+    a.out_f32 = p->out_kind == SDSP_HIP_CIC_OUT_F32;
+    a.scale = p->scale;
+    if (int rc = launch_cic_interp(a, p->variant, stream))
+        return rc;
+    // behind the interpolating kernel: it reads the old history.  Also for calls shorter than the history.  Integer elements of 4
+    // and 8 bytes move as the f32 ones do
+    return carry_history(SDSP_HIP_F32, static_cast<uint32_t>(cic_interp_in_esize(p)), in, in_stride, state, channels, samples, p->hist,
+                         stream, "cic_interp");
+}
+} // namespace
+
+int sdsp_hip_cic_interp_plan_create(sdsp_hip_cic_interp_plan **out, uint32_t order, uint32_t up, uint32_t delay, int in_type,
+                                    uint32_t in_bits, int input_kind, int out_kind, double scale, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    uint32_t growth = 0;
+    if (int rc = sdsp_hip_cic_interp_growth(order, up, delay, &growth)) // the size checks
+        return rc;
+    if (in_type != SDSP_HIP_CIC_I16 && in_type != SDSP_HIP_CIC_I32)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_type must be SDSP_HIP_CIC_I16 or SDSP_HIP_CIC_I32");
+    if (input_kind != SDSP_HIP_CIC_REAL && input_kind != SDSP_HIP_CIC_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input_kind must be SDSP_HIP_CIC_REAL or SDSP_HIP_CIC_COMPLEX");
+    if (out_kind != SDSP_HIP_CIC_OUT_INT && out_kind != SDSP_HIP_CIC_OUT_F32)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "out_kind must be SDSP_HIP_CIC_OUT_INT or SDSP_HIP_CIC_OUT_F32");
+    if (in_bits < 2 || in_bits > (in_type == SDSP_HIP_CIC_I32 ? 32u : 16u))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "in_bits must be in [2, 16] for I16 and [2, 32] for I32");
+    if (!std::isfinite(scale))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scale must be finite");
+    if (in_bits + growth > 64)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "cic_interp plan: in_bits " + std::to_string(in_bits) + " + growth " + std::to_string(growth) +
+                                                  " = " + std::to_string(in_bits + growth) + " bits exceed the 64-bit registers");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_cic_interp_plan();
+    p->order = order;
+    p->up = up;
+    p->delay = delay;
+    p->hist = order * delay;
+    p->in_bits = in_bits;
+    p->growth = growth;
+    p->reg_bits = in_bits + growth <= 32 ? 32 : 64;
+    p->in_type = in_type;
+    p->kind = input_kind;
+    p->out_kind = out_kind;
+    p->scale = scale;
+    p->device = device;
+    std::vector<uint64_t> h(static_cast<size_t>(order) * (up * delay - 1) + 1);
+    sdsp_hip_cic_taps(order, up, delay, h.data());
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->taps), h.size() * sizeof(uint64_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(p->taps, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        sdsp_hip_cic_interp_plan_destroy(p);
+        return plan_fail(e, "cic_interp");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_plan_destroy(sdsp_hip_cic_interp_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->taps);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_state_bytes(const sdsp_hip_cic_interp_plan *p, uint64_t channels, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * channels * cic_interp_in_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_plan_set_variant(sdsp_hip_cic_interp_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_plan_set_segment(sdsp_hip_cic_interp_plan *p, uint32_t chunks)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (chunks >= (1u << 20))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "chunks per segment must be below 2^20");
+    p->segment = chunks;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_plan_launches(const sdsp_hip_cic_interp_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = 0;
+    uint64_t outs = 0;
+    if (int rc = cic_interp_outs(p, samples, &outs))
+        return rc;
+    if (samples)
+        *launches = 2;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_plan_get_info(const sdsp_hip_cic_interp_plan *p, sdsp_hip_cic_interp_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->order = p->order;
+    info->up = p->up;
+    info->delay = p->delay;
+    info->hist = p->hist;
+    info->in_bits = p->in_bits;
+    info->growth = p->growth;
+    info->reg_bits = p->reg_bits;
+    info->chunk = cic_interp_chunk();
+    info->segment = p->segment;
+    info->in_type = p->in_type;
+    info->input_kind = p->kind;
+    info->out_kind = p->out_kind;
+    info->device = p->device;
+    info->scale = p->scale;
+    std::strncpy(info->kernel, cic_interp_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cic_interp_process(sdsp_hip_cic_interp_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride,
+                                uint64_t channels, uint64_t samples, void *state, void *stream)
+{
+    uint64_t outs = 0;
+    if (int rc = cic_interp_check(p, in, in_stride, out, out_stride, channels, samples, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t ies = cic_interp_in_esize(p), oes = cic_interp_out_esize(p);
+    if (int rc = check_out_of_place(in, ((channels - 1) * in_stride + samples) * ies, ies, out, ((channels - 1) * out_stride + outs) * oes,
+                                    oes, state, ies, "in and out ranges overlap (the interpolator runs out of place)"))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    return cic_interp_run(p, in, in_stride, out, out_stride, channels, samples, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_cic_interp_process_host(sdsp_hip_cic_interp_plan *p, const void *host_in, uint64_t in_stride, void *host_out,
+                                     uint64_t out_stride, uint64_t channels, uint64_t samples, void *host_state)
+{
+    uint64_t outs = 0;
+    if (int rc = cic_interp_check(p, host_in, in_stride, host_out, out_stride, channels, samples, &outs))
+        return rc;
+    if (channels == 0 || samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t in_bytes = ((channels - 1) * in_stride + samples) * cic_interp_in_esize(p);
+    const size_t out_bytes = ((channels - 1) * out_stride + outs) * cic_interp_out_esize(p);
+    uint64_t state_bytes = 0;
+    sdsp_hip_cic_interp_state_bytes(p, channels, &state_bytes);
+    host_stage st("cic_interp", { { host_in, in_bytes, false }, { host_out, out_bytes, true }, { host_state, state_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = cic_interp_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

@@ -20,7 +20,7 @@
 //   sdsp_cic_plain_kernel  variant 1: one output per thread as sum_k h[k] x[n - k] mod 2^W from global memory, h = boxcar(R M)^N
 //                          (sdsp_hip_cic_taps): the independent cross-check.
 // The new history is carry_history's (stream_carry.hip), launched by the caller behind either kernel.
-#include "stream_dev.h"
+#include "cic_dev.h"
 
 #include <type_traits>
 
@@ -53,26 +53,6 @@ struct cic_kargs {
     uint32_t ntaps;
     int32_t binom[kMaxOrder + 1]; // (-1)^j C(N, j)
 };
-
-template <typename ACC> struct signed_of {
-    typedef int32_t type;
-};
-template <> struct signed_of<uint64_t> {
-    typedef int64_t type;
-};
-
-// a sample, sign-extended to the register width
-template <typename ACC, typename IN> __device__ __forceinline__ ACC widen(IN x)
-{
-    return static_cast<ACC>(static_cast<typename signed_of<ACC>::type>(x));
-}
-
-// the value of the lane d below (its own for the lanes that have none)
-__device__ __forceinline__ uint32_t lane_up(uint32_t t, uint32_t d) { return __shfl_up(t, d, 64); }
-__device__ __forceinline__ uint64_t lane_up(uint64_t t, uint32_t d)
-{
-    return static_cast<uint64_t>(__shfl_up(static_cast<unsigned long long>(t), d, 64));
-}
 
 // y -> out[idx]: the register as it is (int32 / int64), or (float)((double)y * scale)
 template <typename ACC> __device__ __forceinline__ void put(void *out, uint64_t idx, ACC y, uint32_t out_f32, double scale)

@@ -880,6 +880,43 @@ int sdsp_hip_cic_taps(uint32_t order, uint32_t down, uint32_t delay, uint64_t *h
     }
     return SDSP_HIP_OK;
 }
+// CIC interpolator banks: the decimator's shape limits with R the up-sampling; the gain of every polyphase branch is
+// R^(N - 1) M^N = (R M)^N / R, at most 2^92
+int sdsp_hip_cic_interp_growth(uint32_t order, uint32_t up, uint32_t delay, uint32_t *bits)
+{
+    if (!bits)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *bits = 0;
+    if (int rc = cic_check_shape(order, up, delay))
+        return rc;
+    uint32_t b = 0;
+    for (unsigned __int128 v = cic_gain(order, up, delay) / up - 1; v; v >>= 1)
+        b++;
+    *bits = b;
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_cic_interp_unity_scale(uint32_t order, uint32_t up, uint32_t delay, double *scale)
+{
+    if (!scale)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *scale = 0.0;
+    if (int rc = cic_check_shape(order, up, delay))
+        return rc;
+    // (double)g with one rounding, as in sdsp_hip_cic_unity_scale: the top 64 bits with a sticky bit for the rest
+    unsigned __int128 top = cic_gain(order, up, delay) / up;
+    uint32_t shift = 0;
+    bool sticky = false;
+    while (top >> 64) {
+        sticky = sticky || (top & 1);
+        top >>= 1;
+        shift++;
+    }
+    uint64_t t = static_cast<uint64_t>(top);
+    if (sticky)
+        t |= 1;
+    *scale = 1.0 / std::ldexp(static_cast<double>(t), static_cast<int>(shift));
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_stft_window(int kind, uint32_t n, double *w)
 {
     if (!w)

@@ -353,6 +353,22 @@ int launch_cic(const cic_args &a, int variant, void *stream);
 const char *cic_kernel_for(int variant);
 // input elements one workgroup of sdsp_cic_kernel scans per pass
 uint32_t cic_chunk();
+// CIC interpolator banks (cic_interp.hip): the one launch of a call, in front of carry_history
+struct cic_interp_args {
+    const void *in;
+    void *out;
+    const void *state; // nullable; channels x order * delay elements of the input kind and type, newest first
+    const void *taps;  // device, order * (up * delay - 1) + 1 values of 64 bits (variant 1 only)
+    uint64_t channels, samples, in_stride, out_stride; // samples * up in [1, 2^31)
+    uint32_t order, up, delay;
+    uint32_t segment;  // chunks of output per workgroup of the scan kernel, 0 = automatic
+    int in32, complex_in, reg64, out_f32;
+    double scale;
+};
+int launch_cic_interp(const cic_interp_args &a, int variant, void *stream);
+const char *cic_interp_kernel_for(int variant);
+// outputs one workgroup of sdsp_cic_interp_kernel scans per pass
+uint32_t cic_interp_chunk();
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
