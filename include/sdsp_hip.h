@@ -1419,6 +1419,95 @@ typedef struct {
 } sdsp_hip_cic_interp_plan_info;
 int sdsp_hip_cic_interp_plan_get_info(const sdsp_hip_cic_interp_plan *plan, sdsp_hip_cic_interp_plan_info *info);
 
+/* ------------------------------------------------------------------ time-delay beamformer banks */
+
+/*
+ * Time-delay (filter-and-sum) beamformer bank: the streams of a sensor array are delayed, weighted and summed
+ * into beams.  There are `groups` arrays of `sensors` = C input rows and `beams` = B output rows each: input row g C + c, output row
+ * g B + b, channel-major, strides in elements.  All groups share the plan's entries.  An entry is {beam, sensor, delay} with its own T
+ * taps g[0..T): the beam gets the sensor's stream delayed by `delay` whole samples and filtered with g (a fractional-delay filter, a
+ * weight, or both; sdsp_hip_beam_delay_taps designs one).  A call takes S >= 0 samples per input row and writes S outputs per beam.
+ * The bit-level definition, with x_c = the sensor's history followed by the call's block:
+ *   - output n of beam b has one accumulator, starting at +0.  It runs over the beam's entries in the order given, and within an entry
+ *     over ascending t:  acc = g[t] x_c[n - delay - t] + acc.  REAL: one fmaf per step in f32, a multiply then an add, each rounded, in
+ *     f64.  COMPLEX (accumulators zr, zi): per step, in this order, zr += gr xr, zr -= gi xi, zi += gr xi, zi += gi xr, each of the four
+ *     one fmaf in f32 and a multiply then an add (or subtraction) in f64 -- the DDC bank's filter step.  Nothing else is contracted.
+ *   - taps: host doubles (interleaved re, im pairs for COMPLEX), [entry][t], rounded once to the plan precision.
+ *   - entries are sorted by beam (beam numbers never decrease), and within a beam the sensor numbers strictly ascend: at most one entry
+ *     per sensor and beam.  A beam may have no entry: its outputs are +0.  A sensor may be used by no beam: it is never read, but its
+ *     history is still carried.
+ *   - history: H = (max delay over all entries) + T - 1 elements of the input kind per INPUT ROW, state[(g C + c) H + j] = x[-1 - j]
+ *     (newest first); read at entry, written at exit (a call of S = 0 leaves it as it is); NULL = zero history, final history
+ *     dropped.  There is no stream position: the operation is time-invariant.
+ *   - any split of a stream into calls (blocks shorter than H and empty blocks included) gives the same bits and the same final state.
+ *   - kinds: REAL = real rows, real taps, real beams; COMPLEX = interleaved I/Q rows, complex taps, complex beams (one complex sample is
+ *     one element); with T = 1 this is the narrowband phase-shift beamformer behind a DDC bank.
+ *   - `in` is never written; nothing past each beam's S outputs is.
+ * Limits: 1 <= T <= SDSP_HIP_BEAM_MAX_TAPS, 0 <= delay <= SDSP_HIP_BEAM_MAX_DELAY, 1 <= C, B <= SDSP_HIP_BEAM_MAX_ROWS,
+ * 0 <= n_entries <= SDSP_HIP_BEAM_MAX_ENTRIES, groups >= 1 with groups C and groups B below 2^31.  Entries and taps are fixed at plan
+ * creation.
+ */
+#define SDSP_HIP_BEAM_REAL 0
+#define SDSP_HIP_BEAM_COMPLEX 1
+#define SDSP_HIP_BEAM_MAX_TAPS 256
+#define SDSP_HIP_BEAM_MAX_DELAY 65535
+#define SDSP_HIP_BEAM_MAX_ROWS 4096
+#define SDSP_HIP_BEAM_MAX_ENTRIES (1u << 20)
+typedef struct sdsp_hip_beam_plan sdsp_hip_beam_plan;
+typedef struct {
+    uint32_t beam;   /* output row within a group */
+    uint32_t sensor; /* input row within a group */
+    uint32_t delay;  /* whole samples */
+} sdsp_hip_beam_entry;
+/* fractional-delay taps for one entry, host only, in double: a Kaiser-windowed sinc.  T >= 2: d = floor(tau), mu = tau - d,
+ * c0 = (T - 1) div 2, u_t = t - c0 - mu, g[t] proportional to sinc(u_t) I0(beta sqrt(max(0, 1 - (u_t / ((T + 1) / 2))^2))) / I0(beta)
+ * (sinc(u) = sin(pi u) / (pi u)), scaled so that sum g = weight; *delay = d.  An entry with these taps delays by tau + c0 samples: c0 is
+ * the latency every entry of the plan shares.  T = 1: *delay = floor(tau + 1/2), g[0] = weight.  Errors: taps out of range:
+ * SDSP_HIP_ERR_INVALID_SIZE; tau < 0, tau >= SDSP_HIP_BEAM_MAX_DELAY, beta < 0, a non-finite argument, a null pointer:
+ * SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_beam_delay_taps(double tau, double weight, uint32_t taps, double beta, uint32_t *delay, double *g);
+/* entries: n_entries entries in the contract's order; g: n_entries x taps host doubles (x 2 for COMPLEX).  Errors: sensors, beams,
+ * groups, taps, n_entries or a delay out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an entry naming a beam or sensor the plan
+ * does not have, entries out of order or a (beam, sensor) pair given twice, an unknown kind, a precision other than F32 / F64:
+ * SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_beam_plan_create(sdsp_hip_beam_plan **plan, uint32_t sensors, uint32_t beams, uint32_t groups, uint32_t taps,
+                              uint32_t n_entries, const sdsp_hip_beam_entry *entries, const double *g, int kind, int precision,
+                              int device);
+int sdsp_hip_beam_plan_destroy(sdsp_hip_beam_plan *plan);
+/*
+ * in: DEVICE pointer, input row r = in[r in_stride .. + samples) elements of the kind.  out: DEVICE pointer, output row r = out[r
+ * out_stride .. + samples).  state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one call
+ * per plan in flight.  Errors: null plan, in or out, a stride < samples with more than one row, overlapping in and out ranges,
+ * misaligned pointers: SDSP_HIP_ERR_INVALID_ARG; samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; a grid that does not fit one launch:
+ * SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_beam_process(sdsp_hip_beam_plan *plan, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples,
+                          void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_beam_process_host(sdsp_hip_beam_plan *plan, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                               uint64_t samples, void *host_state);
+/* bytes of the plan's state buffer: H groups C element size (0 when H = 0) */
+int sdsp_hip_beam_state_bytes(const sdsp_hip_beam_plan *plan, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_beam_kernel, the fused form (a workgroup stages each sensor's window in LDS
+ * once for a chunk of beams, a lane slides a register window over the taps for four consecutive outputs); 1 =
+ * sdsp_beam_plain_kernel, one output per thread from global memory (the cross-check; it shares no staging logic with the fused form). */
+int sdsp_hip_beam_plan_set_variant(sdsp_hip_beam_plan *plan, int variant);
+/* kernel launches of one process call with a state buffer: the beam kernel, and one for the new history when H > 0; 0 for
+ * samples == 0 */
+int sdsp_hip_beam_plan_launches(const sdsp_hip_beam_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint32_t sensors, beams, groups, taps, entries;
+    uint32_t max_delay;      /* over all entries */
+    uint32_t hist;           /* H = max_delay + taps - 1 */
+    uint32_t block_out;      /* outputs per beam one workgroup of sdsp_beam_kernel produces */
+    uint32_t chunks;         /* chunks of consecutive beams that share staged sensor windows (the beam chunk table) */
+    uint32_t max_spread;     /* the widest delay spread (max - min over a chunk's beams on one sensor) a chunk may have */
+    uint32_t lds_line_bytes; /* one of the two LDS lines of sdsp_beam_kernel: the plan's widest sensor window, padded */
+    int kind, precision, device, variant;
+    char kernel[64];         /* the kernel the plan's variant runs */
+} sdsp_hip_beam_plan_info;
+int sdsp_hip_beam_plan_get_info(const sdsp_hip_beam_plan *plan, sdsp_hip_beam_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

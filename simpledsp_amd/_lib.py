@@ -170,6 +170,19 @@ class CicInterpPlanInfo(C.Structure):
     ]
 
 
+class BeamEntry(C.Structure):
+    _fields_ = [("beam", C.c_uint32), ("sensor", C.c_uint32), ("delay", C.c_uint32)]
+
+
+class BeamPlanInfo(C.Structure):
+    _fields_ = [
+        ("sensors", C.c_uint32), ("beams", C.c_uint32), ("groups", C.c_uint32), ("taps", C.c_uint32), ("entries", C.c_uint32),
+        ("max_delay", C.c_uint32), ("hist", C.c_uint32), ("block_out", C.c_uint32), ("chunks", C.c_uint32), ("max_spread", C.c_uint32),
+        ("lds_line_bytes", C.c_uint32), ("kind", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("variant", C.c_int),
+        ("kernel", C.c_char * 64),
+    ]
+
+
 CIC_REAL, CIC_COMPLEX = 0, 1
 CIC_I16, CIC_I32 = 0, 1
 CIC_OUT_INT, CIC_OUT_F32 = 0, 1
@@ -181,6 +194,8 @@ DDC_REAL, DDC_COMPLEX = 0, 1
 DDC_MAX_BANDS = 65536
 DUC_REAL, DUC_COMPLEX = 0, 1
 DUC_MAX_BANDS = 65536
+BEAM_REAL, BEAM_COMPLEX = 0, 1
+BEAM_MAX_TAPS, BEAM_MAX_DELAY, BEAM_MAX_ROWS, BEAM_MAX_ENTRIES = 256, 65535, 4096, 1 << 20
 PFB_REAL, PFB_COMPLEX = 0, 1
 PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
 PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
@@ -384,6 +399,15 @@ SIGNATURES = {
     "sdsp_hip_duc_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_duc_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_duc_plan_get_info": (_i, [_vp, C.POINTER(DucPlanInfo)]),
+    "sdsp_hip_beam_delay_taps": (_i, [_d, _d, _u32, _d, C.POINTER(_u32), _vp]),
+    "sdsp_hip_beam_plan_create": (_i, [_pp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _i, _i, _i]),
+    "sdsp_hip_beam_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_beam_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_beam_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_beam_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_beam_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_beam_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_beam_plan_get_info": (_i, [_vp, C.POINTER(BeamPlanInfo)]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -505,6 +505,14 @@ struct sdsp_hip_duc_plan {
     void *h = nullptr;         // the taps, plan precision
     void *osc = nullptr;       // the DDC's C then F: 2 x 65536 interleaved complex values, plan precision
     uint32_t *table = nullptr; // channels + 1 offsets (the bands sorted by dst), then 4 words per band: input row, dst, fcw, phase0
+};
+
+struct sdsp_hip_beam_plan {
+    uint32_t sensors = 0, beams = 0, groups = 1, taps = 0, entries = 0, max_delay = 0, hist = 0; // hist = max_delay + taps - 1
+    int kind = 0, precision = 0, device = 0, variant = 0;
+    void *g = nullptr;         // [entry][tap] taps (interleaved pairs for complex), plan precision
+    uint32_t *table = nullptr; // beam_build_table's: the entries, each beam's run of them, the beam chunks and their sensor records
+    beam_layout lay;
 };
 
 struct sdsp_hip_arb_plan {
@@ -5406,6 +5414,230 @@ int sdsp_hip_cic_interp_process_host(sdsp_hip_cic_interp_plan *p, const void *ho
     int rc = st.in();
     if (!rc)
         rc = cic_interp_run(p, st.dev[0], in_stride, st.dev[1], out_stride, channels, samples, st.dev[2], nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ time-delay beamformer banks (beam.hip)
+
+namespace
+{
+uint64_t beam_esize(const sdsp_hip_beam_plan *p)
+{
+    return p->kind == SDSP_HIP_BEAM_COMPLEX ? esize(p->precision) : real_size(p->precision);
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int beam_check(const sdsp_hip_beam_plan *p, const void *in, uint64_t in_stride, const void *out, uint64_t out_stride, uint64_t samples)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in or out is null");
+    if ((static_cast<uint64_t>(p->groups) * p->sensors > 1 && in_stride < samples) ||
+        (static_cast<uint64_t>(p->groups) * p->beams > 1 && out_stride < samples))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_stride and out_stride must be >= samples");
+    return SDSP_HIP_OK;
+}
+
+int beam_run(sdsp_hip_beam_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples, void *state,
+             hipStream_t stream)
+{
+    beam_args a{};
+    a.in = in;
+    a.out = out;
+    a.state = p->hist ? state : nullptr;
+    a.g = p->g;
+    a.table = p->table;
+    a.lay = p->lay;
+    a.samples = samples;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.taps = p->taps;
+    a.hist = p->hist;
+    a.sensors = p->sensors;
+    a.beams = p->beams;
+    a.groups = p->groups;
+    a.complex_in = p->kind == SDSP_HIP_BEAM_COMPLEX;
+    if (int rc = launch_beam(p->precision, a, p->variant, stream))
+        return rc;
+    // behind the beam kernel: it reads the old history
+    return carry_history(p->precision, static_cast<uint32_t>(beam_esize(p)), in, in_stride, state,
+                         static_cast<uint64_t>(p->groups) * p->sensors, samples, p->hist, stream, "beam");
+}
+} // namespace
+
+int sdsp_hip_beam_plan_create(sdsp_hip_beam_plan **out, uint32_t sensors, uint32_t beams, uint32_t groups, uint32_t taps,
+                              uint32_t n_entries, const sdsp_hip_beam_entry *entries, const double *g, int kind, int precision,
+                              int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (sensors == 0 || sensors > SDSP_HIP_BEAM_MAX_ROWS || beams == 0 || beams > SDSP_HIP_BEAM_MAX_ROWS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "sensors and beams must be in [1, SDSP_HIP_BEAM_MAX_ROWS]");
+    if (groups == 0 || static_cast<uint64_t>(groups) * sensors > 0x7fffffffull || static_cast<uint64_t>(groups) * beams > 0x7fffffffull)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "groups must be >= 1 with groups * sensors and groups * beams below 2^31");
+    if (taps == 0 || taps > SDSP_HIP_BEAM_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_BEAM_MAX_TAPS]");
+    if (n_entries > SDSP_HIP_BEAM_MAX_ENTRIES)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "the entry count must be in [0, SDSP_HIP_BEAM_MAX_ENTRIES]");
+    if (n_entries && (!entries || !g))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "entry or tap pointer is null");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (kind != SDSP_HIP_BEAM_REAL && kind != SDSP_HIP_BEAM_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "kind must be SDSP_HIP_BEAM_REAL or SDSP_HIP_BEAM_COMPLEX");
+    uint32_t max_delay = 0;
+    for (uint32_t i = 0; i < n_entries; i++) {
+        const sdsp_hip_beam_entry &e = entries[i];
+        if (e.beam >= beams || e.sensor >= sensors)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "an entry names a beam or a sensor the plan does not have");
+        if (e.delay > SDSP_HIP_BEAM_MAX_DELAY)
+            return fail(SDSP_HIP_ERR_INVALID_SIZE, "a delay must be in [0, SDSP_HIP_BEAM_MAX_DELAY]");
+        if (i && (e.beam < entries[i - 1].beam || (e.beam == entries[i - 1].beam && e.sensor <= entries[i - 1].sensor)))
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "entries must be sorted by beam, and by strictly ascending sensor within a beam");
+        max_delay = e.delay > max_delay ? e.delay : max_delay;
+    }
+    if (int rc = use_device(device))
+        return rc;
+    const bool cplx = kind == SDSP_HIP_BEAM_COMPLEX;
+    if (int rc = beam_prepare(precision, cplx))
+        return rc;
+    // the host tables grow with the beams and the entries: running out of host memory for them is an error code, not an exception
+    std::vector<uint32_t> table;
+    beam_layout lay;
+    try {
+        beam_build_table(precision, cplx, taps, beams, n_entries, entries, table, lay);
+    } catch (const std::bad_alloc &) {
+        return fail(SDSP_HIP_ERR_NOMEM, "beam plan: out of host memory for the entry tables");
+    }
+    auto *p = new sdsp_hip_beam_plan();
+    p->sensors = sensors;
+    p->beams = beams;
+    p->groups = groups;
+    p->taps = taps;
+    p->entries = n_entries;
+    p->max_delay = max_delay;
+    p->hist = max_delay + taps - 1;
+    p->kind = kind;
+    p->precision = precision;
+    p->device = device;
+    p->lay = lay;
+    const size_t ng = static_cast<size_t>(n_entries) * taps * (cplx ? 2 : 1);
+    const double none = 0.0; // a plan without entries still owns a (one-value) tap table
+    hipError_t e = upload_reals(ng ? g : &none, ng ? ng : 1, precision, &p->g);
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&p->table), table.size() * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(p->table, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        sdsp_hip_beam_plan_destroy(p);
+        return plan_fail(e, "beam");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_beam_plan_destroy(sdsp_hip_beam_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->g);
+        (void)hipFree(p->table);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_beam_state_bytes(const sdsp_hip_beam_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = static_cast<uint64_t>(p->hist) * p->groups * p->sensors * beam_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_beam_plan_set_variant(sdsp_hip_beam_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_beam_plan_launches(const sdsp_hip_beam_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = samples ? 1 + (p->hist ? 1 : 0) : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_beam_plan_get_info(const sdsp_hip_beam_plan *p, sdsp_hip_beam_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->sensors = p->sensors;
+    info->beams = p->beams;
+    info->groups = p->groups;
+    info->taps = p->taps;
+    info->entries = p->entries;
+    info->max_delay = p->max_delay;
+    info->hist = p->hist;
+    info->block_out = beam_block_out();
+    info->chunks = p->lay.chunks;
+    info->max_spread = p->lay.max_spread;
+    info->lds_line_bytes = p->lay.lds_line_bytes;
+    info->kind = p->kind;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, beam_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_beam_process(sdsp_hip_beam_plan *p, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t samples,
+                          void *state, void *stream)
+{
+    if (int rc = beam_check(p, in, in_stride, out, out_stride, samples))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = beam_esize(p), rows_in = static_cast<uint64_t>(p->groups) * p->sensors,
+                   rows_out = static_cast<uint64_t>(p->groups) * p->beams;
+    if (int rc = check_out_of_place(in, ((rows_in - 1) * in_stride + samples) * es, es, out, ((rows_out - 1) * out_stride + samples) * es, es,
+                                    state, es, "in and out ranges overlap (the beamformer runs out of place)"))
+        return rc;
+    if (int rc = use_device(p->device))
+        return rc;
+    return beam_run(p, in, in_stride, out, out_stride, samples, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_beam_process_host(sdsp_hip_beam_plan *p, const void *host_in, uint64_t in_stride, void *host_out, uint64_t out_stride,
+                               uint64_t samples, void *host_state)
+{
+    if (int rc = beam_check(p, host_in, in_stride, host_out, out_stride, samples))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t es = beam_esize(p);
+    const size_t in_bytes = ((static_cast<uint64_t>(p->groups) * p->sensors - 1) * in_stride + samples) * es;
+    const size_t out_bytes = ((static_cast<uint64_t>(p->groups) * p->beams - 1) * out_stride + samples) * es;
+    uint64_t state_bytes = 0;
+    sdsp_hip_beam_state_bytes(p, &state_bytes);
+    const bool with_state = host_state && state_bytes;
+    host_stage st("beam", { { host_in, in_bytes, false }, { host_out, out_bytes, true },
+                        { with_state ? host_state : nullptr, state_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = beam_run(p, st.dev[0], in_stride, st.dev[1], out_stride, samples, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

@@ -991,4 +991,54 @@ int sdsp_hip_filtfilt_default_padlen(uint32_t sections, int kind, const double *
 {
     return filtfilt_default_padlen(sections, kind, a, b, padlen);
 }
+// I0(x) for x >= 0 by its power series sum ((x / 2)^k / k!)^2: every term positive, so nothing cancels; ends when a term no longer
+// changes the sum
+static double bessel_i0(double x)
+{
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000; k++) {
+        term *= q / (static_cast<double>(k) * k);
+        const double next = sum + term;
+        if (next == sum)
+            break;
+        sum = next;
+    }
+    return sum;
+}
+int sdsp_hip_beam_delay_taps(double tau, double weight, uint32_t taps, double beta, uint32_t *delay, double *g)
+{
+    if (!delay || !g)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *delay = 0;
+    if (taps == 0 || taps > SDSP_HIP_BEAM_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_BEAM_MAX_TAPS]");
+    if (!std::isfinite(tau) || !std::isfinite(weight) || !std::isfinite(beta))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "tau, weight and beta must be finite");
+    if (tau < 0.0 || tau >= static_cast<double>(SDSP_HIP_BEAM_MAX_DELAY))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "tau must be in [0, SDSP_HIP_BEAM_MAX_DELAY)");
+    if (beta < 0.0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "beta must be >= 0");
+    if (taps == 1) { // the nearest whole sample
+        *delay = static_cast<uint32_t>(std::floor(tau + 0.5));
+        g[0] = weight;
+        return SDSP_HIP_OK;
+    }
+    const double d = std::floor(tau), mu = tau - d;
+    const double c0 = static_cast<double>((taps - 1) / 2), half = 0.5 * (static_cast<double>(taps) + 1.0), i0b = bessel_i0(beta);
+    double sum = 0.0;
+    for (uint32_t t = 0; t < taps; t++) {
+        const double u = static_cast<double>(t) - c0 - mu, r = u / half, pu = M_PI * u;
+        const double arg = 1.0 - r * r;
+        const double w = bessel_i0(beta * std::sqrt(arg > 0.0 ? arg : 0.0)) / i0b;
+        g[t] = (u == 0.0 ? 1.0 : std::sin(pu) / pu) * w;
+        sum += g[t];
+    }
+    if (!(std::fabs(sum) > 0.0) || !std::isfinite(sum))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the window leaves taps that sum to zero: nothing to scale to the weight");
+    for (uint32_t t = 0; t < taps; t++)
+        g[t] = g[t] / sum * weight;
+    *delay = static_cast<uint32_t>(d);
+    return SDSP_HIP_OK;
+}
 }

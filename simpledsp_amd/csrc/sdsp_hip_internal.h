@@ -369,6 +369,36 @@ int launch_cic_interp(const cic_interp_args &a, int variant, void *stream);
 const char *cic_interp_kernel_for(int variant);
 // outputs one workgroup of sdsp_cic_interp_kernel scans per pass
 uint32_t cic_interp_chunk();
+// time-delay beamformer banks (beam.hip): the one launch of a call, in front of carry_history
+struct beam_layout {
+    uint32_t chunks = 0;         // chunks of consecutive beams
+    uint32_t max_spread = 0;     // the widest delay spread on one sensor a chunk may have
+    uint32_t line_elems = 0;     // elements of the plan's widest staged sensor window (before the pad)
+    uint32_t lds_line_bytes = 0; // ... as one padded LDS line
+    uint32_t off_beams = 0, off_chunks = 0, off_recs = 0; // word offsets into the table
+};
+struct beam_args {
+    const void *in;
+    void *out;
+    const void *state;     // nullable; groups x sensors x hist elements of the kind, newest first
+    const void *g;         // device, plan precision: [entry][tap] taps (interleaved pairs for complex)
+    const uint32_t *table; // device: the plan's table (beam_build_table)
+    beam_layout lay;
+    uint64_t samples, in_stride, out_stride;
+    uint32_t taps, hist, sensors, beams, groups;
+    int complex_in;
+};
+// the plan's device table from its checked entries: 3 words per entry (beam, sensor, delay); beams + 1 offsets of each beam's entries;
+// 4 words per chunk (first beam, beams, first record, records); 8 words per record = one sensor a chunk uses (sensor, smallest and
+// largest delay of the chunk's beams on it, 0, then per beam of the chunk its entry or 0xffffffff)
+void beam_build_table(int precision, int complex_in, uint32_t taps, uint32_t beams, uint32_t n_entries, const sdsp_hip_beam_entry *entries,
+                      std::vector<uint32_t> &table, beam_layout &lay);
+int launch_beam(int precision, const beam_args &a, int variant, void *stream);
+const char *beam_kernel_for(int variant);
+// once per device and instantiation, at plan creation: the fused kernel's dynamic-LDS limit, large enough for every plan
+int beam_prepare(int precision, int complex_in);
+// outputs per beam one workgroup of sdsp_beam_kernel produces
+uint32_t beam_block_out();
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
