@@ -1508,6 +1508,84 @@ typedef struct {
 } sdsp_hip_beam_plan_info;
 int sdsp_hip_beam_plan_get_info(const sdsp_hip_beam_plan *plan, sdsp_hip_beam_plan_info *info);
 
+/* ------------------------------------------------------------------ LMS / NLMS adaptive filter banks */
+
+/*
+ * LMS / NLMS adaptive filter bank: `channels` independent adaptive FIR filters of T taps each, whose weights
+ * move with every sample.  A call takes S >= 0 samples per channel of two input rows, the reference input x and the desired signal d
+ * (channel-major: row c = ptr[c stride .. + S) elements of the kind, strides in elements), and writes up to two output rows, the
+ * filter output y and the error e.  The step size mu is an argument of the call.  The bit-level definition, with x_c = the channel's
+ * history followed by the call's block and w = the channel's T weights, for n = 0 .. S - 1 in this order:
+ *   1. y = +0, then for t = 0 .. T - 1 ascending  y = w[t] x_c[n - t] + y.  REAL: one fmaf per step in f32; a multiply then an add, each
+ *      rounded, in f64.  COMPLEX (no conjugate: with mu = 0 the plan is a complex FIR filter): per tap, in this order,
+ *      yr += wr xr, yr -= wi xi, yi += wr xi, yi += wi xr, each one fmaf in f32 (the subtraction: fmaf(-wi, xi, yr)) and a multiply then an
+ *      add (or subtraction) in f64 -- the DDC bank's filter step.
+ *   2. e = d[n] - y, one subtraction (per component).
+ *   3. LMS: g = mu e, one rounded product (per component).
+ *   4. NLMS: p = +0, then for t ascending  p = x_c[n - t] x_c[n - t] + p  with the rule of step 1 (COMPLEX: xr xr, then xi xi, per
+ *      tap); then g = (mu e) / (eps + p): a rounded product, a rounded sum and a correctly rounded division (both components of a
+ *      complex e divide by the same eps + p).  The energy is recomputed from the window for every sample, never carried.
+ *   5. for t ascending  w[t] = g x_c[n - t] + w[t]  with the rule of step 1.  COMPLEX (w += g conj(x)): wr = gr xr + wr, wr = gi xi + wr,
+ *      wi = gi xr + wi, wi = -(gr xi) + wi (f32: fmaf(-gr, xi, wi); f64: wi - gr xi), in this order.
+ *   6. y[n] and e[n] are the values of steps 1 and 2: the a-priori output and error.
+ * Nothing else is contracted.  mu and eps are host doubles, each rounded once to the plan precision (eps at plan creation).  mu = 0
+ * filters with frozen weights (w[t] = (+-0) x + w[t] still runs: a weight of -0 becomes +0, a non-finite x reaches the weights).
+ *   - state: one caller-owned device buffer of sdsp_hip_lms_state_bytes bytes.  First channels x T weights, state[c T + t] = w_c[t];
+ *     then channels x (T - 1) elements of x history, newest first: state[channels T + c (T - 1) + j] = x_c[-1 - j].  Read at entry,
+ *     written at exit.  A zero-filled buffer is a fresh stream with zero weights.  NULL = zero weights and zero history, nothing kept.
+ *   - there is no stream position; any split of a stream into calls (empty calls included) gives the same bits and the same final
+ *     state.  A call with S = 0 returns at once and leaves the state alone.
+ *   - y or e or both may be NULL and are then not written.  Outputs may not overlap inputs or each other.  x and d are never
+ *     written; nothing past each row's S outputs is.
+ *   - kinds: REAL = real rows and weights; COMPLEX = interleaved I/Q rows and weights (one complex sample is one element).
+ * Limits: 1 <= T <= SDSP_HIP_LMS_MAX_TAPS (SDSP_HIP_LMS_MAX_TAPS_F64_COMPLEX for F64 COMPLEX), 1 <= channels < 2^31, S < 2^31.
+ */
+#define SDSP_HIP_LMS_REAL 0
+#define SDSP_HIP_LMS_COMPLEX 1
+#define SDSP_HIP_LMS_LMS 0
+#define SDSP_HIP_LMS_NLMS 1
+#define SDSP_HIP_LMS_MAX_TAPS 64
+#define SDSP_HIP_LMS_MAX_TAPS_F64_COMPLEX 32
+typedef struct sdsp_hip_lms_plan sdsp_hip_lms_plan;
+/* eps is used by NLMS only.  Errors: channels or taps out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an unknown kind or mode,
+ * a precision other than F32 / F64, for NLMS an eps that is not finite and > 0 once rounded to the precision:
+ * SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_lms_plan_create(sdsp_hip_lms_plan **plan, uint64_t channels, uint32_t taps, int kind, int precision, int mode, double eps,
+                             int device);
+int sdsp_hip_lms_plan_destroy(sdsp_hip_lms_plan *plan);
+/*
+ * x, d: DEVICE pointers; y, e: DEVICE pointers or NULL; state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing
+ * (stream-capturable); one call per plan in flight.  Errors: null plan, x or d, a stride < samples with more than one channel,
+ * overlapping ranges, misaligned pointers, a mu that is not finite in the precision: SDSP_HIP_ERR_INVALID_ARG; samples >= 2^31:
+ * SDSP_HIP_ERR_INVALID_SIZE; a grid that does not fit one launch: SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_lms_process(sdsp_hip_lms_plan *plan, const void *x, uint64_t x_stride, const void *d, uint64_t d_stride, void *y,
+                         uint64_t y_stride, void *e, uint64_t e_stride, uint64_t samples, double mu, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_lms_process_host(sdsp_hip_lms_plan *plan, const void *host_x, uint64_t x_stride, const void *host_d, uint64_t d_stride,
+                              void *host_y, uint64_t y_stride, void *host_e, uint64_t e_stride, uint64_t samples, double mu,
+                              void *host_state);
+/* bytes of the plan's state buffer: channels (2 T - 1) element size */
+int sdsp_hip_lms_state_bytes(const sdsp_hip_lms_plan *plan, uint64_t *bytes);
+/* kernel variants (identical values, bit for bit): 0 = sdsp_lms_kernel (a lane per channel, the weights in registers for the whole call,
+ * rows transposed through LDS, the update of one sample fused into the filtering of the next); 1 = sdsp_lms_plain_kernel, one thread
+ * per channel from global memory with the weights read-modify-written in `state` (the cross-check; it shares no staging logic with
+ * variant 0).  Selecting variant 1 allocates channels x T elements of plan-owned scratch once, for calls without a state buffer. */
+int sdsp_hip_lms_plan_set_variant(sdsp_hip_lms_plan *plan, int variant);
+/* kernel launches of one process call with a state buffer: the filter kernel, and one for the new history when T > 1; 0 for
+ * samples == 0 */
+int sdsp_hip_lms_plan_launches(const sdsp_hip_lms_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint64_t channels;
+    uint32_t taps;
+    uint32_t block;     /* samples per time block of sdsp_lms_kernel for this kind, precision and tap count */
+    uint32_t lds_bytes; /* LDS of one workgroup (one wave, 64 channels) of sdsp_lms_kernel: (T + 2 block) rows of 65 elements */
+    double eps;         /* as rounded to the precision; 0 for LMS */
+    int kind, precision, mode, device, variant;
+    char kernel[64];    /* the kernel the plan's variant runs */
+} sdsp_hip_lms_plan_info;
+int sdsp_hip_lms_plan_get_info(const sdsp_hip_lms_plan *plan, sdsp_hip_lms_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

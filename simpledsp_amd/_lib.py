@@ -183,6 +183,14 @@ class BeamPlanInfo(C.Structure):
     ]
 
 
+class LmsPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels", C.c_uint64), ("taps", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint32), ("eps", C.c_double),
+        ("kind", C.c_int), ("precision", C.c_int), ("mode", C.c_int), ("device", C.c_int), ("variant", C.c_int),
+        ("kernel", C.c_char * 64),
+    ]
+
+
 CIC_REAL, CIC_COMPLEX = 0, 1
 CIC_I16, CIC_I32 = 0, 1
 CIC_OUT_INT, CIC_OUT_F32 = 0, 1
@@ -196,6 +204,9 @@ DUC_REAL, DUC_COMPLEX = 0, 1
 DUC_MAX_BANDS = 65536
 BEAM_REAL, BEAM_COMPLEX = 0, 1
 BEAM_MAX_TAPS, BEAM_MAX_DELAY, BEAM_MAX_ROWS, BEAM_MAX_ENTRIES = 256, 65535, 4096, 1 << 20
+LMS_REAL, LMS_COMPLEX = 0, 1
+LMS_LMS, LMS_NLMS = 0, 1
+LMS_MAX_TAPS, LMS_MAX_TAPS_F64_COMPLEX = 64, 32
 PFB_REAL, PFB_COMPLEX = 0, 1
 PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
 PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
@@ -408,6 +419,14 @@ SIGNATURES = {
     "sdsp_hip_beam_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_beam_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_beam_plan_get_info": (_i, [_vp, C.POINTER(BeamPlanInfo)]),
+    "sdsp_hip_lms_plan_create": (_i, [_pp, _u64, _u32, _i, _i, _i, _d, _i]),
+    "sdsp_hip_lms_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_lms_process": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _d, _vp, _vp]),
+    "sdsp_hip_lms_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _d, _vp]),
+    "sdsp_hip_lms_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_lms_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_lms_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_lms_plan_get_info": (_i, [_vp, C.POINTER(LmsPlanInfo)]),
 }
 
 _lib = None

@@ -52,6 +52,7 @@ SOURCES = {
     "ddc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps and the two complex products: multiply then add, never an FMA
     "duc.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: f64 taps, the complex products and the band sum never contract
     "beam.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: f64 taps multiply then add, never an FMA
+    "lms.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip; no fast-math either: the NLMS step divides with a correctly rounded `/`
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -96,8 +96,8 @@ struct host_stage {
         bool copy_back; // `host` is writable where this is set
     };
     const char *family;
-    item items[4] = {};
-    void *dev[4] = {};
+    item items[5] = {};
+    void *dev[5] = {};
     size_t n = 0;
 
     host_stage(const char *family_, std::initializer_list<item> list) : family(family_)
@@ -513,6 +513,14 @@ struct sdsp_hip_beam_plan {
     void *g = nullptr;         // [entry][tap] taps (interleaved pairs for complex), plan precision
     uint32_t *table = nullptr; // beam_build_table's: the entries, each beam's run of them, the beam chunks and their sensor records
     beam_layout lay;
+};
+
+struct sdsp_hip_lms_plan {
+    uint64_t channels = 0;
+    uint32_t taps = 0;
+    int kind = 0, precision = 0, mode = 0, device = 0, variant = 0;
+    double eps = 0.0;          // rounded to the plan precision
+    void *scratch_w = nullptr; // channels x taps weights for the plain kernel of a call without state; made by set_variant(1)
 };
 
 struct sdsp_hip_arb_plan {
@@ -5638,6 +5646,212 @@ int sdsp_hip_beam_process_host(sdsp_hip_beam_plan *p, const void *host_in, uint6
     int rc = st.in();
     if (!rc)
         rc = beam_run(p, st.dev[0], in_stride, st.dev[1], out_stride, samples, st.dev[2], nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ LMS / NLMS adaptive filter banks (lms.hip)
+
+namespace
+{
+uint64_t lms_esize(const sdsp_hip_lms_plan *p) { return p->kind == SDSP_HIP_LMS_COMPLEX ? esize(p->precision) : real_size(p->precision); }
+
+double lms_round(const sdsp_hip_lms_plan *p, double v) { return p->precision == SDSP_HIP_F64 ? v : static_cast<double>(static_cast<float>(v)); }
+
+// argument checks shared by process and process_host (device pointers or not)
+int lms_check(const sdsp_hip_lms_plan *p, const void *x, uint64_t x_stride, const void *d, uint64_t d_stride, const void *y,
+              uint64_t y_stride, const void *e, uint64_t e_stride, uint64_t samples, double mu)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    if (!std::isfinite(mu) || !std::isfinite(lms_round(p, mu)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mu must be finite in the plan precision");
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!x || !d)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x or d is null");
+    if (p->channels > 1 && (x_stride < samples || d_stride < samples || (y && y_stride < samples) || (e && e_stride < samples)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "every stride must be >= samples");
+    return SDSP_HIP_OK;
+}
+
+int lms_run(sdsp_hip_lms_plan *p, const void *x, uint64_t x_stride, const void *d, uint64_t d_stride, void *y, uint64_t y_stride, void *e,
+            uint64_t e_stride, uint64_t samples, double mu, void *state, hipStream_t stream)
+{
+    const uint64_t es = lms_esize(p);
+    lms_args a{};
+    a.x = x;
+    a.d = d;
+    a.y = y;
+    a.e = e;
+    a.w = state;
+    a.hist = state && p->taps > 1 ? static_cast<unsigned char *>(state) + p->channels * p->taps * es : nullptr;
+    a.channels = p->channels;
+    a.samples = samples;
+    a.x_stride = x_stride;
+    a.d_stride = d_stride;
+    a.y_stride = y_stride;
+    a.e_stride = e_stride;
+    a.taps = p->taps;
+    a.complex_in = p->kind == SDSP_HIP_LMS_COMPLEX;
+    a.nlms = p->mode == SDSP_HIP_LMS_NLMS;
+    a.mu = lms_round(p, mu);
+    a.eps = p->eps;
+    if (p->variant == 1 && !state) { // the plain kernel keeps its weights in memory: zero rows of the plan's
+        if (!p->scratch_w)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "lms: variant 1 without its scratch rows");
+        HIP_TRY(hipMemsetAsync(p->scratch_w, 0, p->channels * p->taps * es, stream));
+        a.w = p->scratch_w;
+    }
+    if (int rc = launch_lms(p->precision, a, p->variant, stream))
+        return rc;
+    // behind the kernel: it reads the old history
+    return carry_history(p->precision, static_cast<uint32_t>(es), x, x_stride, const_cast<void *>(a.hist), p->channels, samples,
+                         p->taps - 1, stream, "lms");
+}
+} // namespace
+
+int sdsp_hip_lms_plan_create(sdsp_hip_lms_plan **out, uint64_t channels, uint32_t taps, int kind, int precision, int mode, double eps,
+                             int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (channels == 0 || channels > 0x7fffffffull)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be in [1, 2^31)");
+    if (taps == 0 || taps > SDSP_HIP_LMS_MAX_TAPS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_LMS_MAX_TAPS]");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (kind != SDSP_HIP_LMS_REAL && kind != SDSP_HIP_LMS_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "kind must be SDSP_HIP_LMS_REAL or SDSP_HIP_LMS_COMPLEX");
+    if (mode != SDSP_HIP_LMS_LMS && mode != SDSP_HIP_LMS_NLMS)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mode must be SDSP_HIP_LMS_LMS or SDSP_HIP_LMS_NLMS");
+    if (precision == SDSP_HIP_F64 && kind == SDSP_HIP_LMS_COMPLEX && taps > SDSP_HIP_LMS_MAX_TAPS_F64_COMPLEX)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps must be in [1, SDSP_HIP_LMS_MAX_TAPS_F64_COMPLEX] for F64 COMPLEX");
+    const double eps_r = precision == SDSP_HIP_F64 ? eps : static_cast<double>(static_cast<float>(eps));
+    if (mode == SDSP_HIP_LMS_NLMS && !(std::isfinite(eps_r) && eps_r > 0.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "eps must be finite and > 0 in the plan precision for NLMS");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_lms_plan();
+    p->channels = channels;
+    p->taps = taps;
+    p->kind = kind;
+    p->precision = precision;
+    p->mode = mode;
+    p->device = device;
+    p->eps = mode == SDSP_HIP_LMS_NLMS ? eps_r : 0.0;
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_lms_plan_destroy(sdsp_hip_lms_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (p->scratch_w && use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->scratch_w);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_lms_state_bytes(const sdsp_hip_lms_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = p->channels * (2ull * p->taps - 1) * lms_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_lms_plan_set_variant(sdsp_hip_lms_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    if (variant == 1 && !p->scratch_w) {
+        if (int rc = use_device(p->device))
+            return rc;
+        const hipError_t e = hipMalloc(&p->scratch_w, p->channels * p->taps * lms_esize(p));
+        if (e != hipSuccess) {
+            p->scratch_w = nullptr;
+            return plan_fail(e, "lms");
+        }
+    }
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_lms_plan_launches(const sdsp_hip_lms_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = samples ? 1 + (p->taps > 1 ? 1 : 0) : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_lms_plan_get_info(const sdsp_hip_lms_plan *p, sdsp_hip_lms_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const int cplx = p->kind == SDSP_HIP_LMS_COMPLEX;
+    info->channels = p->channels;
+    info->taps = p->taps;
+    info->block = lms_block(p->precision, cplx, p->taps);
+    info->lds_bytes = lms_lds_bytes(p->precision, cplx, p->taps);
+    info->eps = p->eps;
+    info->kind = p->kind;
+    info->precision = p->precision;
+    info->mode = p->mode;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, lms_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_lms_process(sdsp_hip_lms_plan *p, const void *x, uint64_t x_stride, const void *d, uint64_t d_stride, void *y,
+                         uint64_t y_stride, void *e, uint64_t e_stride, uint64_t samples, double mu, void *state, void *stream)
+{
+    if (int rc = lms_check(p, x, x_stride, d, d_stride, y, y_stride, e, e_stride, samples, mu))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = lms_esize(p);
+    auto span = [&](uint64_t stride) { return ((p->channels - 1) * stride + samples) * es; };
+    const void *ins[2] = { x, d };
+    const uint64_t in_bytes[2] = { span(x_stride), span(d_stride) };
+    for (int i = 0; i < 2; i++)
+        if (ranges_overlap(ins[i], in_bytes[i], y, span(y_stride)) || ranges_overlap(ins[i], in_bytes[i], e, span(e_stride)))
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "an output range overlaps an input range (the adaptive filter runs out of place)");
+    if (ranges_overlap(y, span(y_stride), e, span(e_stride)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the y and e ranges overlap");
+    if (misaligned(x, es) || misaligned(d, es) || misaligned(y, es) || misaligned(e, es) || misaligned(state, es))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x, d, y, e and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return lms_run(p, x, x_stride, d, d_stride, y, y_stride, e, e_stride, samples, mu, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_lms_process_host(sdsp_hip_lms_plan *p, const void *host_x, uint64_t x_stride, const void *host_d, uint64_t d_stride,
+                              void *host_y, uint64_t y_stride, void *host_e, uint64_t e_stride, uint64_t samples, double mu,
+                              void *host_state)
+{
+    if (int rc = lms_check(p, host_x, x_stride, host_d, d_stride, host_y, y_stride, host_e, e_stride, samples, mu))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t es = lms_esize(p);
+    auto span = [&](uint64_t stride) { return static_cast<size_t>(((p->channels - 1) * stride + samples) * es); };
+    uint64_t state_bytes = 0;
+    sdsp_hip_lms_state_bytes(p, &state_bytes);
+    host_stage st("lms", { { host_x, span(x_stride), false }, { host_d, span(d_stride), false }, { host_y, span(y_stride), true },
+                       { host_e, span(e_stride), true }, { host_state, static_cast<size_t>(state_bytes), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = lms_run(p, st.dev[0], x_stride, st.dev[1], d_stride, st.dev[2], y_stride, st.dev[3], e_stride, samples, mu, st.dev[4],
+                     nullptr);
     return st.out(rc);
 }
 }

@@ -399,6 +399,22 @@ const char *beam_kernel_for(int variant);
 int beam_prepare(int precision, int complex_in);
 // outputs per beam one workgroup of sdsp_beam_kernel produces
 uint32_t beam_block_out();
+// LMS / NLMS adaptive filter banks (lms.hip): the one launch of a call, in front of carry_history
+struct lms_args {
+    const void *x, *d;
+    void *y, *e;      // nullable: not written
+    void *w;          // nullable for variant 0 (zero weights, nothing kept); channels x taps elements of the kind, [channel][tap]
+    const void *hist; // nullable; channels x (taps - 1) elements of x, newest first
+    uint64_t channels, samples, x_stride, d_stride, y_stride, e_stride;
+    uint32_t taps;
+    int complex_in, nlms;
+    double mu, eps; // already rounded to the plan precision
+};
+int launch_lms(int precision, const lms_args &a, int variant, void *stream);
+const char *lms_kernel_for(int variant);
+// samples per time block of sdsp_lms_kernel and its LDS bytes per workgroup (one wave), for this kind, precision and tap count
+uint32_t lms_block(int precision, int complex_in, uint32_t taps);
+uint32_t lms_lds_bytes(int precision, int complex_in, uint32_t taps);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
