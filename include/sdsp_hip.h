@@ -1586,6 +1586,75 @@ typedef struct {
 } sdsp_hip_lms_plan_info;
 int sdsp_hip_lms_plan_get_info(const sdsp_hip_lms_plan *plan, sdsp_hip_lms_plan_info *info);
 
+/* ------------------------------------------------------------------ rank-order filter banks (running median, minimum, maximum) */
+
+/*
+ * Rank-order filter bank: `channels` independent real rows, F32 or F64 (channel-major: row c =
+ * ptr[c stride .. + S) elements, strides in elements).  A plan fixes the window W and the rank r, 0 <= r < W.  A call takes S >= 0
+ * samples per row, out of place.  With x_c = the row's history followed by the call's block,
+ *     y[n] = the element of rank r, counted from 0 and ascending, of the W values x_c[n - W + 1 .. n]:
+ * r = 0 is the running minimum, r = W - 1 the running maximum, r = (W - 1) / 2 with odd W the running median.
+ *   - order: IEEE 754 totalOrder, defined through a key.  Take the value's bits as an unsigned integer u; the key is ~u if the sign
+ *     bit is set, else u | signbit; keys compare as unsigned integers.  So -0 < +0, NaNs with the sign bit set sort below -inf, NaNs
+ *     with it clear sort above +inf, ordered by payload.  Nothing is quieted or canonicalised: the output is bit for bit one of the
+ *     W inputs.  Equal keys are identical bit patterns, so which copy is returned cannot matter.  No floating-point arithmetic
+ *     happens anywhere.
+ *   - state: one caller-owned device buffer of sdsp_hip_rank_state_bytes bytes: channels x (W - 1) elements of x history, newest
+ *     first: state[c (W - 1) + j] = x_c[-1 - j].  Read at entry, written at exit.  A zero-filled buffer is a fresh stream preceded
+ *     by zeros (+0).  NULL = zero history, nothing kept.
+ *   - there is no stream position; any split of a stream into calls (empty calls and calls shorter than W - 1 included) gives the
+ *     same bits and the same final state.  A call with S = 0 returns at once and leaves the state alone.
+ *   - y may not overlap x.  x is never written; nothing past each row's S outputs is.
+ * Limits: 1 <= W <= SDSP_HIP_RANK_MAX_WINDOW (SDSP_HIP_RANK_MAX_WINDOW_F64 for F64; W = 1 is a copy), 1 <= channels < 2^31,
+ * S < 2^31.
+ */
+#define SDSP_HIP_RANK_MAX_WINDOW 255
+#define SDSP_HIP_RANK_MAX_WINDOW_F64 127
+#define SDSP_HIP_RANK_DEPART_TILE 0 /* the departing sample x[n - W] comes from a second staged tile of the input */
+typedef struct sdsp_hip_rank_plan sdsp_hip_rank_plan;
+/* Errors: channels or window out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, a rank >= window, a precision other than
+ * F32 / F64: SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_rank_plan_create(sdsp_hip_rank_plan **plan, uint64_t channels, uint32_t window, uint32_t rank, int precision, int device);
+int sdsp_hip_rank_plan_destroy(sdsp_hip_rank_plan *plan);
+/*
+ * x, y: DEVICE pointers; state: DEVICE pointer or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one call
+ * per plan in flight.  Errors: null plan, x or y, a stride < samples with more than one channel, overlapping ranges, misaligned
+ * pointers: SDSP_HIP_ERR_INVALID_ARG; samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; a grid that does not fit one launch:
+ * SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_rank_process(sdsp_hip_rank_plan *plan, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, uint64_t samples,
+                          void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_rank_process_host(sdsp_hip_rank_plan *plan, const void *host_x, uint64_t x_stride, void *host_y, uint64_t y_stride,
+                               uint64_t samples, void *host_state);
+/* bytes of the plan's state buffer: channels (W - 1) element size */
+int sdsp_hip_rank_state_bytes(const sdsp_hip_rank_plan *plan, uint64_t *bytes);
+/* kernel variants (identical bits): 0 = sdsp_rank_kernel (a lane per run of consecutive outputs, the window as a sorted array of keys
+ * in registers, one delete-and-insert pass per output, rows transposed through LDS); 1 = sdsp_rank_plain_kernel, one thread per output
+ * from global memory, selection by counting in O(W^2) (the cross-check; it shares no logic with variant 0). */
+int sdsp_hip_rank_plan_set_variant(sdsp_hip_rank_plan *plan, int variant);
+/* outputs per lane of sdsp_rank_kernel.  0 (the default) = chosen per call from channels, S and W: enough lanes to fill the device at
+ * the kernel's occupancy, runs of at least 4 W, a multiple of 16.  Any other value is taken as it is (capped at S).  The bits do not
+ * depend on it; the override exists for tests and benchmarks.  run >= 2^31: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_rank_plan_set_run(sdsp_hip_rank_plan *plan, uint64_t run);
+/* kernel launches of one process call with a state buffer: the filter kernel, and one for the new history when W > 1; 0 for
+ * samples == 0 */
+int sdsp_hip_rank_plan_launches(const sdsp_hip_rank_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint64_t channels;
+    uint32_t window, rank;
+    uint32_t padded;    /* WP: the compile-time size of the sorted array (8, 16 .. 256), W keys and WP - W sentinels above them */
+    uint32_t out_index; /* the array index the output is read from (the rank: no sentinels lie below the window) */
+    uint32_t run;       /* set_run's value; 0 = automatic */
+    uint32_t last_run;  /* the run the latest call of variant 0 took; 0 before the first */
+    uint32_t block;     /* samples per staging block of sdsp_rank_kernel */
+    uint32_t lds_bytes; /* LDS of one workgroup (one wave, 64 runs) of sdsp_rank_kernel; it does not depend on W */
+    int departing;      /* where x[n - W] comes from: SDSP_HIP_RANK_DEPART_TILE for every window */
+    int precision, device, variant;
+    char kernel[64];    /* the kernel the plan's variant runs */
+} sdsp_hip_rank_plan_info;
+int sdsp_hip_rank_plan_get_info(const sdsp_hip_rank_plan *plan, sdsp_hip_rank_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

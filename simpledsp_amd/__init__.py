@@ -30,6 +30,7 @@ from .cic_interp import cic_interpolator, cic_interp_growth, cic_interp_unity_sc
 from .duc import duc_bank
 from .beamformer import beamformer_bank, beam_delay_taps, plane_wave_delays
 from .lms import lms_bank
+from .rank_filter import rank_filter_bank, medfilt
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

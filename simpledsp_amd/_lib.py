@@ -191,6 +191,14 @@ class LmsPlanInfo(C.Structure):
     ]
 
 
+class RankPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels", C.c_uint64), ("window", C.c_uint32), ("rank", C.c_uint32), ("padded", C.c_uint32), ("out_index", C.c_uint32),
+        ("run", C.c_uint32), ("last_run", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint32), ("departing", C.c_int),
+        ("precision", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
 CIC_REAL, CIC_COMPLEX = 0, 1
 CIC_I16, CIC_I32 = 0, 1
 CIC_OUT_INT, CIC_OUT_F32 = 0, 1
@@ -207,6 +215,7 @@ BEAM_MAX_TAPS, BEAM_MAX_DELAY, BEAM_MAX_ROWS, BEAM_MAX_ENTRIES = 256, 65535, 409
 LMS_REAL, LMS_COMPLEX = 0, 1
 LMS_LMS, LMS_NLMS = 0, 1
 LMS_MAX_TAPS, LMS_MAX_TAPS_F64_COMPLEX = 64, 32
+RANK_MAX_WINDOW, RANK_MAX_WINDOW_F64 = 255, 127
 PFB_REAL, PFB_COMPLEX = 0, 1
 PFB_PHASE_FRAME, PFB_PHASE_TIME = 0, 1
 PFB_MAX_TAPS_PER_CHANNEL, PFB_MAX_TAPS = 64, 1 << 20
@@ -427,6 +436,15 @@ SIGNATURES = {
     "sdsp_hip_lms_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_lms_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_lms_plan_get_info": (_i, [_vp, C.POINTER(LmsPlanInfo)]),
+    "sdsp_hip_rank_plan_create": (_i, [_pp, _u64, _u32, _u32, _i, _i]),
+    "sdsp_hip_rank_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_rank_process": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_rank_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_rank_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_rank_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_rank_plan_set_run": (_i, [_vp, _u64]),
+    "sdsp_hip_rank_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_rank_plan_get_info": (_i, [_vp, C.POINTER(RankPlanInfo)]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -521,6 +521,14 @@ struct sdsp_hip_lms_plan {
     int kind = 0, precision = 0, mode = 0, device = 0, variant = 0;
     double eps = 0.0;          // rounded to the plan precision
     void *scratch_w = nullptr; // channels x taps weights for the plain kernel of a call without state; made by set_variant(1)
+};
+
+struct sdsp_hip_rank_plan {
+    uint64_t channels = 0;
+    uint32_t window = 0, rank = 0;
+    uint32_t run = 0;      // set_run's override; 0 = chosen per call
+    uint32_t last_run = 0; // what the latest call of variant 0 took
+    int precision = 0, device = 0, variant = 0;
 };
 
 struct sdsp_hip_arb_plan {
@@ -5852,6 +5860,182 @@ int sdsp_hip_lms_process_host(sdsp_hip_lms_plan *p, const void *host_x, uint64_t
     if (!rc)
         rc = lms_run(p, st.dev[0], x_stride, st.dev[1], d_stride, st.dev[2], y_stride, st.dev[3], e_stride, samples, mu, st.dev[4],
                      nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ rank-order filter banks (rank_filter.hip)
+
+namespace
+{
+// argument checks shared by process and process_host (device pointers or not)
+int rank_check(const sdsp_hip_rank_plan *p, const void *x, uint64_t x_stride, const void *y, uint64_t y_stride, uint64_t samples)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!x || !y)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x or y is null");
+    if (p->channels > 1 && (x_stride < samples || y_stride < samples))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "every stride must be >= samples");
+    return SDSP_HIP_OK;
+}
+
+uint32_t rank_run_for(const sdsp_hip_rank_plan *p, uint64_t samples)
+{
+    if (p->run)
+        return static_cast<uint32_t>(p->run < samples ? p->run : samples);
+    return rank_auto_run(p->precision, p->channels, samples, p->window);
+}
+
+int rank_run(sdsp_hip_rank_plan *p, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, uint64_t samples, void *state,
+             hipStream_t stream)
+{
+    rank_args a{};
+    a.x = x;
+    a.y = y;
+    a.hist = p->window > 1 ? state : nullptr;
+    a.channels = p->channels;
+    a.samples = samples;
+    a.x_stride = x_stride;
+    a.y_stride = y_stride;
+    a.window = p->window;
+    a.rank = p->rank;
+    a.run = rank_run_for(p, samples);
+    if (p->variant == 0)
+        p->last_run = a.run;
+    if (int rc = launch_rank(p->precision, a, p->variant, stream))
+        return rc;
+    // behind the kernel: it reads the old history
+    return carry_history(p->precision, static_cast<uint32_t>(real_size(p->precision)), x, x_stride, const_cast<void *>(a.hist), p->channels,
+                         samples, p->window - 1, stream, "rank");
+}
+} // namespace
+
+int sdsp_hip_rank_plan_create(sdsp_hip_rank_plan **out, uint64_t channels, uint32_t window, uint32_t rank, int precision, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (channels == 0 || channels > 0x7fffffffull)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be in [1, 2^31)");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (window == 0 || window > (precision == SDSP_HIP_F64 ? SDSP_HIP_RANK_MAX_WINDOW_F64 : SDSP_HIP_RANK_MAX_WINDOW))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "window must be in [1, SDSP_HIP_RANK_MAX_WINDOW] (SDSP_HIP_RANK_MAX_WINDOW_F64 for F64)");
+    if (rank >= window)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "rank must be below the window");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_rank_plan();
+    p->channels = channels;
+    p->window = window;
+    p->rank = rank;
+    p->precision = precision;
+    p->device = device;
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_plan_destroy(sdsp_hip_rank_plan *p)
+{
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_state_bytes(const sdsp_hip_rank_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = p->channels * (p->window - 1ull) * real_size(p->precision);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_plan_set_variant(sdsp_hip_rank_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_plan_set_run(sdsp_hip_rank_plan *p, uint64_t run)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (run >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "run must be below 2^31");
+    p->run = static_cast<uint32_t>(run);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_plan_launches(const sdsp_hip_rank_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = samples ? 1 + (p->window > 1 ? 1 : 0) : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_plan_get_info(const sdsp_hip_rank_plan *p, sdsp_hip_rank_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->channels = p->channels;
+    info->window = p->window;
+    info->rank = p->rank;
+    info->padded = rank_padded(p->window);
+    info->out_index = p->rank;
+    info->run = p->run;
+    info->last_run = p->last_run;
+    info->block = rank_block(p->precision);
+    info->lds_bytes = rank_lds_bytes(p->precision);
+    info->departing = SDSP_HIP_RANK_DEPART_TILE;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, rank_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rank_process(sdsp_hip_rank_plan *p, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, uint64_t samples,
+                          void *state, void *stream)
+{
+    if (int rc = rank_check(p, x, x_stride, y, y_stride, samples))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = real_size(p->precision);
+    auto span = [&](uint64_t stride) { return ((p->channels - 1) * stride + samples) * es; };
+    if (ranges_overlap(x, span(x_stride), y, span(y_stride)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the y range overlaps the x range (the rank filter runs out of place)");
+    if (misaligned(x, es) || misaligned(y, es) || misaligned(state, es))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x, y and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return rank_run(p, x, x_stride, y, y_stride, samples, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_rank_process_host(sdsp_hip_rank_plan *p, const void *host_x, uint64_t x_stride, void *host_y, uint64_t y_stride,
+                               uint64_t samples, void *host_state)
+{
+    if (int rc = rank_check(p, host_x, x_stride, host_y, y_stride, samples))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t es = real_size(p->precision);
+    auto span = [&](uint64_t stride) { return static_cast<size_t>(((p->channels - 1) * stride + samples) * es); };
+    uint64_t state_bytes = 0;
+    sdsp_hip_rank_state_bytes(p, &state_bytes);
+    host_stage st("rank", { { host_x, span(x_stride), false }, { host_y, span(y_stride), true },
+                        { host_state, static_cast<size_t>(state_bytes), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = rank_run(p, st.dev[0], x_stride, st.dev[1], y_stride, samples, st.dev[2], nullptr);
     return st.out(rc);
 }
 }

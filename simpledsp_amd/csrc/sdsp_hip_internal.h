@@ -415,6 +415,23 @@ const char *lms_kernel_for(int variant);
 // samples per time block of sdsp_lms_kernel and its LDS bytes per workgroup (one wave), for this kind, precision and tap count
 uint32_t lms_block(int precision, int complex_in, uint32_t taps);
 uint32_t lms_lds_bytes(int precision, int complex_in, uint32_t taps);
+// rank-order filter banks (rank_filter.hip): the one launch of a call, in front of carry_history
+struct rank_args {
+    const void *x;
+    void *y;
+    const void *hist; // nullable; channels x (window - 1) elements of x, newest first
+    uint64_t channels, samples, x_stride, y_stride;
+    uint32_t window, rank;
+    uint32_t run; // outputs per lane of sdsp_rank_kernel, 1 .. samples (unused by the plain kernel)
+};
+int launch_rank(int precision, const rank_args &a, int variant, void *stream);
+const char *rank_kernel_for(int variant);
+// the sorted array's compile-time size for a window, the samples per staging block and the LDS bytes per workgroup (one wave) of
+// sdsp_rank_kernel, and the run it takes by default for a call's shape
+uint32_t rank_padded(uint32_t window);
+uint32_t rank_block(int precision);
+uint32_t rank_lds_bytes(int precision);
+uint32_t rank_auto_run(int precision, uint64_t channels, uint64_t samples, uint32_t window);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
