@@ -1655,6 +1655,101 @@ typedef struct {
 } sdsp_hip_rank_plan_info;
 int sdsp_hip_rank_plan_get_info(const sdsp_hip_rank_plan *plan, sdsp_hip_rank_plan_info *info);
 
+/* ------------------------------------------------------------------ CFAR detector banks (CA, GO, SO and OS thresholds) */
+
+/*
+ * Constant-false-alarm-rate detector bank: `channels` independent rows, F32 or F64 (channel-major: row c =
+ * ptr[c stride .. + S) elements, strides in elements of the row's kind).  A plan fixes train = L (training cells per side), guard = G
+ * (guard cells per side), a mode, the OS rank k, the input kind and the factor alpha.  Let half = L + G, W = 2 half + 1 and p_c = the
+ * powers of the row's history followed by those of the call's block.  For every input sample n the cell under test is p[n - half]: the
+ * bank is causal with a delay of half samples.
+ *   - input kinds.  POWER: real rows, used as they are; no value is rejected (negative values, NaN and inf go through the arithmetic
+ *     below).  IQ: interleaved I/Q rows (one complex sample is one element), p = fl(fl(re re) + fl(im im)): two products and a sum,
+ *     never an FMA -- the bits of the STFT bank's power output.
+ *   - training cells: lag (older) = p[n - W + 1 .. n - W + L], lead (newer) = p[n - L + 1 .. n].
+ *   - modes; c is a host double rounded once to the precision.
+ *       CA: lag = (((+0 + p[n - W + 1]) + p[n - W + 2]) + ..) in ascending index, lead likewise;
+ *           thr = fl(fl(lag + lead) c), c = alpha / (2 L).
+ *       GO: v = (lag > lead) ? lag : lead, thr = fl(v c), c = alpha / L.     SO: v = (lag < lead) ? lag : lead, the same c.
+ *       OS: v = the element of rank k (from 0, ascending, IEEE 754 totalOrder through the rank bank's key) of the 2 L training cells;
+ *           thr = fl(v alpha).
+ *   - a threshold that is a NaN is written as the canonical quiet NaN (0x7FC00000, F64: 0x7FF8000000000000): IEEE 754 leaves the
+ *     sign and payload of a NaN result to the implementation, so this is what makes "the same bits" below hold for such rows too,
+ *     across kernel variants, runs and splits.  Every other threshold, infinities and signed zeros included, is the arithmetic's.
+ *   - detection: det[n] = (p[n - half] > thr[n]) ? 1 : 0, one byte.  A NaN on either side gives 0.
+ *   - outputs: thr (a row of the precision) and det (a row of uint8_t, stride in bytes).  Either may be NULL and is then not written;
+ *     both NULL is an error.  Outputs may not overlap x or each other; x is never written; nothing past each row's S outputs is.
+ *   - state: one caller-owned device buffer of sdsp_hip_cfar_state_bytes bytes: channels x (W - 1) elements of the input's kind,
+ *     newest first: state[c (W - 1) + j] = x_c[-1 - j].  Read at entry, written at exit.  A zero-filled buffer is a fresh stream
+ *     preceded by zeros.  NULL = zero history, nothing kept.
+ *   - there is no stream position; any split of a stream into calls (empty calls included) gives the same bits and the same final
+ *     state.  A call with S = 0 returns at once and leaves the state alone.
+ * Limits: 1 <= L <= SDSP_HIP_CFAR_MAX_TRAIN; in OS mode 2 L <= SDSP_HIP_RANK_MAX_WINDOW (SDSP_HIP_RANK_MAX_WINDOW_F64 for F64), the rank
+ * bank's register limits; 0 <= G <= SDSP_HIP_CFAR_MAX_GUARD; 0 <= k < 2 L; 1 <= channels < 2^31; S < 2^31.
+ */
+#define SDSP_HIP_CFAR_CA 0
+#define SDSP_HIP_CFAR_GO 1
+#define SDSP_HIP_CFAR_SO 2
+#define SDSP_HIP_CFAR_OS 3
+#define SDSP_HIP_CFAR_POWER 0
+#define SDSP_HIP_CFAR_IQ 1
+#define SDSP_HIP_CFAR_MAX_TRAIN 128
+#define SDSP_HIP_CFAR_MAX_GUARD 255
+typedef struct sdsp_hip_cfar_plan sdsp_hip_cfar_plan;
+typedef struct {
+    uint32_t train, guard;
+    int mode;      /* SDSP_HIP_CFAR_CA / GO / SO / OS */
+    uint32_t rank; /* OS only (ignored otherwise) */
+    int input;     /* SDSP_HIP_CFAR_POWER / IQ */
+    double alpha;
+} sdsp_hip_cfar_desc;
+/* Errors: channels, train or guard out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an unknown mode or input kind, in OS mode
+ * a rank >= 2 train, a precision other than F32 / F64: SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_cfar_plan_create(sdsp_hip_cfar_plan **plan, uint64_t channels, const sdsp_hip_cfar_desc *desc, int precision, int device);
+int sdsp_hip_cfar_plan_destroy(sdsp_hip_cfar_plan *plan);
+/*
+ * x: DEVICE pointer; thr, det, state: DEVICE pointers or NULL.  Asynchronous on `stream`, allocates nothing (stream-capturable); one
+ * call per plan in flight.  Errors: null plan or x, thr and det both null, a stride < samples with more than one channel, overlapping
+ * ranges, pointers not aligned to their element size: SDSP_HIP_ERR_INVALID_ARG; samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; a grid
+ * that does not fit one launch: SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: nothing to do.
+ */
+int sdsp_hip_cfar_process(sdsp_hip_cfar_plan *plan, const void *x, uint64_t x_stride, void *thr, uint64_t thr_stride, uint8_t *det,
+                          uint64_t det_stride, uint64_t samples, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_cfar_process_host(sdsp_hip_cfar_plan *plan, const void *host_x, uint64_t x_stride, void *host_thr, uint64_t thr_stride,
+                               uint8_t *host_det, uint64_t det_stride, uint64_t samples, void *host_state);
+/* bytes of the plan's state buffer: channels (W - 1) element size of the input's kind */
+int sdsp_hip_cfar_state_bytes(const sdsp_hip_cfar_plan *plan, uint64_t *bytes);
+/* alpha for later calls; the state is left alone */
+int sdsp_hip_cfar_plan_set_alpha(sdsp_hip_cfar_plan *plan, double alpha);
+/* kernel variants (identical bits): 0 = sdsp_cfar_sum_kernel for CA, GO and SO (a workgroup per row segment, powers and one boxcar per
+ * position in LDS, eight consecutive boxcars per thread in registers: L additions per output) and sdsp_cfar_os_kernel for OS (the rank
+ * bank's lane per run with the 2 L training keys as a sorted array in registers, two delete-and-insert passes per output);
+ * 1 = sdsp_cfar_plain_kernel, one thread per output from global memory, plain loops and selection by counting (the cross-check; it
+ * shares no logic with variant 0). */
+int sdsp_hip_cfar_plan_set_variant(sdsp_hip_cfar_plan *plan, int variant);
+/* outputs per workgroup (sum modes, capped at info.block) or per lane (OS) of variant 0.  0 (the default) = chosen per call from
+ * channels, S and W.  The bits do not depend on it; the override exists for tests and benchmarks.  run >= 2^31:
+ * SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_cfar_plan_set_run(sdsp_hip_cfar_plan *plan, uint64_t run);
+/* kernel launches of one process call with a state buffer: the detector kernel and one for the new history; 0 for samples == 0 */
+int sdsp_hip_cfar_plan_launches(const sdsp_hip_cfar_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint64_t channels;
+    uint32_t train, guard, half, window; /* half = L + G, window = W = 2 half + 1 */
+    uint32_t lag_shift;                  /* D = L + 2 G + 1: the lag sum at n is the lead sum at n - D */
+    uint32_t rank;                       /* OS only */
+    uint32_t padded;                     /* OS: WP, the compile-time size of the sorted array (8, 16 .. 256); else 0 */
+    uint32_t run;                        /* set_run's value; 0 = automatic */
+    uint32_t last_run;                   /* the run the latest call of variant 0 took; 0 before the first */
+    uint32_t block;                      /* sum modes: the largest segment of a workgroup; OS: samples per staging block */
+    uint32_t lds_bytes;                  /* LDS of one workgroup of the variant-0 kernel */
+    double alpha, scale;                 /* alpha as given; c (OS: alpha) as rounded to the precision */
+    int mode, input, precision, device, variant;
+    char kernel[64];                     /* the kernel the plan's variant runs */
+} sdsp_hip_cfar_plan_info;
+int sdsp_hip_cfar_plan_get_info(const sdsp_hip_cfar_plan *plan, sdsp_hip_cfar_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,24 @@ class RankPlanInfo(C.Structure):
     ]
 
 
+class CfarDesc(C.Structure):
+    _fields_ = [
+        ("train", C.c_uint32), ("guard", C.c_uint32), ("mode", C.c_int), ("rank", C.c_uint32), ("input", C.c_int), ("alpha", C.c_double),
+    ]
+
+
+class CfarPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels", C.c_uint64), ("train", C.c_uint32), ("guard", C.c_uint32), ("half", C.c_uint32), ("window", C.c_uint32),
+        ("lag_shift", C.c_uint32), ("rank", C.c_uint32), ("padded", C.c_uint32), ("run", C.c_uint32), ("last_run", C.c_uint32),
+        ("block", C.c_uint32), ("lds_bytes", C.c_uint32), ("alpha", C.c_double), ("scale", C.c_double), ("mode", C.c_int),
+        ("input", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
+CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3
+CFAR_POWER, CFAR_IQ = 0, 1
+CFAR_MAX_TRAIN, CFAR_MAX_GUARD = 128, 255
 CIC_REAL, CIC_COMPLEX = 0, 1
 CIC_I16, CIC_I32 = 0, 1
 CIC_OUT_INT, CIC_OUT_F32 = 0, 1
@@ -445,6 +463,16 @@ SIGNATURES = {
     "sdsp_hip_rank_plan_set_run": (_i, [_vp, _u64]),
     "sdsp_hip_rank_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_rank_plan_get_info": (_i, [_vp, C.POINTER(RankPlanInfo)]),
+    "sdsp_hip_cfar_plan_create": (_i, [_pp, _u64, C.POINTER(CfarDesc), _i, _i]),
+    "sdsp_hip_cfar_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_cfar_process": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp, _vp]),
+    "sdsp_hip_cfar_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_cfar_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_cfar_plan_set_alpha": (_i, [_vp, _d]),
+    "sdsp_hip_cfar_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_cfar_plan_set_run": (_i, [_vp, _u64]),
+    "sdsp_hip_cfar_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_cfar_plan_get_info": (_i, [_vp, C.POINTER(CfarPlanInfo)]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -529,6 +529,15 @@ struct sdsp_hip_rank_plan {
     uint32_t run = 0;      // set_run's override; 0 = chosen per call
     uint32_t last_run = 0; // what the latest call of variant 0 took
     int precision = 0, device = 0, variant = 0;
+};
+
+struct sdsp_hip_cfar_plan {
+    uint64_t channels = 0;
+    uint32_t train = 0, guard = 0, rank = 0;
+    uint32_t run = 0;      // set_run's override; 0 = chosen per call
+    uint32_t last_run = 0; // what the latest call of variant 0 took
+    int mode = 0, input = 0, precision = 0, device = 0, variant = 0;
+    double alpha = 0.0, scale = 0.0; // scale: c of the mode, rounded to the precision
 };
 
 struct sdsp_hip_arb_plan {
@@ -6036,6 +6045,237 @@ int sdsp_hip_rank_process_host(sdsp_hip_rank_plan *p, const void *host_x, uint64
     int rc = st.in();
     if (!rc)
         rc = rank_run(p, st.dev[0], x_stride, st.dev[1], y_stride, samples, st.dev[2], nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ CFAR detector banks (cfar.hip)
+
+namespace
+{
+uint32_t cfar_hist(const sdsp_hip_cfar_plan *p) { return 2 * (p->train + p->guard); }
+uint64_t cfar_in_esize(const sdsp_hip_cfar_plan *p) { return real_size(p->precision) * (p->input == SDSP_HIP_CFAR_IQ ? 2u : 1u); }
+
+// c of the mode from alpha: a host double rounded once to the precision
+double cfar_scale(int mode, uint32_t train, double alpha, int precision)
+{
+    const double c = mode == SDSP_HIP_CFAR_CA ? alpha / (2.0 * train) : mode == SDSP_HIP_CFAR_OS ? alpha : alpha / train;
+    return precision == SDSP_HIP_F64 ? c : static_cast<double>(static_cast<float>(c));
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int cfar_check(const sdsp_hip_cfar_plan *p, const void *x, uint64_t x_stride, const void *thr, uint64_t thr_stride, const void *det,
+               uint64_t det_stride, uint64_t samples)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!thr && !det)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "thr and det are both null: nothing to write");
+    if (!x)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x is null");
+    if (p->channels > 1 && (x_stride < samples || (thr && thr_stride < samples) || (det && det_stride < samples)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "every stride must be >= samples");
+    return SDSP_HIP_OK;
+}
+
+uint32_t cfar_run_for(const sdsp_hip_cfar_plan *p, uint64_t samples)
+{
+    uint64_t run = p->run ? p->run : cfar_auto_run(p->precision, p->mode, p->channels, samples, p->train, p->guard);
+    if (p->mode != SDSP_HIP_CFAR_OS && run > cfar_block(p->precision, p->mode))
+        run = cfar_block(p->precision, p->mode);
+    return static_cast<uint32_t>(run < samples ? run : samples);
+}
+
+int cfar_run(sdsp_hip_cfar_plan *p, const void *x, uint64_t x_stride, void *thr, uint64_t thr_stride, void *det, uint64_t det_stride,
+             uint64_t samples, void *state, hipStream_t stream)
+{
+    cfar_args a{};
+    a.x = x;
+    a.thr = thr;
+    a.det = det;
+    a.hist = state;
+    a.channels = p->channels;
+    a.samples = samples;
+    a.x_stride = x_stride;
+    a.thr_stride = thr_stride;
+    a.det_stride = det_stride;
+    a.train = p->train;
+    a.guard = p->guard;
+    a.rank = p->rank;
+    a.mode = p->mode;
+    a.iq = p->input == SDSP_HIP_CFAR_IQ;
+    a.scale = p->scale;
+    a.run = cfar_run_for(p, samples);
+    if (p->variant == 0)
+        p->last_run = a.run;
+    if (int rc = launch_cfar(p->precision, a, p->variant, stream))
+        return rc;
+    // behind the kernel: it reads the old history
+    return carry_history(p->precision, static_cast<uint32_t>(cfar_in_esize(p)), x, x_stride, state, p->channels, samples, cfar_hist(p),
+                         stream, "cfar");
+}
+} // namespace
+
+int sdsp_hip_cfar_plan_create(sdsp_hip_cfar_plan **out, uint64_t channels, const sdsp_hip_cfar_desc *d, int precision, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (!d)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "descriptor is null");
+    if (channels == 0 || channels > 0x7fffffffull)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be in [1, 2^31)");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (d->mode < SDSP_HIP_CFAR_CA || d->mode > SDSP_HIP_CFAR_OS)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mode must be SDSP_HIP_CFAR_CA, GO, SO or OS");
+    if (d->input != SDSP_HIP_CFAR_POWER && d->input != SDSP_HIP_CFAR_IQ)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "input must be SDSP_HIP_CFAR_POWER or SDSP_HIP_CFAR_IQ");
+    if (d->train == 0 || d->train > SDSP_HIP_CFAR_MAX_TRAIN)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "train must be in [1, SDSP_HIP_CFAR_MAX_TRAIN]");
+    if (d->guard > SDSP_HIP_CFAR_MAX_GUARD)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "guard must be in [0, SDSP_HIP_CFAR_MAX_GUARD]");
+    if (d->mode == SDSP_HIP_CFAR_OS) {
+        if (2 * d->train > (precision == SDSP_HIP_F64 ? SDSP_HIP_RANK_MAX_WINDOW_F64 : SDSP_HIP_RANK_MAX_WINDOW))
+            return fail(SDSP_HIP_ERR_INVALID_SIZE,
+                        "OS: 2 train must be at most SDSP_HIP_RANK_MAX_WINDOW (SDSP_HIP_RANK_MAX_WINDOW_F64 for F64)");
+        if (d->rank >= 2 * d->train)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "rank must be below 2 train");
+    }
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_cfar_plan();
+    p->channels = channels;
+    p->train = d->train;
+    p->guard = d->guard;
+    p->mode = d->mode;
+    p->rank = d->mode == SDSP_HIP_CFAR_OS ? d->rank : 0;
+    p->input = d->input;
+    p->alpha = d->alpha;
+    p->scale = cfar_scale(d->mode, d->train, d->alpha, precision);
+    p->precision = precision;
+    p->device = device;
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_plan_destroy(sdsp_hip_cfar_plan *p)
+{
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_state_bytes(const sdsp_hip_cfar_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = p->channels * cfar_hist(p) * cfar_in_esize(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_plan_set_alpha(sdsp_hip_cfar_plan *p, double alpha)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    p->alpha = alpha;
+    p->scale = cfar_scale(p->mode, p->train, alpha, p->precision);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_plan_set_variant(sdsp_hip_cfar_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_plan_set_run(sdsp_hip_cfar_plan *p, uint64_t run)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (run >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "run must be below 2^31");
+    p->run = static_cast<uint32_t>(run);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_plan_launches(const sdsp_hip_cfar_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = samples ? 2 : 0; // W - 1 >= 2: there is always a history to carry
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_plan_get_info(const sdsp_hip_cfar_plan *p, sdsp_hip_cfar_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->channels = p->channels;
+    info->train = p->train;
+    info->guard = p->guard;
+    info->half = p->train + p->guard;
+    info->window = 2 * info->half + 1;
+    info->lag_shift = p->train + 2 * p->guard + 1;
+    info->rank = p->rank;
+    info->padded = p->mode == SDSP_HIP_CFAR_OS ? cfar_padded(2 * p->train) : 0;
+    info->run = p->run;
+    info->last_run = p->last_run;
+    info->block = cfar_block(p->precision, p->mode);
+    info->lds_bytes = cfar_lds_bytes(p->precision, p->mode);
+    info->alpha = p->alpha;
+    info->scale = p->scale;
+    info->mode = p->mode;
+    info->input = p->input;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, cfar_kernel_for(p->variant, p->mode), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar_process(sdsp_hip_cfar_plan *p, const void *x, uint64_t x_stride, void *thr, uint64_t thr_stride, uint8_t *det,
+                          uint64_t det_stride, uint64_t samples, void *state, void *stream)
+{
+    if (int rc = cfar_check(p, x, x_stride, thr, thr_stride, det, det_stride, samples))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = real_size(p->precision), xs = cfar_in_esize(p);
+    auto span = [&](uint64_t stride, uint64_t bytes) { return ((p->channels - 1) * stride + samples) * bytes; };
+    if (ranges_overlap(x, span(x_stride, xs), thr, span(thr_stride, es)) || ranges_overlap(x, span(x_stride, xs), det, span(det_stride, 1)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "an output range overlaps the x range (the detector runs out of place)");
+    if (ranges_overlap(thr, span(thr_stride, es), det, span(det_stride, 1)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the thr and det ranges overlap");
+    if (misaligned(x, xs) || misaligned(thr, es) || misaligned(state, xs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x, thr and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return cfar_run(p, x, x_stride, thr, thr_stride, det, det_stride, samples, state, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_cfar_process_host(sdsp_hip_cfar_plan *p, const void *host_x, uint64_t x_stride, void *host_thr, uint64_t thr_stride,
+                               uint8_t *host_det, uint64_t det_stride, uint64_t samples, void *host_state)
+{
+    if (int rc = cfar_check(p, host_x, x_stride, host_thr, thr_stride, host_det, det_stride, samples))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t es = real_size(p->precision), xs = cfar_in_esize(p);
+    auto span = [&](uint64_t stride, uint64_t bytes) { return static_cast<size_t>(((p->channels - 1) * stride + samples) * bytes); };
+    uint64_t state_bytes = 0;
+    sdsp_hip_cfar_state_bytes(p, &state_bytes);
+    host_stage st("cfar", { { host_x, span(x_stride, xs), false }, { host_thr, span(thr_stride, es), true },
+                        { host_det, span(det_stride, 1), true }, { host_state, static_cast<size_t>(state_bytes), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = cfar_run(p, st.dev[0], x_stride, st.dev[1], thr_stride, st.dev[2], det_stride, samples, st.dev[3], nullptr);
     return st.out(rc);
 }
 }

@@ -432,6 +432,25 @@ uint32_t rank_padded(uint32_t window);
 uint32_t rank_block(int precision);
 uint32_t rank_lds_bytes(int precision);
 uint32_t rank_auto_run(int precision, uint64_t channels, uint64_t samples, uint32_t window);
+// CFAR detector banks (cfar.hip): the one launch of a call, in front of carry_history
+struct cfar_args {
+    const void *x;
+    void *thr, *det;  // nullable: not written (det: bytes)
+    const void *hist; // nullable; channels x 2 (train + guard) elements of the input's kind, newest first
+    uint64_t channels, samples, x_stride, thr_stride, det_stride;
+    uint32_t train, guard, rank;
+    int mode, iq;
+    double scale; // c of the mode (OS: alpha), rounded to the precision
+    uint32_t run; // outputs per workgroup (sum modes) or per lane (OS) of variant 0, 1 .. samples (unused by the plain kernel)
+};
+int launch_cfar(int precision, const cfar_args &a, int variant, void *stream);
+const char *cfar_kernel_for(int variant, int mode);
+// the sorted array's compile-time size for 2 L training cells, the block (sum modes: the largest segment; OS: samples per staging
+// block) and the LDS bytes per workgroup of the variant-0 kernel, and the run it takes by default for a call's shape
+uint32_t cfar_padded(uint32_t cells);
+uint32_t cfar_block(int precision, int mode);
+uint32_t cfar_lds_bytes(int precision, int mode);
+uint32_t cfar_auto_run(int precision, int mode, uint64_t channels, uint64_t samples, uint32_t train, uint32_t guard);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
