@@ -1,0 +1,156 @@
+// sdsp/pll.h -- carrier-recovery PLL / Costas loop bank for the MI355X engine (sdsp_hip_pll_*).
+//
+// `channels` independent second-order loops on interleaved I/Q rows: process() de-rotates every row with its own 32-bit numerically
+// controlled oscillator, measures the phase error with the bank's detector and steers the oscillator through a proportional-plus-
+// integral loop filter whose gains alpha and beta are arguments of the call; it writes the de-rotated rows y, the detector output err
+// and the tracked frequency offset freq (cycles per sample), any of which may be left out.  Mirrors sdsp::lms_bank (sdsp/lms.h): RAII
+// plan and device-resident state, process() on device pointers, process_host() for host buffers.  The state holds the integrators
+// (channels reals), then the phase words (channels uint32); freq(), phase(), set_freq() and set_phase() copy them.  No reference
+// counterpart: pinned to tests/pll_ref.py.  There is no CPU path.
+#ifndef SDSP_MI355X_PLL_H
+#define SDSP_MI355X_PLL_H
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "detail/hip_runtime.h"
+
+namespace sdsp
+{
+template <typename real_t = float> class pll_bank {
+public:
+    // mode: SDSP_HIP_PLL_CROSS, SDSP_HIP_PLL_BPSK or SDSP_HIP_PLL_QPSK; fcw0: the centre-frequency words of sdsp_hip_ddc_phase_word, one
+    // per channel; max_dev in (0, 0.5] cycles per sample bounds the integrator
+    pll_bank(std::uint64_t channels, int mode, const std::vector<std::uint32_t> &fcw0, double max_dev = 0.5, int device = 0)
+        : m_channels(channels), m_device(device)
+    {
+        detail::check(sdsp_hip_pll_plan_create(&m_plan, channels, detail::precision_of<real_t>::value, mode, fcw0.data(), fcw0.size(), max_dev,
+                                               device));
+    }
+    // one centre-frequency word shared by every channel
+    pll_bank(std::uint64_t channels, int mode, std::uint32_t fcw0, double max_dev = 0.5, int device = 0)
+        : m_channels(channels), m_device(device)
+    {
+        detail::check(sdsp_hip_pll_plan_create(&m_plan, channels, detail::precision_of<real_t>::value, mode, &fcw0, 1, max_dev, device));
+    }
+    ~pll_bank()
+    {
+        if (m_plan)
+            sdsp_hip_pll_plan_destroy(m_plan);
+        if (m_state)
+            sdsp_hip_free(m_state, m_device);
+    }
+    pll_bank(const pll_bank &) = delete;
+    pll_bank &operator=(const pll_bank &) = delete;
+
+    // zero integrators, phase 0
+    void reset()
+    {
+        if (m_state)
+            zero_state();
+    }
+
+    // device pointers (channel-major rows: x and y of I/Q pairs, err and freq of reals, strides in elements; y, err and freq may be null,
+    // y may be x), asynchronous on `stream`; continues every channel's loop
+    void process(const real_t *device_x, std::uint64_t x_stride, real_t *device_y, std::uint64_t y_stride, real_t *device_err,
+                 std::uint64_t err_stride, real_t *device_freq, std::uint64_t freq_stride, std::uint64_t samples, double alpha, double beta,
+                 void *stream = nullptr)
+    {
+        ensure_state();
+        detail::check(sdsp_hip_pll_process(m_plan, device_x, x_stride, device_y, y_stride, device_err, err_stride, device_freq, freq_stride,
+                                           samples, alpha, beta, m_state, stream));
+    }
+    // host pointers: contiguous channels x samples elements each (x and y: interleaved re, im); y, err and freq may be null
+    void process_host(const real_t *host_x, real_t *host_y, real_t *host_err, real_t *host_freq, std::uint64_t samples, double alpha,
+                      double beta)
+    {
+        ensure_state();
+        if (samples == 0)
+            return;
+        const std::size_t reals = static_cast<std::size_t>(m_channels * samples) * sizeof(real_t);
+        const std::size_t bytes[4] = { 2 * reals, 2 * reals, reals, reals };
+        void *dev[4] = { nullptr, nullptr, nullptr, nullptr };
+        void *const host_out[4] = { nullptr, host_y, host_err, host_freq };
+        int rc = 0;
+        for (int i = 0; i < 4 && !rc; i++)
+            if (i == 0 || host_out[i])
+                rc = sdsp_hip_malloc(&dev[i], bytes[i], m_device);
+        if (!rc)
+            rc = sdsp_hip_memcpy_h2d(dev[0], host_x, bytes[0], m_device);
+        if (!rc)
+            rc = sdsp_hip_pll_process(m_plan, dev[0], samples, dev[1], samples, dev[2], samples, dev[3], samples, samples, alpha, beta,
+                                      m_state, nullptr);
+        for (int i = 1; i < 4 && !rc; i++)
+            if (host_out[i])
+                rc = sdsp_hip_memcpy_d2h(host_out[i], dev[i], bytes[i], m_device);
+        for (void *p : dev)
+            if (p)
+                sdsp_hip_free(p, m_device);
+        detail::check(rc);
+    }
+    // the integrators, copied from the device state: the tracked frequency offsets in cycles per sample
+    std::vector<real_t> freq()
+    {
+        ensure_state();
+        std::vector<real_t> f(static_cast<std::size_t>(m_channels));
+        detail::check(sdsp_hip_memcpy_d2h(f.data(), m_state, f.size() * sizeof(real_t), m_device));
+        return f;
+    }
+    // the phase words, copied from the device state
+    std::vector<std::uint32_t> phase()
+    {
+        ensure_state();
+        std::vector<std::uint32_t> t(static_cast<std::size_t>(m_channels));
+        detail::check(sdsp_hip_memcpy_d2h(t.data(), words(), t.size() * sizeof(std::uint32_t), m_device));
+        return t;
+    }
+    // ... copied into it; the other half of the state stays
+    void set_freq(const std::vector<real_t> &f)
+    {
+        if (f.size() != m_channels)
+            throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: freq must hold one value per channel");
+        ensure_state();
+        detail::check(sdsp_hip_memcpy_h2d(m_state, f.data(), f.size() * sizeof(real_t), m_device));
+    }
+    void set_phase(const std::vector<std::uint32_t> &t)
+    {
+        if (t.size() != m_channels)
+            throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: phase must hold one word per channel");
+        ensure_state();
+        detail::check(sdsp_hip_memcpy_h2d(words(), t.data(), t.size() * sizeof(std::uint32_t), m_device));
+    }
+    std::uint64_t channels() const noexcept { return m_channels; }
+    void set_variant(int variant) { detail::check(sdsp_hip_pll_plan_set_variant(m_plan, variant)); }
+    sdsp_hip_pll_plan_info info() const
+    {
+        sdsp_hip_pll_plan_info i{};
+        detail::check(sdsp_hip_pll_plan_get_info(m_plan, &i));
+        return i;
+    }
+
+private:
+    void *words() const noexcept { return static_cast<unsigned char *>(m_state) + static_cast<std::size_t>(m_channels) * sizeof(real_t); }
+    void zero_state()
+    {
+        std::uint64_t bytes = 0;
+        detail::check(sdsp_hip_pll_state_bytes(m_plan, &bytes));
+        if (!m_state)
+            detail::check(sdsp_hip_malloc(&m_state, static_cast<std::size_t>(bytes), m_device));
+        const std::vector<unsigned char> host(static_cast<std::size_t>(bytes), 0);
+        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size(), m_device));
+    }
+    void ensure_state()
+    {
+        if (!m_state)
+            zero_state();
+    }
+
+    std::uint64_t m_channels;
+    int m_device;
+    sdsp_hip_pll_plan *m_plan{ nullptr };
+    void *m_state{ nullptr };
+};
+} // namespace sdsp
+
+#endif // SDSP_MI355X_PLL_H

@@ -1750,6 +1750,97 @@ typedef struct {
 } sdsp_hip_cfar_plan_info;
 int sdsp_hip_cfar_plan_get_info(const sdsp_hip_cfar_plan *plan, sdsp_hip_cfar_plan_info *info);
 
+/* ------------------------------------------------------------------ carrier-recovery PLL / Costas loop banks */
+
+/*
+ * Carrier-recovery bank: `channels` independent second-order phase-locked loops on interleaved I/Q rows, F32
+ * or F64 (channel-major: row c = ptr[c stride .. + S) elements, strides in elements of the row's kind: one complex sample is one
+ * element of x and y, one real is one element of err and freq).  Each loop has a numerically controlled oscillator with a 32-bit
+ * phase accumulator theta, a phase detector fixed by the plan, and a proportional-plus-integral loop filter whose gains alpha and beta
+ * are arguments of the call (acquire wide, then track narrow; a zero gain freezes that path).  R is the plan precision.
+ * Notation: ma(a, b, c) = a b + c as one fmaf in F32 and as a multiply then an add, each rounded, in F64.  u (x) v = (ur vr - ui vi,
+ * ur vi + ui vr): four products, one difference and one sum, each rounded.  Per channel, for n = 0 .. S - 1, in this order:
+ *   1. oscillator: j = theta.  w = C[j >> 21] (x) F[(j >> 10) & 0x7ff] with C[a] = e^(-2 pi i a / 2^11) and F[a] = e^(-2 pi i a / 2^22),
+ *      2048 entries each, the doubles of sdsp_hip_pll_oscillator rounded once to R.  The accumulator keeps all 32 bits (a frequency
+ *      resolution of 2^-32 cycles per sample); the oscillator sees the top 22 (a phase granularity of 2^-22 cycle, about 1.5 urad).
+ *   2. mix: y = x[n] (x) w.
+ *   3. detector.  CROSS: e = yi (a tone or pilot).  BPSK: e = yr yi, one rounded product.  QPSK: e = a - b, a = yi with its sign bit
+ *      flipped when the sign bit of yr is set, b = yr with its sign bit flipped when the sign bit of yi is set: bit operations, -0
+ *      counts as negative.
+ *   4. loop filter: integ = ma(beta, e, integ); then integ = integ < -max_dev ? -max_dev : (integ > max_dev ? max_dev : integ) (a NaN
+ *      stays a NaN); v = ma(alpha, e, integ).
+ *   5. advance: t = v 2^32 (a power-of-two scaling); t = t < lo ? lo : (t > hi ? hi : t) with lo = -2^31 and hi = 2^31 - 128 in F32,
+ *      2^31 - 1 in F64; a NaN becomes 0; k = t rounded to the nearest integer, ties to even, as int32;
+ *      theta = theta + fcw0 + k mod 2^32.
+ *   6. outputs: y[n], err[n] = e, freq[n] = integ after its clamp: the tracked frequency offset in cycles per sample.
+ * With this sign convention a carrier at fcw0 / 2^32 + df cycles per sample drives freq to +df.  alpha, beta and max_dev are host
+ * doubles, each rounded once to R (max_dev at plan creation).  Outputs are bit-exact for finite data.  A NaN in x poisons its own
+ * channel and no other: y[n] and err[n] of that sample and integ, hence freq, from that sample on are NaN, while theta goes on at
+ * fcw0, so the later y and err are those of the open loop (the payload of such a NaN is not contracted).
+ *   - state: one caller-owned device buffer of sdsp_hip_pll_state_bytes = channels (sizeof(R) + 4) bytes: channels elements of R
+ *     (integ), then channels uint32_t (theta).  Read at entry, written at exit.  A zero-filled buffer is a fresh loop at phase 0.
+ *     NULL = zero state, nothing kept.
+ *   - there is no history and no stream position: any split of a stream into calls (empty calls included) gives the same bits and the
+ *     same final state.  A call with S = 0 returns at once and leaves the state alone.
+ *   - y, err and freq may each be NULL and are then not written.  y may be x itself (the same pointer and stride); any other overlap
+ *     between an output and x or another output, or between the state buffer and x or an output, is an error.  Nothing past each
+ *     row's S outputs is written.
+ * Limits: 1 <= channels < 2^31, S < 2^31, 0 < max_dev <= 0.5.
+ */
+#define SDSP_HIP_PLL_CROSS 0
+#define SDSP_HIP_PLL_BPSK 1
+#define SDSP_HIP_PLL_QPSK 2
+typedef struct sdsp_hip_pll_plan sdsp_hip_pll_plan;
+/* host helper: coarse[2 a], coarse[2 a + 1] = re, im of e^(-2 pi i a / 2^11) and fine[..] of e^(-2 pi i a / 2^22), a < 2048, in double;
+ * the axis values are exact */
+int sdsp_hip_pll_oscillator(double *coarse, double *fine);
+/* host helper: the gains of a loop of noise bandwidth bn (cycles per sample, > 0) and damping zeta (> 0) for a signal of the given
+ * amplitude (> 0).  theta = bn / (zeta + 1 / (4 zeta)), d = 1 + 2 zeta theta + theta^2, alpha = 4 zeta theta / (d Kd 2 pi),
+ * beta = 4 theta^2 / (d Kd 2 pi); the detector gain per radian Kd is A (CROSS), A^2 (BPSK), A sqrt(2) (QPSK); the factor 2 pi is there
+ * because the loop works in cycles.  Errors: a null pointer, an unknown mode, an argument that is not finite and > 0:
+ * SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_pll_gains(double bn, double zeta, double amplitude, int mode, double *alpha, double *beta);
+/* fcw0: n_fcw0 = channels centre-frequency words (sdsp_hip_ddc_phase_word), or n_fcw0 = 1 for one word shared by every channel (HOST
+ * pointer).  Errors: channels out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, n_fcw0 other than 1 or channels, an unknown
+ * mode, a precision other than F32 / F64, a max_dev that is not in (0, 0.5] once rounded to the precision: SDSP_HIP_ERR_INVALID_ARG; no
+ * device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_pll_plan_create(sdsp_hip_pll_plan **plan, uint64_t channels, int precision, int mode, const uint32_t *fcw0, uint64_t n_fcw0,
+                             double max_dev, int device);
+int sdsp_hip_pll_plan_destroy(sdsp_hip_pll_plan *plan);
+/*
+ * x: DEVICE pointer; y, err, freq, state: DEVICE pointers or NULL.  Asynchronous on `stream`, one launch, allocates nothing
+ * (stream-capturable); one call per plan in flight.  Errors: null plan, null x with samples > 0, a stride < samples with more than one
+ * channel, overlapping ranges other than y == x, misaligned pointers, an alpha or beta that is not finite in the precision:
+ * SDSP_HIP_ERR_INVALID_ARG; samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; a grid that does not fit one launch: SDSP_HIP_ERR_UNSUPPORTED.
+ * samples == 0: nothing to do.
+ */
+int sdsp_hip_pll_process(sdsp_hip_pll_plan *plan, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, void *err,
+                         uint64_t err_stride, void *freq, uint64_t freq_stride, uint64_t samples, double alpha, double beta, void *state,
+                         void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_pll_process_host(sdsp_hip_pll_plan *plan, const void *host_x, uint64_t x_stride, void *host_y, uint64_t y_stride,
+                              void *host_err, uint64_t err_stride, void *host_freq, uint64_t freq_stride, uint64_t samples, double alpha,
+                              double beta, void *host_state);
+/* bytes of the plan's state buffer: channels (sizeof(R) + 4) */
+int sdsp_hip_pll_state_bytes(const sdsp_hip_pll_plan *plan, uint64_t *bytes);
+/* kernel variants (identical bits): 0 = sdsp_pll_kernel (a lane per channel with theta and integ in registers for the whole call, both
+ * tables in LDS, rows transposed through LDS); 1 = sdsp_pll_plain_kernel, one thread per channel from global memory, the tables read
+ * from global memory and the state read-modify-written (the cross-check; it shares no staging logic with variant 0).  Selecting
+ * variant 1 allocates one plan-owned state buffer once, for calls without a state buffer. */
+int sdsp_hip_pll_plan_set_variant(sdsp_hip_pll_plan *plan, int variant);
+/* kernel launches of one process call: 1; 0 for samples == 0 */
+int sdsp_hip_pll_plan_launches(const sdsp_hip_pll_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint64_t channels;
+    uint32_t block;     /* samples per time block of sdsp_pll_kernel */
+    uint32_t waves;     /* waves (of 64 channels each) per workgroup of sdsp_pll_kernel */
+    uint32_t lds_bytes; /* LDS of one workgroup of sdsp_pll_kernel: both tables and `waves` tiles of 4 x block rows of 65 reals */
+    double max_dev;     /* as rounded to the precision */
+    int precision, mode, device, variant;
+    char kernel[64];    /* the kernel the plan's variant runs */
+} sdsp_hip_pll_plan_info;
+int sdsp_hip_pll_plan_get_info(const sdsp_hip_pll_plan *plan, sdsp_hip_pll_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    BEAM_REAL, BEAM_COMPLEX,
                    LMS_REAL, LMS_COMPLEX, LMS_LMS, LMS_NLMS,
                    CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS, CFAR_POWER, CFAR_IQ,
+                   PLL_CROSS, PLL_BPSK, PLL_QPSK,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -33,6 +34,7 @@ from .beamformer import beamformer_bank, beam_delay_taps, plane_wave_delays
 from .lms import lms_bank
 from .rank_filter import rank_filter_bank, medfilt
 from .cfar import cfar_bank, cfar_alpha, cfar
+from .pll import pll_bank, pll_gains
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

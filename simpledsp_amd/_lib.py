@@ -214,6 +214,14 @@ class CfarPlanInfo(C.Structure):
     ]
 
 
+class PllPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels", C.c_uint64), ("block", C.c_uint32), ("waves", C.c_uint32), ("lds_bytes", C.c_uint32), ("max_dev", C.c_double),
+        ("precision", C.c_int), ("mode", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
+PLL_CROSS, PLL_BPSK, PLL_QPSK = 0, 1, 2
 CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3
 CFAR_POWER, CFAR_IQ = 0, 1
 CFAR_MAX_TRAIN, CFAR_MAX_GUARD = 128, 255
@@ -473,6 +481,16 @@ SIGNATURES = {
     "sdsp_hip_cfar_plan_set_run": (_i, [_vp, _u64]),
     "sdsp_hip_cfar_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_cfar_plan_get_info": (_i, [_vp, C.POINTER(CfarPlanInfo)]),
+    "sdsp_hip_pll_oscillator": (_i, [_vp, _vp]),
+    "sdsp_hip_pll_gains": (_i, [_d, _d, _d, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "sdsp_hip_pll_plan_create": (_i, [_pp, _u64, _i, _i, C.POINTER(_u32), _u64, _d, _i]),
+    "sdsp_hip_pll_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_pll_process": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _d, _d, _vp, _vp]),
+    "sdsp_hip_pll_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _d, _d, _vp]),
+    "sdsp_hip_pll_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_pll_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_pll_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_pll_plan_get_info": (_i, [_vp, C.POINTER(PllPlanInfo)]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, pll) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -538,6 +538,15 @@ struct sdsp_hip_cfar_plan {
     uint32_t last_run = 0; // what the latest call of variant 0 took
     int mode = 0, input = 0, precision = 0, device = 0, variant = 0;
     double alpha = 0.0, scale = 0.0; // scale: c of the mode, rounded to the precision
+};
+
+struct sdsp_hip_pll_plan {
+    uint64_t channels = 0;
+    int precision = 0, mode = 0, device = 0, variant = 0;
+    double max_dev = 0.0;      // rounded to the plan precision
+    uint32_t *fcw0 = nullptr;  // device: channels centre-frequency words
+    void *osc = nullptr;       // device: the tables C then F, 2 x 2048 complex values of the precision
+    void *scratch = nullptr;   // a state buffer for the plain kernel of a call without state; made by set_variant(1)
 };
 
 struct sdsp_hip_arb_plan {
@@ -6276,6 +6285,231 @@ int sdsp_hip_cfar_process_host(sdsp_hip_cfar_plan *p, const void *host_x, uint64
     int rc = st.in();
     if (!rc)
         rc = cfar_run(p, st.dev[0], x_stride, st.dev[1], thr_stride, st.dev[2], det_stride, samples, st.dev[3], nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ carrier-recovery PLL / Costas loop banks (pll.hip)
+
+namespace
+{
+double pll_round(const sdsp_hip_pll_plan *p, double v) { return p->precision == SDSP_HIP_F64 ? v : static_cast<double>(static_cast<float>(v)); }
+
+uint64_t pll_state_size(const sdsp_hip_pll_plan *p) { return p->channels * (real_size(p->precision) + sizeof(uint32_t)); }
+
+// argument checks shared by process and process_host (device pointers or not)
+int pll_check(const sdsp_hip_pll_plan *p, const void *x, uint64_t x_stride, const void *y, uint64_t y_stride, const void *err,
+              uint64_t err_stride, const void *freq, uint64_t freq_stride, uint64_t samples, double alpha, double beta)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(pll_round(p, alpha)) || !std::isfinite(pll_round(p, beta)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "alpha and beta must be finite in the plan precision");
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!x)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x is null");
+    if (p->channels > 1 &&
+        (x_stride < samples || (y && y_stride < samples) || (err && err_stride < samples) || (freq && freq_stride < samples)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "every stride must be >= samples");
+    return SDSP_HIP_OK;
+}
+
+int pll_run(sdsp_hip_pll_plan *p, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, void *err, uint64_t err_stride, void *freq,
+            uint64_t freq_stride, uint64_t samples, double alpha, double beta, void *state, hipStream_t stream)
+{
+    if (p->variant == 1 && !state) { // the plain kernel keeps its state in memory: a zeroed buffer of the plan's
+        if (!p->scratch)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "pll: variant 1 without its scratch state");
+        HIP_TRY(hipMemsetAsync(p->scratch, 0, pll_state_size(p), stream));
+        state = p->scratch;
+    }
+    pll_args a{};
+    a.x = x;
+    a.y = y;
+    a.err = err;
+    a.freq = freq;
+    a.integ = state;
+    a.theta = state ? reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(state) + p->channels * real_size(p->precision)) : nullptr;
+    a.fcw0 = p->fcw0;
+    a.osc = p->osc;
+    a.channels = p->channels;
+    a.samples = samples;
+    a.x_stride = x_stride;
+    a.y_stride = y_stride;
+    a.err_stride = err_stride;
+    a.freq_stride = freq_stride;
+    a.mode = p->mode;
+    a.alpha = pll_round(p, alpha);
+    a.beta = pll_round(p, beta);
+    a.max_dev = p->max_dev;
+    return launch_pll(p->precision, a, p->variant, stream);
+}
+} // namespace
+
+int sdsp_hip_pll_plan_create(sdsp_hip_pll_plan **out, uint64_t channels, int precision, int mode, const uint32_t *fcw0, uint64_t n_fcw0,
+                             double max_dev, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (channels == 0 || channels > 0x7fffffffull)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be in [1, 2^31)");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (mode != SDSP_HIP_PLL_CROSS && mode != SDSP_HIP_PLL_BPSK && mode != SDSP_HIP_PLL_QPSK)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mode must be SDSP_HIP_PLL_CROSS, SDSP_HIP_PLL_BPSK or SDSP_HIP_PLL_QPSK");
+    if (!fcw0 || (n_fcw0 != 1 && n_fcw0 != channels))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "fcw0 must hold one word or one word per channel");
+    const double dev_r = precision == SDSP_HIP_F64 ? max_dev : static_cast<double>(static_cast<float>(max_dev));
+    if (!(dev_r > 0.0 && dev_r <= 0.5)) // NaN included
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "max_dev must be in (0, 0.5] in the plan precision");
+    if (int rc = use_device(device))
+        return rc;
+    std::vector<uint32_t> words;
+    std::vector<double> osc;
+    try {
+        words.resize(static_cast<size_t>(channels));
+        osc.resize(4 * 2048);
+    } catch (const std::bad_alloc &) {
+        return fail(SDSP_HIP_ERR_NOMEM, "pll plan: out of host memory for the frequency words");
+    }
+    for (uint64_t c = 0; c < channels; c++)
+        words[static_cast<size_t>(c)] = fcw0[n_fcw0 == 1 ? 0 : c];
+    sdsp_hip_pll_oscillator(osc.data(), osc.data() + 2 * 2048);
+    auto *p = new sdsp_hip_pll_plan();
+    p->channels = channels;
+    p->precision = precision;
+    p->mode = mode;
+    p->device = device;
+    p->max_dev = dev_r;
+    hipError_t e = upload_reals(osc.data(), osc.size(), precision, &p->osc);
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&p->fcw0), words.size() * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(p->fcw0, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        sdsp_hip_pll_plan_destroy(p);
+        return plan_fail(e, "pll");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pll_plan_destroy(sdsp_hip_pll_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->osc);
+        (void)hipFree(p->fcw0);
+        (void)hipFree(p->scratch);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pll_state_bytes(const sdsp_hip_pll_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = pll_state_size(p);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pll_plan_set_variant(sdsp_hip_pll_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    if (variant == 1 && !p->scratch) {
+        if (int rc = use_device(p->device))
+            return rc;
+        const hipError_t e = hipMalloc(&p->scratch, pll_state_size(p));
+        if (e != hipSuccess) {
+            p->scratch = nullptr;
+            return plan_fail(e, "pll");
+        }
+    }
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pll_plan_launches(const sdsp_hip_pll_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = samples ? 1 : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pll_plan_get_info(const sdsp_hip_pll_plan *p, sdsp_hip_pll_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->channels = p->channels;
+    info->block = pll_block(p->precision);
+    info->waves = pll_waves(p->precision);
+    info->lds_bytes = pll_lds_bytes(p->precision);
+    info->max_dev = p->max_dev;
+    info->precision = p->precision;
+    info->mode = p->mode;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, pll_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_pll_process(sdsp_hip_pll_plan *p, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, void *err,
+                         uint64_t err_stride, void *freq, uint64_t freq_stride, uint64_t samples, double alpha, double beta, void *state,
+                         void *stream)
+{
+    if (int rc = pll_check(p, x, x_stride, y, y_stride, err, err_stride, freq, freq_stride, samples, alpha, beta))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = esize(p->precision), rs = real_size(p->precision);
+    auto span = [&](uint64_t stride, uint64_t bytes) { return ((p->channels - 1) * stride + samples) * bytes; };
+    const bool in_place = y == x && y_stride == x_stride;
+    if (!in_place && ranges_overlap(x, span(x_stride, es), y, span(y_stride, es)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "y overlaps x without being x itself (the same pointer and stride)");
+    const void *reals[2] = { err, freq };
+    const uint64_t real_bytes[2] = { span(err_stride, rs), span(freq_stride, rs) };
+    for (int i = 0; i < 2; i++)
+        if (ranges_overlap(reals[i], real_bytes[i], x, span(x_stride, es)) || ranges_overlap(reals[i], real_bytes[i], y, span(y_stride, es)))
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "err or freq overlaps x or y");
+    if (ranges_overlap(err, real_bytes[0], freq, real_bytes[1]))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the err and freq ranges overlap");
+    const uint64_t state_bytes = pll_state_size(p);
+    if (ranges_overlap(state, state_bytes, x, span(x_stride, es)) || ranges_overlap(state, state_bytes, y, span(y_stride, es)) ||
+        ranges_overlap(state, state_bytes, err, real_bytes[0]) || ranges_overlap(state, state_bytes, freq, real_bytes[1]))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the state buffer overlaps x or an output");
+    if (misaligned(x, es) || misaligned(y, es) || misaligned(err, rs) || misaligned(freq, rs) || misaligned(state, rs))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x, y, err, freq and state must be aligned to their element size");
+    if (int rc = use_device(p->device))
+        return rc;
+    return pll_run(p, x, x_stride, y, y_stride, err, err_stride, freq, freq_stride, samples, alpha, beta, state,
+                   reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_pll_process_host(sdsp_hip_pll_plan *p, const void *host_x, uint64_t x_stride, void *host_y, uint64_t y_stride,
+                              void *host_err, uint64_t err_stride, void *host_freq, uint64_t freq_stride, uint64_t samples, double alpha,
+                              double beta, void *host_state)
+{
+    if (int rc = pll_check(p, host_x, x_stride, host_y, y_stride, host_err, err_stride, host_freq, freq_stride, samples, alpha, beta))
+        return rc;
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t es = esize(p->precision), rs = real_size(p->precision);
+    auto span = [&](uint64_t stride, uint64_t bytes) { return static_cast<size_t>(((p->channels - 1) * stride + samples) * bytes); };
+    host_stage st("pll", { { host_x, span(x_stride, es), false }, { host_y, span(y_stride, es), true }, { host_err, span(err_stride, rs), true },
+                       { host_freq, span(freq_stride, rs), true }, { host_state, static_cast<size_t>(pll_state_size(p)), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = pll_run(p, st.dev[0], x_stride, st.dev[1], y_stride, st.dev[2], err_stride, st.dev[3], freq_stride, samples, alpha, beta,
+                     st.dev[4], nullptr);
     return st.out(rc);
 }
 }

@@ -689,6 +689,36 @@ int sdsp_hip_ddc_oscillator(double *coarse, double *fine)
     }
     return SDSP_HIP_OK;
 }
+int sdsp_hip_pll_oscillator(double *coarse, double *fine)
+{
+    if (!coarse || !fine)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    for (uint32_t a = 0; a < 2048; a++) { // the conjugates: e^(-2 pi i a / 2^11) and e^(-2 pi i a / 2^22)
+        double c, s;
+        ddc_unit_phase(a << 21, &c, &s);
+        coarse[2 * a] = c;
+        coarse[2 * a + 1] = -s;
+        ddc_unit_phase(a << 10, &c, &s);
+        fine[2 * a] = c;
+        fine[2 * a + 1] = -s;
+    }
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_pll_gains(double bn, double zeta, double amplitude, int mode, double *alpha, double *beta)
+{
+    if (!alpha || !beta)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *alpha = *beta = 0.0;
+    if (mode != SDSP_HIP_PLL_CROSS && mode != SDSP_HIP_PLL_BPSK && mode != SDSP_HIP_PLL_QPSK)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mode must be SDSP_HIP_PLL_CROSS, SDSP_HIP_PLL_BPSK or SDSP_HIP_PLL_QPSK");
+    if (!(std::isfinite(bn) && bn > 0.0 && std::isfinite(zeta) && zeta > 0.0 && std::isfinite(amplitude) && amplitude > 0.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bn, zeta and amplitude must be finite and > 0");
+    const double theta = bn / (zeta + 1.0 / (4.0 * zeta)), d = 1.0 + 2.0 * zeta * theta + theta * theta;
+    const double kd = mode == SDSP_HIP_PLL_CROSS ? amplitude : mode == SDSP_HIP_PLL_BPSK ? amplitude * amplitude : amplitude * std::sqrt(2.0);
+    *alpha = 4.0 * zeta * theta / (d * kd * (2.0 * M_PI));
+    *beta = 4.0 * theta * theta / (d * kd * (2.0 * M_PI));
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_ddc_out_samples(uint32_t down, uint64_t samples, uint64_t *out)
 {
     if (!out)

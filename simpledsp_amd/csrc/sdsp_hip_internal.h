@@ -451,6 +451,24 @@ uint32_t cfar_padded(uint32_t cells);
 uint32_t cfar_block(int precision, int mode);
 uint32_t cfar_lds_bytes(int precision, int mode);
 uint32_t cfar_auto_run(int precision, int mode, uint64_t channels, uint64_t samples, uint32_t train, uint32_t guard);
+// Carrier-recovery PLL / Costas loop banks (pll.hip): the one launch of a call
+struct pll_args {
+    const void *x;
+    void *y, *err, *freq; // nullable: not written; y may be x
+    void *integ;          // channels reals; nullable for variant 0 (zero state, nothing kept)
+    uint32_t *theta;      // channels phase words; null with integ
+    const uint32_t *fcw0; // channels centre-frequency words
+    const void *osc;      // the two oscillator tables of the precision, C then F
+    uint64_t channels, samples, x_stride, y_stride, err_stride, freq_stride;
+    int mode;
+    double alpha, beta, max_dev; // already rounded to the plan precision
+};
+int launch_pll(int precision, const pll_args &a, int variant, void *stream);
+const char *pll_kernel_for(int variant);
+// samples per time block, waves per workgroup and LDS bytes per workgroup of sdsp_pll_kernel
+uint32_t pll_block(int precision);
+uint32_t pll_waves(int precision);
+uint32_t pll_lds_bytes(int precision);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
