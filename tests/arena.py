@@ -9,6 +9,11 @@ not hidden by any tolerance.  All comparisons are on bit patterns (`bits`), so t
 
 tests/test_arena_host.py shows on CPU tensors that each check fails when it should; tests/test_gpu_isolation.py uses them.
 A plain module, not a conftest: it changes nothing about how the suite runs.
+
+The second half (`Buffers` and the `check_*_bank` functions) frames EVERY buffer of a streaming bank's call at once -- in, out, state,
+accumulators -- and drives a "bank": any object with the few members listed at `check_framed_bank`.  The HIP banks of
+tests/test_gpu_stream_isolation.py and the numpy stand-ins of tests/test_arena_host.py (with planted defects) go through the same
+functions, on "cuda" and on "cpu".
 """
 import math
 
@@ -138,3 +143,181 @@ def assert_rows_isolated(out, clean, poisoned, nan_from=None):
                                      f"({miss.numel()} places)")
             if not bool(torch.equal(bits(out[r])[~want], bits(clean[r])[~want])):
                 raise AssertionError(f"poisoned row {r}: values outside the NaN mask differ from the clean result")
+
+
+# ------------------------------------------------------------------ every buffer of a streaming bank's call, framed at once
+
+STRIDES = ("exact", "odd", "vec")
+
+
+def stride_for(cols, element_size, kind):
+    """row stride in elements: "exact" = cols; "odd" = the next odd number above cols (rows alternate between 16-byte aligned and
+    not); "vec" = the next multiple of 16 bytes above cols (every row keeps the alignment of the first)"""
+    if kind == "exact":
+        return cols
+    if kind == "odd":
+        return cols + 1 + cols % 2
+    assert kind == "vec", kind
+    per = max(1, 16 // element_size)
+    return (cols // per + 1) * per
+
+
+def assert_nan_exactly(out, clean, mask, tag=""):
+    """out is NaN (complex: in either half) exactly where the boolean `mask` says and has clean's bits everywhere else"""
+    import torch
+    assert out.shape == clean.shape == mask.shape, (tag, out.shape, clean.shape, mask.shape)
+    isnan = torch.isnan(torch.view_as_real(out)).any(dim=-1) if out.is_complex() else torch.isnan(out)
+    mask = mask.to(isnan.device)
+    if not bool(torch.equal(isnan, mask)):
+        extra, missing = torch.nonzero(isnan & ~mask), torch.nonzero(~isnan & mask)
+        raise AssertionError(f"{tag}: NaN mask differs from the expected one: {extra.shape[0]} unexpected NaN(s), the first at "
+                             f"{extra[:1].tolist()}; {missing.shape[0]} missing, the first at {missing[:1].tolist()}")
+    if not bool(torch.equal(bits(out)[~mask], bits(clean)[~mask])):
+        diff = (bits(out) != bits(clean))
+        diff = (diff.any(dim=-1) if out.is_complex() else diff) & ~mask
+        raise AssertionError(f"{tag}: {int(diff.sum())} value(s) outside the NaN mask differ from the clean result, the first at "
+                             f"{torch.nonzero(diff)[:1].tolist()}")
+
+
+class Buffers:
+    """The named 2-D buffers of a bank's call.  specs: {name: dict(shape = (rows, cols), dtype, init = tensor (rows, cols) or None,
+    read_only = bool, strided = bool)}.  layout = None: ordinary, exactly-sized tensors (the clean run).  Otherwise every buffer is a
+    view into an arena of its own (`framed`), a margin of at least one whole row on each side; layout[name] = (lead elements past the
+    arena's 512-byte base, one of STRIDES), (0, "exact") where a name is missing; a buffer with strided = False (a state: its rows
+    are contiguous by contract) takes the lead only.  The arenas are `fills(dtype)[fill]` everywhere except where `init` goes."""
+
+    def __init__(self, torch, specs, layout=None, fill=0, device="cuda"):
+        self.torch, self.specs, self.device = torch, specs, device
+        self.t, self.arena, self.before, self.cols = {}, {}, {}, {}
+        for name, s in specs.items():
+            rows, cols = s["shape"]
+            self.cols[name] = cols
+            if layout is None:
+                self.t[name] = torch.zeros((rows, cols), dtype=s["dtype"], device=device)
+            else:
+                lead, kind = layout.get(name, (0, "exact"))
+                esize = torch.empty((), dtype=s["dtype"]).element_size()
+                stride = stride_for(cols, esize, kind if s.get("strided", True) else "exact")
+                margin = -(-max(stride, 1) // 128) * 128  # whole rows, and a multiple of 512 bytes: the lead stays what it says
+                self.arena[name], self.t[name] = framed(torch, (rows, cols), s["dtype"], lead, margin, fills(s["dtype"])[fill], stride,
+                                                        device)
+            if s.get("init") is not None:
+                self.inner(name).copy_(s["init"])
+            if layout is not None:
+                self.before[name] = bits(self.arena[name]).clone()
+
+    def has(self, name):
+        return name in self.t
+
+    def inner(self, name):
+        """the (rows, cols) part of the buffer that belongs to the call"""
+        return self.t[name][:, :self.cols[name]]
+
+    def stride(self, name):
+        return self.t[name].shape[1]
+
+    def ptr(self, name, col=0):
+        """address of element (0, col); None for a buffer the call does not have (state = NULL)"""
+        if name not in self.t:
+            return None
+        return self.t[name].data_ptr() + col * self.t[name].element_size()
+
+    def sync(self):
+        if self.device != "cpu":
+            self.torch.cuda.synchronize()
+
+    def writable(self):
+        return [n for n, s in self.specs.items() if not s.get("read_only")]
+
+    def check_frames(self, tag=""):
+        """a read-only buffer's arena is unchanged everywhere; of the others, everything outside the (rows, cols) interiors is: the
+        margins on both sides, the lead and the row padding"""
+        torch = self.torch
+        self.sync()
+        for name, arena in self.arena.items():
+            if self.specs[name].get("read_only"):
+                changed = bits(arena) != self.before[name]
+                if bool(changed.any()):
+                    at = int(torch.nonzero(changed.reshape(arena.numel(), -1).any(dim=1))[0])
+                    start = (self.t[name].data_ptr() - arena.data_ptr()) // arena.element_size()
+                    raise AssertionError(f"{tag}: read-only buffer '{name}' was written, first at flat index {at} ({at - start:+d} "
+                                         f"from its first element)")
+                continue
+            try:
+                assert_frame_untouched(self.before[name], arena, interior_mask(torch, arena, self.t[name], self.cols[name]))
+            except AssertionError as e:
+                raise AssertionError(f"{tag}: buffer '{name}': {e}") from None
+
+
+def clean_bank(torch, bank, device="cuda", null_state=False):
+    """the bank's whole stream in one call on ordinary, exactly-sized tensors: {name: result} of every writable buffer"""
+    b = Buffers(torch, bank.specs(null_state), device=device)
+    bank.run(b, 0, bank.ticks)
+    b.sync()
+    return {n: b.inner(n).clone() for n in b.writable()}
+
+
+def check_framed_bank(torch, bank, clean, layout, splits=(), device="cuda", null_state=False, loose=None, tag=""):
+    """A bank is any object with
+        ticks                    frames (or samples, where a call may end anywhere) of its whole stream
+        specs(null_state)        the Buffers specs of one stream: "in" read-only, every other buffer writable; no "state" when null_state
+        run(b, t0, t1)           one call on the Buffers b: ticks [t0, t1) of the stream (b.has("state") says whether it gets a state)
+        masks(row, col)          {name: boolean (rows, cols) tensor}: where every writable buffer is NaN after ONE call of the whole
+                                 stream with in[row, col] = NaN (check_poisoned_bank)
+    Under both fills: frames every buffer by `layout`, feeds the stream as the calls `splits` cuts it into (none: one call) against
+    the same buffers, checks after every call that nothing outside the interiors changed (and nothing at all in "in"), and at the end
+    that every writable interior has clean's bits -- or passes loose[name](got, want) where the contract promises less than bits."""
+    edges = [0, *splits, bank.ticks]
+    for fill in (0, 1):
+        b = Buffers(torch, bank.specs(null_state), layout, fill, device)
+        for t0, t1 in zip(edges, edges[1:]):
+            bank.run(b, t0, t1)
+            b.check_frames(f"{tag} fill {fill} ticks [{t0}, {t1})")
+        for name, want in clean.items():
+            got = b.inner(name)
+            if loose and name in loose:
+                loose[name](got, want)
+            elif not same_bits(got, want):
+                diff = bits(got) != bits(want)
+                raise AssertionError(f"{tag} fill {fill}: the interior of '{name}' differs from the clean result in {int(diff.sum())} "
+                                     f"place(s), the first at {torch.nonzero(diff)[:1].tolist()}")
+
+
+def check_poisoned_bank(torch, bank, clean, poisons, layout, device="cuda", tag=""):
+    """poisons: (label, row, col) elements of "in".  One at a time and under both fills: the framed call with that element NaN leaves
+    every writable buffer NaN exactly where bank.masks(row, col) says, with clean's bits everywhere else, and the frames untouched."""
+    for fill in (0, 1):
+        for label, row, col in poisons:
+            specs = dict(bank.specs())
+            x = specs["in"]["init"].clone()
+            x[row, col] = complex(NAN, NAN) if x.is_complex() else NAN
+            specs["in"] = dict(specs["in"], init=x)
+            b = Buffers(torch, specs, layout, fill, device)
+            bank.run(b, 0, bank.ticks)
+            where = f"{tag} fill {fill} NaN at in[{row}, {col}] ({label})"
+            b.check_frames(where)
+            masks = bank.masks(row, col)
+            for name, want in clean.items():
+                assert_nan_exactly(b.inner(name), want, masks[name], f"{where} buffer '{name}'")
+
+
+def slice_map(units, per_slice):
+    """[g0, g1) of every workspace slice of a call of `units` units"""
+    return [(g, min(g + per_slice, units)) for g in range(0, units, per_slice)]
+
+
+def edge_units(channels, frames, per_slice):
+    """(label, channel, frame) of the units next to the edges of a call whose units g = channel frames + frame run in slices of
+    `per_slice`: the last frame of a slice and the first of the next INSIDE one channel, and the last frame of a channel and the first
+    of the next INSIDE one slice.  Raises where the shape has no such edge: the caller chose the wrong workspace."""
+    out = []
+    cut = [g for g, _ in slice_map(channels * frames, per_slice)[1:] if g % frames]
+    assert cut, ("no slice starts inside a channel", channels, frames, per_slice)
+    g = cut[0]
+    assert (g - 1) // frames == g // frames
+    out += [("last frame of a slice", (g - 1) // frames, (g - 1) % frames), ("first frame of the next slice", g // frames, g % frames)]
+    seam = [c * frames for c in range(1, channels) if (c * frames) % per_slice]
+    assert seam, ("no channel starts inside a slice", channels, frames, per_slice)
+    c = seam[0] // frames
+    out += [(f"last frame of channel {c - 1}, in the slice of the next", c - 1, frames - 1), (f"first frame of channel {c}", c, 0)]
+    return out

@@ -5,7 +5,11 @@ access, on the arena memory around it).  The operation is y = 2 x per row.  A cl
 defect -- a one-element write just before / just after the interior, a write into row padding, a read one element past the
 interior, a 1e-9 leak from the neighbouring row -- is reported.  The last two are far below any rounding tolerance on Gaussian
 data: they are caught because the checks compare bits under two fills and track NaNs, which is what tests/test_gpu_isolation.py
-relies on for the HIP kernels."""
+relies on for the HIP kernels.
+
+The second half does the same for the streaming-bank harness (arena.Buffers, check_framed_bank, check_poisoned_bank) that
+tests/test_gpu_stream_isolation.py runs the HIP banks through: numpy stand-ins of an STFT and an inverse STFT bank pass it, and
+each of seven planted defects is reported by the assertion meant for it."""
 import numpy as np
 import pytest
 import torch
@@ -144,6 +148,182 @@ def test_nan_masks_of_poisoned_rows():
     got[2, 3] += 1e-12  # a poisoned row must keep the clean bits before its NaN
     with pytest.raises(AssertionError, match="outside the NaN mask"):
         arena.assert_rows_isolated(got, want, [2], nan_from={2: mask})
+
+
+# ------------------------------------------------------------------ the streaming-bank harness (tests/test_gpu_stream_isolation.py)
+#
+# The stand-in "banks" are the numpy references of the STFT and inverse STFT contracts behind the bank protocol of
+# arena.check_framed_bank, working in slices of UNITS (channel, frame) units like the HIP banks.  `fault` plants one defect.
+
+N_FFT, HOP, CH, FRAMES, UNITS = 16, 4, 3, 7, 5  # hist = 12; slices [0,5) [5,10) [10,15) [15,20) [20,21) of 21 units
+BINS, HIST = N_FFT // 2 + 1, N_FFT - HOP
+WINDOW = 0.5 + 0.25 * np.cos(np.arange(N_FFT))  # no zeros: a NaN sample reaches every bin of its frames
+
+
+class StftStandIn:
+    ticks = FRAMES
+
+    def __init__(self, fault=None):
+        from stft_ref import stft_ref
+        self.ref, self.fault = stft_ref, fault
+        rng = np.random.default_rng(11)
+        self.x = torch.from_numpy(rng.standard_normal((CH, FRAMES * HOP)))
+        self.hist = torch.from_numpy(rng.standard_normal((CH, HIST)))
+
+    def specs(self, null_state=False):
+        s = {"in": dict(shape=(CH, FRAMES * HOP), dtype=torch.float64, init=self.x, read_only=True),
+             "out": dict(shape=(CH, FRAMES * BINS), dtype=torch.complex128, init=None)}
+        if not null_state:
+            s["state"] = dict(shape=(CH, HIST), dtype=torch.float64, init=self.hist, strided=False)
+        return s
+
+    def run(self, b, t0, t1):
+        F, S = t1 - t0, (t1 - t0) * HOP
+        x = b.t["in"][:, t0 * HOP:t1 * HOP].numpy().copy()
+        if self.fault == "reads_before_in":  # sample 0 of channel 0 picks up 1e-9 of the element in front of the buffer
+            x[0, 0] += 1e-9 * _around(b.t["in"])[0]
+        hist = b.inner("state").numpy().copy() if b.has("state") else None
+        y, state = self.ref(x, N_FFT, HOP, WINDOW, hist)
+        for g0, g1 in arena.slice_map(CH * F, UNITS):
+            for g in range(g0, g1):
+                c, j = divmod(g, F)
+                src = c
+                if self.fault == "frame_from_the_previous_channel" and j == 0 and g > g0:  # a channel that starts inside a slice
+                    src = c - 1
+                b.t["out"][c, (t0 + j) * BINS:(t0 + j + 1) * BINS] = torch.from_numpy(y[src, j])
+        if self.fault == "writes_past_last_row":
+            _around(b.t["out"])[-1] = 1.0
+        if self.fault == "writes_before_first_row":
+            _around(b.t["out"])[0] = 1.0
+        if self.fault == "writes_row_padding" and b.stride("out") > FRAMES * BINS:
+            b.t["out"][1, FRAMES * BINS] = 1.0
+        if self.fault == "writes_in":
+            b.t["in"][1, 2] = 0.0
+        if b.has("state"):
+            if self.fault == "state_shifted_by_one" and S < HIST:  # the in-place shift of a short block
+                state = np.roll(state, 1, axis=1)
+            b.inner("state").copy_(torch.from_numpy(state))
+
+    def masks(self, row, col):
+        out = torch.zeros((CH, FRAMES, BINS), dtype=torch.bool)
+        p = col + HIST
+        for j in range(FRAMES):
+            out[row, j] = j * HOP <= p < j * HOP + N_FFT
+        state = torch.zeros((CH, HIST), dtype=torch.bool)
+        if FRAMES * HOP - 1 - col < HIST:
+            state[row, FRAMES * HOP - 1 - col] = True
+        return {"out": out.reshape(CH, -1), "state": state}
+
+
+class IstftStandIn:
+    ticks = FRAMES
+
+    def __init__(self, fault=None):
+        from istft_ref import istft_ref
+        self.ref, self.fault = istft_ref, fault
+        rng = np.random.default_rng(12)
+        X = rng.standard_normal((CH, FRAMES, BINS)) + 1j * rng.standard_normal((CH, FRAMES, BINS))
+        self.X = torch.from_numpy(X.reshape(CH, -1))
+        self.pending = torch.from_numpy(rng.standard_normal((CH, HIST)))
+
+    def specs(self, null_state=False):
+        s = {"in": dict(shape=(CH, FRAMES * BINS), dtype=torch.complex128, init=self.X, read_only=True),
+             "out": dict(shape=(CH, FRAMES * HOP), dtype=torch.float64, init=None)}
+        if not null_state:
+            s["state"] = dict(shape=(CH, HIST), dtype=torch.float64, init=self.pending, strided=False)
+        return s
+
+    def run(self, b, t0, t1):
+        X = b.t["in"][:, t0 * BINS:t1 * BINS].numpy().reshape(CH, t1 - t0, BINS)
+        y, state = self.ref(X, N_FFT, HOP, WINDOW, b.inner("state").numpy().copy() if b.has("state") else None)
+        b.t["out"][:, t0 * HOP:t1 * HOP].copy_(torch.from_numpy(y))
+        if self.fault == "writes_before_first_row":
+            _around(b.t["out"])[0] = 1.0
+        if b.has("state"):
+            b.inner("state").copy_(torch.from_numpy(state))
+
+    def masks(self, row, col):
+        j = col // BINS
+        t = torch.arange(FRAMES * HOP + HIST)
+        hit = (t >= j * HOP) & (t < j * HOP + N_FFT)
+        out = torch.zeros((CH, FRAMES * HOP), dtype=torch.bool)
+        state = torch.zeros((CH, HIST), dtype=torch.bool)
+        out[row], state[row] = hit[:FRAMES * HOP], hit[FRAMES * HOP:]
+        return {"out": out, "state": state}
+
+
+ODD = {"in": (1, "odd"), "out": (1, "odd"), "state": (1, "exact")}
+LAYOUTS = [{}, ODD, {"in": (2, "vec"), "out": (2, "vec"), "state": (2, "exact")}, {"state": (1, "exact")}]
+
+
+def _stft_poisons():
+    edges = arena.edge_units(CH, FRAMES, UNITS)
+    assert [(c, j) for _, c, j in edges] == [(0, 4), (0, 5), (0, 6), (1, 0)]  # slices [0, 5) [5, 10): 5 is inside channel 0, 7 in [5, 10)
+    return [(label, c, j * HOP + HOP - 1) for label, c, j in edges] + [("first", 0, 0), ("last", CH - 1, FRAMES * HOP - 1)]
+
+
+def _drive(bank, clean=None, poison_bank=None):
+    """what tests/test_gpu_stream_isolation.py does with a HIP bank: layouts, two calls, state = NULL, poisons"""
+    clean = arena.clean_bank(torch, bank, "cpu") if clean is None else clean
+    for layout in LAYOUTS:
+        arena.check_framed_bank(torch, bank, clean, layout, device="cpu", tag="one call")
+    arena.check_framed_bank(torch, bank, arena.clean_bank(torch, bank, "cpu", null_state=True), ODD, device="cpu", null_state=True)
+    poisons = _stft_poisons() if isinstance(bank, StftStandIn) else [("a bin of frame 3", 1, 3 * BINS + 2), ("last", CH - 1, FRAMES * BINS - 2)]
+    for layout in ({}, ODD):
+        arena.check_poisoned_bank(torch, bank, clean, poisons, layout, device="cpu", tag="poison")
+    for layout in LAYOUTS:
+        arena.check_framed_bank(torch, bank, clean, layout, splits=(2,), device="cpu", tag="two calls")
+
+
+def test_stream_harness_passes_the_clean_stand_ins():
+    for bank in (StftStandIn(), IstftStandIn()):
+        _drive(bank)
+    # the stand-ins are the references themselves: their clean result is the reference's, to the bit
+    from stft_ref import stft_ref
+    b = StftStandIn()
+    want, state = stft_ref(b.x.numpy(), N_FFT, HOP, WINDOW, b.hist.numpy())
+    clean = arena.clean_bank(torch, b, "cpu")
+    assert np.array_equal(clean["out"].numpy().reshape(want.shape), want) and np.array_equal(clean["state"].numpy(), state)
+
+
+@pytest.mark.parametrize("fault,match", [
+    ("writes_past_last_row", r"buffer 'out': 1 element\(s\) outside the interior.*\+1 from its end"),
+    ("writes_before_first_row", r"buffer 'out': 1 element\(s\) outside the interior.*-1 from the interior's start"),
+    ("writes_row_padding", r"buffer 'out': 1 element\(s\) outside the interior"),
+    ("reads_before_in", r"the interior of 'out' differs from the clean result"),
+    ("frame_from_the_previous_channel", r"first frame of channel 1\) buffer 'out': NaN mask differs"),
+    ("state_shifted_by_one", r"two calls.*differs from the clean result"),  # the second call reads the shifted history
+    ("writes_in", r"read-only buffer 'in' was written"),
+])
+def test_stream_harness_reports_each_planted_fault(fault, match):
+    """the clean result comes from the faulted bank itself where the fault would be in a HIP bank's clean run too (a slice-edge mix-up,
+    a wrong in-place shift): only the NaN masks and the two-call comparison can see those"""
+    bank = StftStandIn(fault)
+    own = fault in ("frame_from_the_previous_channel", "state_shifted_by_one")
+    clean = arena.clean_bank(torch, bank if own else StftStandIn(), "cpu")
+    with pytest.raises(AssertionError, match=match):
+        _drive(bank, clean)
+    if fault == "reads_before_in":  # far below any tolerance under the finite fill: it is the bit comparison that sees it
+        b = arena.Buffers(torch, bank.specs(), {}, 1, "cpu")
+        bank.run(b, 0, FRAMES)
+        assert float((b.inner("out") - clean["out"]).abs().max()) < 1e-6 and not arena.same_bits(b.inner("out"), clean["out"])
+
+
+def test_stream_harness_reports_a_write_in_front_of_an_overlap_add_output():
+    with pytest.raises(AssertionError, match=r"buffer 'out': 1 element\(s\) outside the interior.*-1 from the interior's start"):
+        _drive(IstftStandIn("writes_before_first_row"), arena.clean_bank(torch, IstftStandIn(), "cpu"))
+
+
+def test_edge_units_and_strides():
+    assert arena.slice_map(21, 5) == [(0, 5), (5, 10), (10, 15), (15, 20), (20, 21)]
+    with pytest.raises(AssertionError, match="no slice starts inside a channel"):
+        arena.edge_units(3, 7, 7)  # slices of whole channels
+    with pytest.raises(AssertionError, match="no slice starts inside a channel"):
+        arena.edge_units(3, 7, 1000)  # one slice
+    assert [arena.stride_for(10, 4, k) for k in arena.STRIDES] == [10, 11, 12]
+    assert [arena.stride_for(11, 4, k) for k in arena.STRIDES] == [11, 13, 12]
+    assert [arena.stride_for(8, 16, k) for k in arena.STRIDES] == [8, 9, 9]
+    assert arena.stride_for(12, 8, "vec") == 14
 
 
 def test_bits_are_exact_and_nan_safe():
