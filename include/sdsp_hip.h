@@ -1841,6 +1841,129 @@ typedef struct {
 } sdsp_hip_pll_plan_info;
 int sdsp_hip_pll_plan_get_info(const sdsp_hip_pll_plan *plan, sdsp_hip_pll_plan_info *info);
 
+/* ------------------------------------------------------------------ symbol-timing recovery banks (Gardner, zero-crossing) */
+
+/*
+ * Symbol-timing recovery bank: `channels` independent second-order timing loops on interleaved I/Q rows, F32
+ * or F64 (channel-major: row c = ptr[c stride ..), strides in elements of the row's kind: one complex sample is one element of x and
+ * y, one real is one element of err and period).  Each loop interpolates its row with the nearest-phase polyphase interpolator of the
+ * arbitrary-ratio resampler (L phases of T taps, H[p][k] = h[k L + p] rounded once to R, exactly as sdsp_hip_arb_tables lays it out)
+ * at two strobes per symbol, measures the timing error on the symbol strobes with the plan's detector, and steers its step through a
+ * proportional-plus-integral loop filter whose gains alpha and beta are arguments of the call.  The number of symbols a channel
+ * yields depends on its data and differs from channel to channel.  R is the plan precision.
+ * Notation: ma(a, b, c) = a b + c as one fmaf in F32 and as a multiply then an add, each rounded, in F64.  s(v) = +1 or -1 by the sign
+ * bit of v (-0 counts as negative; s of a NaN is a NaN).  step0 is the nominal half-symbol period as a Q32.32 word, 2^32 <= step0 <= 2^38 (2 to 128 samples
+ * per symbol, not necessarily an integer; sdsp_hip_timing_step).  Per channel the state is: the integrator integ (R), the stream time
+ * t (uint64, Q32.32: the integer part counts from the first sample of the call, the fraction is the sub-sample position), the advance
+ * word w (int32), parity (0: the next strobe is a mid-symbol strobe, 1: a symbol strobe), the previous symbol strobe ps and the last
+ * mid-symbol strobe ym (complex R), and the T - 1 input samples in front of the call, newest first.
+ * Per channel, while (t >> 32) < S, in this order:
+ *   1. interpolate: i = t >> 32, f = t & 0xffffffff, p = f >> (32 - log2 L) (0 when L = 1).  Per real plane z = H[p][0] x[i], a plain
+ *      product, then z = ma(H[p][k], x[i - k], z) for k = 1 .. T - 1 in ascending order; x at negative indices is the history.
+ *   2. parity == 0 (mid-symbol strobe): ym = z; parity = 1.
+ *   3. otherwise (symbol strobe):
+ *        detector.  GARDNER: dr = ps.r - z.r, di = ps.i - z.i, e = ma(di, ym.i, dr ym.r) (dr ym.r is one rounded product).
+ *                   ZC_QPSK: the same with dr = s(ps.r) - s(z.r) and di = s(ps.i) - s(z.i).
+ *                   ZC_BPSK: e = (s(ps.r) - s(z.r)) ym.r, one rounded product.
+ *        loop filter.  integ = ma(beta, e, integ); integ = integ < -max_dev ? -max_dev : (integ > max_dev ? max_dev : integ) (a NaN
+ *                   stays a NaN); v = ma(alpha, e, integ); q = v 2^32 (a power-of-two scaling); q = q < lo ? lo : (q > hi ? hi : q)
+ *                   with lo = -2^31 and hi = 2^31 - 128 in F32, 2^31 - 1 in F64; a NaN becomes 0; w = q rounded to the nearest integer,
+ *                   ties to even, as int32.
+ *        outputs.   With m the channel's count of this call so far: y[m] = z, err[m] = e, period[m] = integ (after its clamp: the
+ *                   tracked offset of the half-symbol period from step0, in samples); then the count goes up by one.
+ *        ps = z; parity = 0.
+ *   4. t = t + step0 + w.  The word set at a symbol strobe serves both half steps up to the next one.  step0 >= 2^32 and |w| <= 2^31:
+ *      the advance is always positive, and at most two strobes fall on one input sample.
+ * At the end of the call t = t - (S << 32) and the history becomes the last T - 1 inputs.  Sign convention: e < 0 means the strobes
+ * are late and the period shrinks.  alpha, beta and max_dev are host doubles, each rounded once to R (max_dev at plan creation); zero
+ * gains free-run at step0.  Outputs are bit-exact for finite data.  A NaN in x poisons its own channel and no other: the strobes
+ * whose windows hold it, and integ (hence period) from the first such symbol on, are NaN, while the time goes on at step0, so the
+ * channel's count and its later y are those of the open loop (the payload of such a NaN is not contracted).  ZC_BPSK reads real
+ * parts only in its detector: a NaN in an imaginary part alone reaches y and nothing else.
+ *   - outputs: y is required; err and period may each be NULL and are then not written.  counts, a required DEVICE array of `channels`
+ *     uint32_t, receives each channel's number of symbols of this call.  Elements of a row at or past its count are not written.  A row
+ *     needs room for sdsp_hip_timing_max_out(plan, S) elements, the most any loop yields from S inputs: with n = ceil(S 2^32 / (step0 -
+ *     2^31)) strobes at most, (n + 1) / 2 of them symbol strobes.  y, err, period and counts must not overlap x, one another or the state.
+ *   - state: one caller-owned DEVICE buffer of sdsp_hip_timing_state_bytes, 8-byte aligned: one array per field, each starting at
+ *     the next multiple of 8 bytes, in this order: t (channels uint64_t), ps (channels complex R), ym (channels complex R), integ
+ *     (channels R), w (channels int32_t), parity (channels uint32_t), then the history (channels rows of T - 1 complex R, newest first).
+ *     Read at entry, written at exit.  A zero-filled buffer is a fresh loop at t = 0 preceded by zeros.  NULL = zero state, nothing kept.
+ *   - any split of a stream into calls (empty calls included) gives the same concatenated per-channel outputs and the same final
+ *     state, bit for bit.  A call with S = 0 zeroes counts and leaves the state alone.
+ * Limits: 1 <= channels < 2^31, S < 2^31, L a power of two <= 128, 1 <= T <= 64, L T <= 4096, 0 < max_dev <= 0.5.
+ */
+#define SDSP_HIP_TIMING_GARDNER 0
+#define SDSP_HIP_TIMING_ZC_QPSK 1
+#define SDSP_HIP_TIMING_ZC_BPSK 2
+#define SDSP_HIP_TIMING_MAX_PHASES 128
+#define SDSP_HIP_TIMING_MAX_TAPS 64
+#define SDSP_HIP_TIMING_MAX_TABLE 4096
+#define SDSP_HIP_TIMING_MIN_STEP (1ull << 32)
+#define SDSP_HIP_TIMING_MAX_STEP (1ull << 38)
+typedef struct sdsp_hip_timing_plan sdsp_hip_timing_plan;
+/* host helper: the half-symbol step word of sps samples per symbol, round(sps / 2 2^32) with ties to even.  Errors: a null pointer, sps
+ * outside [2, 128] (NaN included): SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_timing_step(double sps, uint64_t *step0);
+/* host helper: the capacity a row needs for `samples` inputs at step word step0 (see above).  Errors: a null pointer:
+ * SDSP_HIP_ERR_INVALID_ARG; step0 outside [2^32, 2^38] or samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_timing_max_out_for(uint64_t step0, uint64_t samples, uint64_t *n);
+/* host helper: the gains of a loop of noise bandwidth bn (cycles per symbol, > 0) and damping zeta (> 0) for a detector of slope kd
+ * (units of e per symbol of timing offset, > 0; it depends on the pulse and the amplitude: INTEGRATION.md says how to read it off the
+ * open loop) at sps samples per symbol.  theta = bn / (zeta + 1 / (4 zeta)), d = 1 + 2 zeta theta + theta^2,
+ * alpha = 4 zeta theta / (d kd) sps / 2, beta = 4 theta^2 / (d kd) sps / 2: v is in samples per half symbol.  Errors: a null pointer, an
+ * argument that is not finite and > 0: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_timing_gains(double bn, double zeta, double kd, double sps, double *alpha, double *beta);
+/* host helper: the root-raised-cosine matched prototype of `phases` x `taps` values for sps samples per symbol (> 0) and a roll-off in
+ * (0, 1]: sampled at sps phases per symbol, centred at (phases taps - 1) / 2, scaled so that the values sum to `phases` (the
+ * sdsp_hip_arb_design convention: every phase has about unit gain at DC).  The two removable singularities (the centre and
+ * |tau| = 1 / (4 rolloff)) take their limits.  Errors: the shape limits above: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, sps or rolloff
+ * out of range: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_timing_design(uint32_t phases, uint32_t taps, double sps, double rolloff, double *h);
+/* h: phases x taps HOST doubles.  Errors: channels, phases, taps or step0 out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an
+ * unknown mode, a precision other than F32 / F64, a max_dev that is not in (0, 0.5] once rounded to the precision, a tap that is not
+ * finite in the precision: SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE. */
+int sdsp_hip_timing_plan_create(sdsp_hip_timing_plan **plan, uint64_t channels, int precision, int mode, uint32_t phases, uint32_t taps,
+                                const double *h, uint64_t step0, double max_dev, int device);
+int sdsp_hip_timing_plan_destroy(sdsp_hip_timing_plan *plan);
+/*
+ * x, y, counts: DEVICE pointers; err, period, state: DEVICE pointers or NULL.  Asynchronous on `stream`, one launch, allocates
+ * nothing (stream-capturable); one call per plan in flight.  Errors: null plan, null x, y or counts with samples > 0, x_stride <
+ * samples or an output stride < sdsp_hip_timing_max_out with more than one channel, overlapping ranges, misaligned pointers, an alpha
+ * or beta that is not finite in the precision: SDSP_HIP_ERR_INVALID_ARG; samples >= 2^31: SDSP_HIP_ERR_INVALID_SIZE; a grid that does
+ * not fit one launch: SDSP_HIP_ERR_UNSUPPORTED.  samples == 0: counts is zeroed (when given), nothing else is touched.
+ */
+int sdsp_hip_timing_process(sdsp_hip_timing_plan *plan, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, void *err,
+                            uint64_t err_stride, void *period, uint64_t period_stride, uint32_t *counts, uint64_t samples, double alpha,
+                            double beta, void *state, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_timing_process_host(sdsp_hip_timing_plan *plan, const void *host_x, uint64_t x_stride, void *host_y, uint64_t y_stride,
+                                 void *host_err, uint64_t err_stride, void *host_period, uint64_t period_stride, uint32_t *host_counts,
+                                 uint64_t samples, double alpha, double beta, void *host_state);
+/* bytes of the plan's state buffer (the layout above) */
+int sdsp_hip_timing_state_bytes(const sdsp_hip_timing_plan *plan, uint64_t *bytes);
+/* the capacity a row needs for `samples` inputs: sdsp_hip_timing_max_out_for at the plan's step0 */
+int sdsp_hip_timing_max_out(const sdsp_hip_timing_plan *plan, uint64_t samples, uint64_t *n);
+/* kernel variants (identical bits): 0 = sdsp_timing_kernel (a lane per channel with the loop in registers for the whole call, the
+ * table in LDS, rows transposed through a per-wave LDS ring); 1 = sdsp_timing_plain_kernel, one thread per channel from global memory,
+ * the table read from global memory and the state read-modify-written (the cross-check; it shares no staging logic with variant 0).
+ * Selecting variant 1 allocates one plan-owned state buffer once, for calls without a state buffer. */
+int sdsp_hip_timing_plan_set_variant(sdsp_hip_timing_plan *plan, int variant);
+/* kernel launches of one process call: 1; 0 for samples == 0 */
+int sdsp_hip_timing_plan_launches(const sdsp_hip_timing_plan *plan, uint64_t samples, uint64_t *launches);
+typedef struct {
+    uint64_t channels;
+    uint64_t step0;
+    uint32_t phases, taps;
+    uint32_t block;     /* input samples per time block of sdsp_timing_kernel */
+    uint32_t waves;     /* waves (of 64 channels each) per workgroup of sdsp_timing_kernel, sized from the plan against 160 KiB */
+    uint32_t lds_bytes; /* LDS of one workgroup of sdsp_timing_kernel: the table at its odd row pitch and `waves` rings of
+                           block + taps - 1 rows of 65 complex values */
+    double max_dev;     /* as rounded to the precision */
+    int precision, mode, device, variant;
+    char kernel[64];    /* the kernel the plan's variant runs */
+} sdsp_hip_timing_plan_info;
+int sdsp_hip_timing_plan_get_info(const sdsp_hip_timing_plan *plan, sdsp_hip_timing_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    LMS_REAL, LMS_COMPLEX, LMS_LMS, LMS_NLMS,
                    CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS, CFAR_POWER, CFAR_IQ,
                    PLL_CROSS, PLL_BPSK, PLL_QPSK,
+                   TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -35,6 +36,7 @@ from .lms import lms_bank
 from .rank_filter import rank_filter_bank, medfilt
 from .cfar import cfar_bank, cfar_alpha, cfar
 from .pll import pll_bank, pll_gains
+from .timing import timing_bank, timing_step, timing_max_out, timing_gains, timing_design
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

@@ -221,6 +221,16 @@ class PllPlanInfo(C.Structure):
     ]
 
 
+class TimingPlanInfo(C.Structure):
+    _fields_ = [
+        ("channels", C.c_uint64), ("step0", C.c_uint64), ("phases", C.c_uint32), ("taps", C.c_uint32), ("block", C.c_uint32),
+        ("waves", C.c_uint32), ("lds_bytes", C.c_uint32), ("max_dev", C.c_double),
+        ("precision", C.c_int), ("mode", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
+TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK = 0, 1, 2
+TIMING_MAX_PHASES, TIMING_MAX_TAPS, TIMING_MAX_TABLE = 128, 64, 4096
 PLL_CROSS, PLL_BPSK, PLL_QPSK = 0, 1, 2
 CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3
 CFAR_POWER, CFAR_IQ = 0, 1
@@ -491,6 +501,19 @@ SIGNATURES = {
     "sdsp_hip_pll_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_pll_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_pll_plan_get_info": (_i, [_vp, C.POINTER(PllPlanInfo)]),
+    "sdsp_hip_timing_step": (_i, [_d, C.POINTER(_u64)]),
+    "sdsp_hip_timing_max_out_for": (_i, [_u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_timing_gains": (_i, [_d, _d, _d, _d, C.POINTER(_d), C.POINTER(_d)]),
+    "sdsp_hip_timing_design": (_i, [_u32, _u32, _d, _d, _vp]),
+    "sdsp_hip_timing_plan_create": (_i, [_pp, _u64, _i, _i, _u32, _u32, _vp, _u64, _d, _i]),
+    "sdsp_hip_timing_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_timing_process": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _d, _d, _vp, _vp]),
+    "sdsp_hip_timing_process_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _d, _d, _vp]),
+    "sdsp_hip_timing_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_timing_max_out": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_timing_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_timing_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_timing_plan_get_info": (_i, [_vp, C.POINTER(TimingPlanInfo)]),
 }
 
 _lib = None

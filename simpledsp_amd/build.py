@@ -56,6 +56,7 @@ SOURCES = {
     "rank_filter.hip": [],  # compare-and-select on integer keys only: there is no arithmetic to pin
     "cfar.hip": ["-ffp-contract=off"],  # the I/Q power as stft.hip's; thr = fl(fl(lag + lead) c): a sum then a product, never an FMA
     "pll.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: the complex products and the f64 loop filter never contract; no fast-math
+    "timing.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as pll.hip: the f64 taps, detector and loop filter never contract; no fast-math
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, pll) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, pll, timing) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -96,8 +96,8 @@ struct host_stage {
         bool copy_back; // `host` is writable where this is set
     };
     const char *family;
-    item items[5] = {};
-    void *dev[5] = {};
+    item items[6] = {};
+    void *dev[6] = {};
     size_t n = 0;
 
     host_stage(const char *family_, std::initializer_list<item> list) : family(family_)
@@ -547,6 +547,15 @@ struct sdsp_hip_pll_plan {
     uint32_t *fcw0 = nullptr;  // device: channels centre-frequency words
     void *osc = nullptr;       // device: the tables C then F, 2 x 2048 complex values of the precision
     void *scratch = nullptr;   // a state buffer for the plain kernel of a call without state; made by set_variant(1)
+};
+
+struct sdsp_hip_timing_plan {
+    uint64_t channels = 0, step0 = 0;
+    uint32_t phases = 1, taps = 0;
+    int precision = 0, mode = 0, device = 0, variant = 0;
+    double max_dev = 0.0;    // rounded to the plan precision
+    void *table = nullptr;   // device: H[p][k] = h[k L + p], phases x taps reals of the precision
+    void *scratch = nullptr; // a state buffer for the plain kernel of a call without state; made by set_variant(1)
 };
 
 struct sdsp_hip_arb_plan {
@@ -6510,6 +6519,299 @@ int sdsp_hip_pll_process_host(sdsp_hip_pll_plan *p, const void *host_x, uint64_t
     if (!rc)
         rc = pll_run(p, st.dev[0], x_stride, st.dev[1], y_stride, st.dev[2], err_stride, st.dev[3], freq_stride, samples, alpha, beta,
                      st.dev[4], nullptr);
+    return st.out(rc);
+}
+// ------------------------------------------------------------------ symbol-timing recovery banks (timing.hip)
+
+namespace
+{
+double timing_round(const sdsp_hip_timing_plan *p, double v) { return p->precision == SDSP_HIP_F64 ? v : static_cast<double>(static_cast<float>(v)); }
+
+// byte offsets of the state's arrays: one per field, each at the next multiple of 8 bytes, the history last
+struct timing_layout {
+    uint64_t time, ps, ym, integ, w, parity, hist, bytes;
+};
+timing_layout timing_state_layout(const sdsp_hip_timing_plan *p)
+{
+    const uint64_t ch = p->channels, rs = real_size(p->precision);
+    auto up8 = [](uint64_t v) { return (v + 7) / 8 * 8; };
+    timing_layout l{};
+    uint64_t o = 0;
+    l.time = o;
+    o = up8(o + ch * 8);
+    l.ps = o;
+    o = up8(o + ch * 2 * rs);
+    l.ym = o;
+    o = up8(o + ch * 2 * rs);
+    l.integ = o;
+    o = up8(o + ch * rs);
+    l.w = o;
+    o = up8(o + ch * 4);
+    l.parity = o;
+    o = up8(o + ch * 4);
+    l.hist = o;
+    o = up8(o + ch * (p->taps - 1) * 2 * rs);
+    l.bytes = o;
+    return l;
+}
+
+uint64_t timing_cap(const sdsp_hip_timing_plan *p, uint64_t samples)
+{
+    uint64_t n = 0;
+    (void)sdsp_hip_timing_max_out_for(p->step0, samples, &n); // both in range: checked at plan creation and by timing_check
+    return n;
+}
+
+// argument checks shared by process and process_host (device pointers or not)
+int timing_check(const sdsp_hip_timing_plan *p, const void *x, uint64_t x_stride, const void *y, uint64_t y_stride, const void *err,
+                 uint64_t err_stride, const void *period, uint64_t period_stride, const void *counts, uint64_t samples, double alpha,
+                 double beta)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(timing_round(p, alpha)) || !std::isfinite(timing_round(p, beta)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "alpha and beta must be finite in the plan precision");
+    if (samples == 0)
+        return SDSP_HIP_OK;
+    if (!x || !y || !counts)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x, y and counts must not be null");
+    const uint64_t cap = timing_cap(p, samples);
+    if (p->channels > 1 && (x_stride < samples || y_stride < cap || (err && err_stride < cap) || (period && period_stride < cap)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x_stride must be >= samples and every output stride >= sdsp_hip_timing_max_out of samples");
+    return SDSP_HIP_OK;
+}
+
+int timing_run(sdsp_hip_timing_plan *p, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, void *err, uint64_t err_stride,
+               void *period, uint64_t period_stride, uint32_t *counts, uint64_t samples, double alpha, double beta, void *state,
+               hipStream_t stream)
+{
+    const timing_layout l = timing_state_layout(p);
+    if (p->variant == 1 && !state) { // the plain kernel keeps its state in memory: a zeroed buffer of the plan's
+        if (!p->scratch)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "timing: variant 1 without its scratch state");
+        HIP_TRY(hipMemsetAsync(p->scratch, 0, l.bytes, stream));
+        state = p->scratch;
+    }
+    unsigned char *s = static_cast<unsigned char *>(state);
+    timing_args a{};
+    a.x = x;
+    a.y = y;
+    a.err = err;
+    a.period = period;
+    a.counts = counts;
+    if (s) {
+        a.time = reinterpret_cast<uint64_t *>(s + l.time);
+        a.ps = s + l.ps;
+        a.ym = s + l.ym;
+        a.integ = s + l.integ;
+        a.w = reinterpret_cast<int32_t *>(s + l.w);
+        a.parity = reinterpret_cast<uint32_t *>(s + l.parity);
+        a.hist = s + l.hist;
+    }
+    a.table = p->table;
+    a.channels = p->channels;
+    a.samples = samples;
+    a.x_stride = x_stride;
+    a.y_stride = y_stride;
+    a.err_stride = err_stride;
+    a.period_stride = period_stride;
+    a.step0 = p->step0;
+    a.cap = timing_cap(p, samples);
+    a.phases = p->phases;
+    a.taps = p->taps;
+    a.mode = p->mode;
+    a.alpha = timing_round(p, alpha);
+    a.beta = timing_round(p, beta);
+    a.max_dev = p->max_dev;
+    return launch_timing(p->precision, a, p->variant, stream);
+}
+} // namespace
+
+int sdsp_hip_timing_plan_create(sdsp_hip_timing_plan **out, uint64_t channels, int precision, int mode, uint32_t phases, uint32_t taps,
+                                const double *h, uint64_t step0, double max_dev, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (channels == 0 || channels > 0x7fffffffull)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be in [1, 2^31)");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (mode != SDSP_HIP_TIMING_GARDNER && mode != SDSP_HIP_TIMING_ZC_QPSK && mode != SDSP_HIP_TIMING_ZC_BPSK)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "mode must be SDSP_HIP_TIMING_GARDNER, SDSP_HIP_TIMING_ZC_QPSK or SDSP_HIP_TIMING_ZC_BPSK");
+    if (phases == 0 || phases > SDSP_HIP_TIMING_MAX_PHASES || (phases & (phases - 1)))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "phases must be a power of 2 in [1, SDSP_HIP_TIMING_MAX_PHASES]");
+    if (taps == 0 || taps > SDSP_HIP_TIMING_MAX_TAPS || static_cast<uint64_t>(phases) * taps > SDSP_HIP_TIMING_MAX_TABLE)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps per phase must be in [1, SDSP_HIP_TIMING_MAX_TAPS] and phases * taps <= SDSP_HIP_TIMING_MAX_TABLE");
+    if (step0 < SDSP_HIP_TIMING_MIN_STEP || step0 > SDSP_HIP_TIMING_MAX_STEP)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "step0 must be in [2^32, 2^38]");
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "h is null");
+    const double dev_r = precision == SDSP_HIP_F64 ? max_dev : static_cast<double>(static_cast<float>(max_dev));
+    if (!(dev_r > 0.0 && dev_r <= 0.5)) // NaN included
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "max_dev must be in (0, 0.5] in the plan precision");
+    const size_t n = static_cast<size_t>(phases) * taps;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(precision == SDSP_HIP_F64 ? h[i] : static_cast<double>(static_cast<float>(h[i]))))
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "every tap must be finite in the plan precision");
+    if (int rc = use_device(device))
+        return rc;
+    std::vector<double> tab(n); // H[p][k] = h[k L + p], as sdsp_hip_arb_tables lays it out
+    for (uint32_t p = 0; p < phases; p++)
+        for (uint32_t k = 0; k < taps; k++)
+            tab[static_cast<size_t>(p) * taps + k] = h[static_cast<size_t>(k) * phases + p];
+    auto *p = new sdsp_hip_timing_plan();
+    p->channels = channels;
+    p->step0 = step0;
+    p->phases = phases;
+    p->taps = taps;
+    p->precision = precision;
+    p->mode = mode;
+    p->device = device;
+    p->max_dev = dev_r;
+    const hipError_t e = upload_reals(tab.data(), tab.size(), precision, &p->table);
+    if (e != hipSuccess) {
+        sdsp_hip_timing_plan_destroy(p);
+        return plan_fail(e, "timing");
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_timing_plan_destroy(sdsp_hip_timing_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->table);
+        (void)hipFree(p->scratch);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_timing_state_bytes(const sdsp_hip_timing_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = timing_state_layout(p).bytes;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_timing_max_out(const sdsp_hip_timing_plan *p, uint64_t samples, uint64_t *n)
+{
+    if (!p || !n)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    return sdsp_hip_timing_max_out_for(p->step0, samples, n);
+}
+
+int sdsp_hip_timing_plan_set_variant(sdsp_hip_timing_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    if (variant == 1 && !p->scratch) {
+        if (int rc = use_device(p->device))
+            return rc;
+        const hipError_t e = hipMalloc(&p->scratch, timing_state_layout(p).bytes);
+        if (e != hipSuccess) {
+            p->scratch = nullptr;
+            return plan_fail(e, "timing");
+        }
+    }
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_timing_plan_launches(const sdsp_hip_timing_plan *p, uint64_t samples, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = samples ? 1 : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_timing_plan_get_info(const sdsp_hip_timing_plan *p, sdsp_hip_timing_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->channels = p->channels;
+    info->step0 = p->step0;
+    info->phases = p->phases;
+    info->taps = p->taps;
+    info->block = timing_block(p->precision);
+    info->waves = timing_waves(p->precision, p->phases, p->taps);
+    info->lds_bytes = timing_lds_bytes(p->precision, p->phases, p->taps);
+    info->max_dev = p->max_dev;
+    info->precision = p->precision;
+    info->mode = p->mode;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, timing_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_timing_process(sdsp_hip_timing_plan *p, const void *x, uint64_t x_stride, void *y, uint64_t y_stride, void *err,
+                            uint64_t err_stride, void *period, uint64_t period_stride, uint32_t *counts, uint64_t samples, double alpha,
+                            double beta, void *state, void *stream)
+{
+    if (int rc = timing_check(p, x, x_stride, y, y_stride, err, err_stride, period, period_stride, counts, samples, alpha, beta))
+        return rc;
+    if (misaligned(counts, sizeof(uint32_t)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "counts must be aligned to 4 bytes");
+    if (samples == 0) {
+        if (!counts)
+            return SDSP_HIP_OK;
+        if (int rc = use_device(p->device))
+            return rc;
+        HIP_TRY(hipMemsetAsync(counts, 0, p->channels * sizeof(uint32_t), reinterpret_cast<hipStream_t>(stream)));
+        return SDSP_HIP_OK;
+    }
+    const uint64_t es = esize(p->precision), rs = real_size(p->precision), cap = timing_cap(p, samples);
+    auto span = [&](uint64_t stride, uint64_t n, uint64_t bytes) { return ((p->channels - 1) * stride + n) * bytes; };
+    const void *ptr[6] = { x, y, err, period, counts, state };
+    const uint64_t bytes[6] = { span(x_stride, samples, es), span(y_stride, cap, es),   span(err_stride, cap, rs),
+                                span(period_stride, cap, rs), p->channels * sizeof(uint32_t), timing_state_layout(p).bytes };
+    for (int i = 0; i < 6; i++)
+        for (int j = i + 1; j < 6; j++)
+            if (ranges_overlap(ptr[i], bytes[i], ptr[j], bytes[j]))
+                return fail(SDSP_HIP_ERR_INVALID_ARG, "x, y, err, period, counts and the state buffer must not overlap one another");
+    if (misaligned(x, es) || misaligned(y, es) || misaligned(err, rs) || misaligned(period, rs) || misaligned(state, 8))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "x, y, err and period must be aligned to their element size and state to 8 bytes");
+    if (int rc = use_device(p->device))
+        return rc;
+    return timing_run(p, x, x_stride, y, y_stride, err, err_stride, period, period_stride, counts, samples, alpha, beta, state,
+                      reinterpret_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_timing_process_host(sdsp_hip_timing_plan *p, const void *host_x, uint64_t x_stride, void *host_y, uint64_t y_stride,
+                                 void *host_err, uint64_t err_stride, void *host_period, uint64_t period_stride, uint32_t *host_counts,
+                                 uint64_t samples, double alpha, double beta, void *host_state)
+{
+    if (int rc = timing_check(p, host_x, x_stride, host_y, y_stride, host_err, err_stride, host_period, period_stride, host_counts, samples,
+                              alpha, beta))
+        return rc;
+    if (samples == 0) {
+        if (host_counts)
+            std::memset(host_counts, 0, static_cast<size_t>(p->channels) * sizeof(uint32_t));
+        return SDSP_HIP_OK;
+    }
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t es = esize(p->precision), rs = real_size(p->precision), cap = timing_cap(p, samples);
+    auto span = [&](uint64_t stride, uint64_t n, uint64_t bytes) { return static_cast<size_t>(((p->channels - 1) * stride + n) * bytes); };
+    host_stage st("timing", { { host_x, span(x_stride, samples, es), false },
+                              { host_y, span(y_stride, cap, es), true },
+                              { host_err, span(err_stride, cap, rs), true },
+                              { host_period, span(period_stride, cap, rs), true },
+                              { host_counts, static_cast<size_t>(p->channels) * sizeof(uint32_t), true },
+                              { host_state, static_cast<size_t>(timing_state_layout(p).bytes), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = timing_run(p, st.dev[0], x_stride, st.dev[1], y_stride, st.dev[2], err_stride, st.dev[3], period_stride,
+                        static_cast<uint32_t *>(st.dev[4]), samples, alpha, beta, st.dev[5], nullptr);
     return st.out(rc);
 }
 }

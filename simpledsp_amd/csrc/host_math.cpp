@@ -719,6 +719,87 @@ int sdsp_hip_pll_gains(double bn, double zeta, double amplitude, int mode, doubl
     *beta = 4.0 * theta * theta / (d * kd * (2.0 * M_PI));
     return SDSP_HIP_OK;
 }
+// symbol-timing recovery banks: L a power of two in [1, 128], T in [1, 64], L T <= 4096
+static int timing_check_shape(uint32_t phases, uint32_t taps)
+{
+    if (phases == 0 || phases > SDSP_HIP_TIMING_MAX_PHASES || (phases & (phases - 1)))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "phases must be a power of 2 in [1, SDSP_HIP_TIMING_MAX_PHASES]");
+    if (taps == 0 || taps > SDSP_HIP_TIMING_MAX_TAPS || static_cast<uint64_t>(phases) * taps > SDSP_HIP_TIMING_MAX_TABLE)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "taps per phase must be in [1, SDSP_HIP_TIMING_MAX_TAPS] and phases * taps <= SDSP_HIP_TIMING_MAX_TABLE");
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_timing_step(double sps, uint64_t *step0)
+{
+    if (!step0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *step0 = 0;
+    if (!(sps >= 2.0 && sps <= 128.0)) // NaN included
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "samples per symbol must be in [2, 128]");
+    // the scaling is exact; ties go to the even word (Python's round)
+    *step0 = static_cast<uint64_t>(std::nearbyint(sps * 2147483648.0));
+    return SDSP_HIP_OK;
+}
+// every half step is at least step0 - 2^31, so at most n = ceil(S 2^32 / (step0 - 2^31)) strobes start below S (the first at t >= 0); a
+// call that begins on a symbol strobe has (n + 1) / 2 of them
+static uint64_t timing_max_out_of(uint64_t step0, uint64_t samples)
+{
+    const uint64_t least = step0 - (1ull << 31), n = ((samples << 32) + least - 1) / least; // samples < 2^31: below 2^63
+    return (n + 1) / 2;
+}
+int sdsp_hip_timing_max_out_for(uint64_t step0, uint64_t samples, uint64_t *n)
+{
+    if (!n)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *n = 0;
+    if (step0 < SDSP_HIP_TIMING_MIN_STEP || step0 > SDSP_HIP_TIMING_MAX_STEP)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "step0 must be in [2^32, 2^38]");
+    if (samples >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "samples must be below 2^31");
+    *n = timing_max_out_of(step0, samples);
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_timing_gains(double bn, double zeta, double kd, double sps, double *alpha, double *beta)
+{
+    if (!alpha || !beta)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    *alpha = *beta = 0.0;
+    if (!(std::isfinite(bn) && bn > 0.0 && std::isfinite(zeta) && zeta > 0.0 && std::isfinite(kd) && kd > 0.0 && std::isfinite(sps) && sps > 0.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bn, zeta, kd and sps must be finite and > 0");
+    const double theta = bn / (zeta + 1.0 / (4.0 * zeta)), d = 1.0 + 2.0 * zeta * theta + theta * theta;
+    *alpha = 4.0 * zeta * theta / (d * kd) * sps / 2.0;
+    *beta = 4.0 * theta * theta / (d * kd) * sps / 2.0;
+    return SDSP_HIP_OK;
+}
+int sdsp_hip_timing_design(uint32_t phases, uint32_t taps, double sps, double rolloff, double *h)
+{
+    if (int rc = timing_check_shape(phases, taps))
+        return rc;
+    if (!h)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null output pointer");
+    if (!(std::isfinite(sps) && sps > 0.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "samples per symbol must be finite and > 0");
+    if (!(rolloff > 0.0 && rolloff <= 1.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "rolloff must be in (0, 1]");
+    const uint64_t n = static_cast<uint64_t>(phases) * taps;
+    const double centre = 0.5 * static_cast<double>(n - 1), per_symbol = sps * phases, b = rolloff;
+    double sum = 0.0;
+    for (uint64_t j = 0; j < n; j++) {
+        const double tau = (static_cast<double>(j) - centre) / per_symbol; // in symbols
+        const double u = 4.0 * b * tau;
+        double v;
+        if (tau == 0.0)
+            v = 1.0 - b + 4.0 * b / M_PI;
+        else if (std::fabs(std::fabs(u) - 1.0) < 1e-9) // |tau| = 1 / (4 b): the limit, exact to the second order of the distance
+            v = b / std::sqrt(2.0) * ((1.0 + 2.0 / M_PI) * std::sin(M_PI / (4.0 * b)) + (1.0 - 2.0 / M_PI) * std::cos(M_PI / (4.0 * b)));
+        else
+            v = (std::sin(M_PI * tau * (1.0 - b)) + u * std::cos(M_PI * tau * (1.0 + b))) / (M_PI * tau * (1.0 - u * u));
+        h[j] = v;
+        sum += v;
+    }
+    for (uint64_t j = 0; j < n; j++)
+        h[j] *= static_cast<double>(phases) / sum;
+    return SDSP_HIP_OK;
+}
 int sdsp_hip_ddc_out_samples(uint32_t down, uint64_t samples, uint64_t *out)
 {
     if (!out)

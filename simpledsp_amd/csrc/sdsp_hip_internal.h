@@ -469,6 +469,31 @@ const char *pll_kernel_for(int variant);
 uint32_t pll_block(int precision);
 uint32_t pll_waves(int precision);
 uint32_t pll_lds_bytes(int precision);
+// Symbol-timing recovery banks (timing.hip): the one launch of a call
+struct timing_args {
+    const void *x;
+    void *y, *err, *period; // err and period nullable: not written
+    uint32_t *counts;       // channels words: each channel's symbols of this call
+    // the arrays of the state buffer, all null for variant 0 without state (zero state, nothing kept)
+    uint64_t *time;         // channels Q32.32 stream times
+    void *ps, *ym;          // channels complex values each
+    void *integ;            // channels reals
+    int32_t *w;             // channels advance words
+    uint32_t *parity;       // channels words, 0 or 1
+    void *hist;             // channels x (taps - 1) complex values, newest first
+    const void *table;      // [phase][tap] reals of the precision
+    uint64_t channels, samples, x_stride, y_stride, err_stride, period_stride, step0;
+    uint64_t cap;           // sdsp_hip_timing_max_out of samples: no row is written at or past it
+    uint32_t phases, taps;
+    int mode;
+    double alpha, beta, max_dev; // already rounded to the plan precision
+};
+int launch_timing(int precision, const timing_args &a, int variant, void *stream);
+const char *timing_kernel_for(int variant);
+// samples per input block, waves per workgroup and LDS bytes per workgroup of sdsp_timing_kernel
+uint32_t timing_block(int precision);
+uint32_t timing_waves(int precision, uint32_t phases, uint32_t taps);
+uint32_t timing_lds_bytes(int precision, uint32_t phases, uint32_t taps);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
