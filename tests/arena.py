@@ -14,6 +14,9 @@ The second half (`Buffers` and the `check_*_bank` functions) frames EVERY buffer
 accumulators -- and drives a "bank": any object with the few members listed at `check_framed_bank`.  The HIP banks of
 tests/test_gpu_stream_isolation.py and the numpy stand-ins of tests/test_arena_host.py (with planted defects) go through the same
 functions, on "cuda" and on "cpu".
+
+The third part (`WideRows`, `run_placed`, `check_wide`) puts ONE buffer of a call at a row distance past `wrap` bytes (2^32 on the
+device, 2^16 for the stand-ins of tests/test_arena_host.py), so that an offset truncated to log2(wrap) bits lands in row 0's data.
 """
 import math
 
@@ -21,9 +24,12 @@ NAN = float("nan")
 
 
 def fills(dtype):
-    """the two fills every framed case runs under: all-NaN and a finite pattern (7 + 3j / 7.0)"""
+    """the two fills every framed case runs under: all-NaN and a finite pattern (7 + 3j / 7.0); integer types have no NaN and take
+    0x55 in its place"""
     if dtype.is_complex:
         return (complex(NAN, NAN), complex(7.0, 3.0))
+    if not dtype.is_floating_point:
+        return (0x55, 7)
     return (NAN, 7.0)
 
 
@@ -321,3 +327,142 @@ def edge_units(channels, frames, per_slice):
     c = seam[0] // frames
     out += [(f"last frame of channel {c - 1}, in the slice of the next", c - 1, frames - 1), (f"first frame of channel {c}", c, 0)]
     return out
+
+
+# ------------------------------------------------------------------ one buffer of a call with its two rows more than `wrap` apart
+
+WIDE_GUARD = 4096  # bytes on either side of each wide row that are filled, and must keep their bits
+
+
+def wide_distance(element_size, wrap=1 << 32):
+    """bytes from row 0 to row 1.  4-byte elements and wider: 4 wrap + 256, so that the stride in 4-byte units is wrap + 64 and both the
+    element index (4-byte types) and the byte offset (every type) pass `wrap`; narrower elements: wrap + 64.  Truncated to log2(wrap)
+    bits the offset is 256 (64) bytes: inside row 0, whose rows are at least 160 elements long."""
+    return 4 * wrap + 256 if element_size >= 4 else wrap + 64
+
+
+def raw(t):
+    """t's bytes, flat: equality on them is exact, NaN-safe and works for every dtype"""
+    import torch
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+class Placed:
+    """Where a (rows, cols) buffer of a call lies: `base` is a flat typed tensor, element (r, c) is base[offset + r stride + c].  A device
+    entry gets `ptr` and `stride`; a numpy stand-in indexes `base` itself, with whatever arithmetic it wants to get wrong."""
+
+    def __init__(self, base, offset, stride, rows, cols):
+        self.base, self.offset, self.stride, self.rows, self.cols = base, offset, stride, rows, cols
+
+    @property
+    def ptr(self):
+        return self.base.data_ptr() + self.offset * self.base.element_size()
+
+    def row(self, r):
+        return self.base[self.offset + r * self.stride:self.offset + r * self.stride + self.cols]
+
+    def get(self):
+        import torch
+        return torch.stack([self.row(r) for r in range(self.rows)]).clone()
+
+    def put(self, t):
+        for r in range(self.rows):
+            self.row(r).copy_(t.reshape(self.rows, self.cols)[r])
+
+
+class WideRows(Placed):
+    """Two rows of `cols` elements of `dtype` inside the flat byte tensor `flat`, `wide_distance` apart, row 0 one guard band in.  The
+    rows and WIDE_GUARD bytes on either side of each are `fill`; nothing else of `flat` is touched or looked at."""
+
+    def __init__(self, torch, flat, dtype, cols, fill, wrap=1 << 32):
+        assert flat.dtype == torch.uint8 and flat.dim() == 1 and flat.is_contiguous()
+        es = torch.empty((), dtype=dtype).element_size()
+        self.distance = wide_distance(es, wrap)
+        assert self.distance % es == 0 and WIDE_GUARD % es == 0
+        assert cols * es > self.distance % wrap, "the truncated offset must fall inside row 0"
+        assert cols * es + 2 * WIDE_GUARD < wrap, "a row and its bands stay below the wrap"
+        assert 2 * WIDE_GUARD + self.distance + cols * es <= flat.numel(), "the flat buffer is too small"
+        Placed.__init__(self, flat.view(dtype), WIDE_GUARD // es, self.distance // es, 2, cols)
+        self.windows = [flat[r * self.distance:r * self.distance + 2 * WIDE_GUARD + cols * es] for r in (0, 1)]
+        for w in self.windows:
+            w.view(dtype).fill_(fill)
+        self.before = None
+
+    def mark(self):
+        self.before = [w.clone() for w in self.windows]
+
+    def assert_guards(self, tag=""):
+        import torch
+        for r, (w, b) in enumerate(zip(self.windows, self.before)):
+            for side, sl in (("before", slice(0, WIDE_GUARD)), ("after", slice(w.numel() - WIDE_GUARD, w.numel()))):
+                if not bool(torch.equal(w[sl], b[sl])):
+                    at = int(torch.nonzero(w[sl] != b[sl])[0])
+                    raise AssertionError(f"{tag}: the guard band {side} wide row {r} was written, first at byte {at} of the band")
+
+    def unchanged(self):
+        import torch
+        return all(bool(torch.equal(w, b)) for w, b in zip(self.windows, self.before))
+
+
+def run_placed(torch, specs, call, fill, wide=None, flat=None, wrap=1 << 32, device="cuda", tag="", guards=None):
+    """One call with every buffer placed.  specs: {name: dict(shape = (rows, cols), dtype, init = tensor or None, read_only = bool)};
+    every buffer is an ordinary, exactly-sized tensor except `wide`, whose two rows go into `flat` (WideRows).  All of them are
+    fills(dtype)[fill] except where `init` goes.  call(placed) -> status, placed = {name: Placed}.
+    Status 0: returns (0, {name: contents after the call}), after checking that read-only buffers kept their bits and the wide rows'
+    guard bands theirs (with a list for `guards`, the WideRows is appended to it and its bands are left to the caller).  Any other
+    status is a refusal: nothing at all may have changed, and (status, None) is returned."""
+    placed, before = {}, {}
+    for name, s in specs.items():
+        rows, cols = s["shape"]
+        f = fills(s["dtype"])[fill]
+        if name == wide:
+            assert rows == 2, (tag, name, "the wide buffer has two rows", rows)
+            placed[name] = WideRows(torch, flat, s["dtype"], cols, f, wrap)
+        else:
+            placed[name] = Placed(torch.full((rows * cols,), f, dtype=s["dtype"], device=device), 0, cols, rows, cols)
+        if s.get("init") is not None:
+            placed[name].put(s["init"].to(device))
+        before[name] = placed[name].get()
+    if wide is not None:
+        placed[wide].mark()
+    status = call(placed)
+    if device != "cpu":
+        torch.cuda.synchronize()
+    after = {name: p.get() for name, p in placed.items()}
+    if status != 0:
+        for name in specs:
+            assert bool(torch.equal(raw(after[name]), raw(before[name]))), (tag, f"refused with {status}, but '{name}' changed")
+        assert wide is None or placed[wide].unchanged(), (tag, f"refused with {status}, but the wide rows or their bands changed")
+        return status, None
+    for name, s in specs.items():
+        if s.get("read_only") and not bool(torch.equal(raw(after[name]), raw(before[name]))):
+            raise AssertionError(f"{tag}: read-only buffer '{name}' was written")
+    if wide is not None and guards is None:
+        placed[wide].assert_guards(tag)
+    elif wide is not None:
+        guards.append(placed[wide])
+    return 0, after
+
+
+def check_wide(torch, specs, call, clean, wide, flat, wrap=1 << 32, device="cuda", tag=""):
+    """clean = [results under fill 0, results under fill 1] of run_placed with every buffer compact.  The same call with `wide` in
+    `flat` gives, under each fill, clean's bits in every buffer -- or is refused under both, and the status is returned."""
+    codes = []
+    for fill in (0, 1):
+        where = f"{tag} '{wide}' wide, fill {fill}"
+        held = []  # the contents first, then the bands: a truncated write shows as what it is
+        status, got = run_placed(torch, specs, call, fill, wide, flat, wrap, device, where, held)
+        codes.append(status)
+        if status != 0:
+            continue
+        for name, want in clean[fill].items():
+            a, b = raw(got[name]), raw(want)
+            if a.shape != b.shape or not bool(torch.equal(a, b)):
+                es = want.element_size()
+                at = torch.nonzero(a != b).flatten() // es
+                cols = specs[name]["shape"][1]
+                raise AssertionError(f"{where}: '{name}' differs from the compact call in {int(at.unique().numel())} element(s), the first "
+                                     f"at row {int(at[0]) // cols}, column {int(at[0]) % cols}")
+        held[0].assert_guards(where)
+    assert codes[0] == codes[1], (tag, wide, codes)
+    return codes[0]

@@ -9,7 +9,11 @@ relies on for the HIP kernels.
 
 The second half does the same for the streaming-bank harness (arena.Buffers, check_framed_bank, check_poisoned_bank) that
 tests/test_gpu_stream_isolation.py runs the HIP banks through: numpy stand-ins of an STFT and an inverse STFT bank pass it, and
-each of seven planted defects is reported by the assertion meant for it."""
+each of seven planted defects is reported by the assertion meant for it.
+
+The third part does it for the wide-row harness (arena.WideRows, run_placed, check_wide) of tests/test_gpu_wide_strides.py, at a wrap of
+2^16 in place of 2^32: a stand-in that narrows the row offset of `in` or of `out` to 16 bits -- in elements or in bytes -- fails the
+bit comparison, the narrowed write leaves row 1 at its fill, and a refusal that changed a buffer is reported."""
 import numpy as np
 import pytest
 import torch
@@ -332,3 +336,122 @@ def test_bits_are_exact_and_nan_safe():
     assert not arena.same_bits(torch.tensor([0.0]), torch.tensor([-0.0]))
     assert arena.bits(torch.zeros(3, dtype=torch.complex64)).shape == (3, 2)
     assert arena.bits(torch.zeros(3, dtype=torch.complex128)).dtype == torch.int64
+
+
+# ------------------------------------------------------------------ one buffer with its rows more than `wrap` bytes apart
+
+WRAP = 1 << 16  # the stand-ins' "2^32": tests/test_gpu_wide_strides.py runs the same functions with the real one
+WIDE_COLS = 200
+
+
+class WideStandIn:
+    """out[c] = 2 in[c] + history[c] for two rows, with the row offsets formed the way a kernel forms them: c * stride in elements,
+    or that times the element size in bytes.  `fault` = (buffer, unit) truncates that buffer's offset in that unit to 16 bits;
+    refuse = (status, writes) returns the status without computing, after writing one element of out when `writes`."""
+
+    def __init__(self, dtype, fault=None, refuse=None):
+        self.dtype, self.fault, self.refuse = dtype, fault, refuse
+        g = torch.Generator().manual_seed(11)
+        self.x = torch.randn((2, WIDE_COLS), generator=g, dtype=torch.float64).to(dtype)
+        self.h = torch.randn((2, 1), generator=g, dtype=torch.float64).to(dtype)
+
+    def specs(self):
+        return {"in": dict(shape=(2, WIDE_COLS), dtype=self.dtype, init=self.x, read_only=True),
+                "out": dict(shape=(2, WIDE_COLS), dtype=self.dtype, init=None),
+                "state": dict(shape=(2, 1), dtype=self.dtype, init=self.h)}
+
+    def offset(self, name, p, c):
+        off = c * p.stride
+        if self.fault == (name, "elements"):
+            off %= WRAP
+        es = p.base.element_size()
+        if self.fault == (name, "bytes"):
+            off = (off * es % WRAP) // es
+        return p.offset + off
+
+    def call(self, p):
+        if self.refuse:
+            if self.refuse[1]:
+                p["out"].base[p["out"].offset] = 0
+            return self.refuse[0]
+        for c in range(2):
+            i, o = self.offset("in", p["in"], c), self.offset("out", p["out"], c)
+            x = p["in"].base[i:i + WIDE_COLS].clone()
+            p["out"].base[o:o + WIDE_COLS] = 2 * x + p["state"].row(c)
+            p["state"].row(c).copy_(x[-1:])
+        return 0
+
+
+def _wide_flat():
+    return torch.empty(arena.wide_distance(4, WRAP) + (1 << 14), dtype=torch.uint8)
+
+
+def _wide_drive(bank, wide, flat=None):
+    flat = _wide_flat() if flat is None else flat
+    ok = WideStandIn(bank.dtype)
+    clean = [arena.run_placed(torch, ok.specs(), ok.call, fill, device="cpu")[1] for fill in (0, 1)]
+    assert bool(torch.equal(clean[0]["out"], 2 * ok.x + ok.h)) and arena.same_bits(clean[0]["out"], clean[1]["out"])
+    return arena.check_wide(torch, bank.specs(), bank.call, clean, wide, flat, WRAP, "cpu")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.complex64, torch.int32])
+@pytest.mark.parametrize("wide", ["in", "out"])
+def test_wide_rows_correct_stand_in_passes(dtype, wide):
+    assert _wide_drive(WideStandIn(dtype), wide) == 0
+
+
+def test_wide_rows_geometry():
+    """4-byte elements pass the wrap in elements and in bytes, 8-byte ones in bytes only; either way the truncated offset is 256 bytes"""
+    assert arena.wide_distance(4) == (1 << 34) + 256 and arena.wide_distance(1) == (1 << 32) + 64
+    for dtype, elems in ((torch.float32, (1 << 32) + 64), (torch.complex64, (1 << 31) + 32), (torch.complex128, (1 << 30) + 16)):
+        es = torch.empty((), dtype=dtype).element_size()
+        assert arena.wide_distance(es) // es == elems and arena.wide_distance(es) % (1 << 32) == 256
+    w = arena.WideRows(torch, _wide_flat(), torch.float32, WIDE_COLS, 7.0, WRAP)
+    assert w.stride == WRAP + 64 and w.stride % WRAP == 64 and w.ptr == w.base.data_ptr() + arena.WIDE_GUARD
+    assert arena.WideRows(torch, _wide_flat(), torch.float64, WIDE_COLS, 7.0, WRAP).stride == WRAP // 2 + 32  # below the wrap in elements
+    with pytest.raises(AssertionError, match="inside row 0"):
+        arena.WideRows(torch, _wide_flat(), torch.float32, 64, 7.0, WRAP)
+
+
+@pytest.mark.parametrize("dtype,unit", [(torch.float32, "elements"), (torch.float32, "bytes"), (torch.float64, "bytes")])
+def test_wide_rows_truncated_read_is_reported(dtype, unit):
+    """row 1 of out is then row 0 of in, shifted: finite, plausible values that only the comparison with the compact call sees"""
+    with pytest.raises(AssertionError, match="'in' wide, fill 0: 'out' differs from the compact call in 200 element.*row 1, column 0"):
+        _wide_drive(WideStandIn(dtype, ("in", unit)), "in")
+    assert _wide_drive(WideStandIn(dtype, ("in", unit)), "out") == 0  # the fault needs the buffer it sits in to be the wide one
+
+
+@pytest.mark.parametrize("dtype,unit", [(torch.float32, "elements"), (torch.float32, "bytes"), (torch.float64, "bytes")])
+def test_wide_rows_truncated_write_is_reported_and_leaves_row_1_at_its_fill(dtype, unit):
+    flat = _wide_flat()
+    with pytest.raises(AssertionError, match="'out' wide, fill 0: 'out' differs from the compact call.*row 0"):
+        _wide_drive(WideStandIn(dtype, ("out", unit)), "out", flat)
+    es = torch.empty((), dtype=dtype).element_size()
+    row1 = flat[arena.wide_distance(es, WRAP) + arena.WIDE_GUARD:][:WIDE_COLS * es].view(dtype)
+    assert bool(torch.isnan(row1).all())  # fill 0: nothing was ever written there
+    row0 = flat[arena.WIDE_GUARD:][:WIDE_COLS * es].view(dtype)
+    assert not bool(torch.isnan(row0[256 // es:]).any())  # row 1's result landed 256 bytes into row 0
+
+
+def test_wide_rows_element_truncation_is_invisible_to_eight_byte_types():
+    """what the device module's docstring says: the stride of an 8-byte type stays below the wrap in elements"""
+    assert _wide_drive(WideStandIn(torch.float64, ("in", "elements")), "in") == 0
+
+
+def test_wide_rows_write_into_a_guard_band_is_reported():
+    class Past(WideStandIn):
+        def call(self, p):
+            WideStandIn.call(self, p)
+            o = p["out"]
+            o.base[o.offset + o.stride + WIDE_COLS] = 1.0  # one element past wide row 1
+            return 0
+    with pytest.raises(AssertionError, match="guard band after wide row 1 was written, first at byte 2 of the band"):  # 1.0f and the NaN fill share their low bytes
+        _wide_drive(Past(torch.float32), "out")
+
+
+def test_wide_rows_refusal_must_change_nothing():
+    assert _wide_drive(WideStandIn(torch.float32, refuse=(22, False)), "in") == 22
+    with pytest.raises(AssertionError, match="refused with 22, but 'out' changed"):
+        _wide_drive(WideStandIn(torch.float32, refuse=(22, True)), "in")
+    with pytest.raises(AssertionError, match="'out' wide, fill 0.*refused with 22, but 'out' changed"):
+        _wide_drive(WideStandIn(torch.float32, refuse=(22, True)), "out")
