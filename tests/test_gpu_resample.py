@@ -46,6 +46,14 @@ def _dev(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+def _matches(got, ref, precision):
+    """the bank against tests/resample_ref.py fed the taps of the precision: f64 bit for bit, f32 to 1e-6 normwise (the reference sums
+    in double)"""
+    if precision == "f64":
+        return np.array_equal(got, ref)
+    return got.shape == ref.shape and (ref.size == 0 or rel_max_err(got, ref) <= 1e-6 or np.abs(ref).max() == 0)
+
+
 def _samples(up, down, at_least):
     q = q_of(up, down)
     return q * max(1, -(-at_least // q))
@@ -76,7 +84,7 @@ def test_f64_bit_exact_against_reference_all_variants(sd, torch_cuda, up, down, 
             torch_cuda.cuda.synchronize()
             got = out.cpu().numpy()
             assert got.shape == (channels, M)
-            assert np.array_equal(got, want), (variant, channels, samples)
+            assert _matches(got, want, "f64"), (variant, channels, samples)
             if H:
                 assert np.array_equal(r.state.cpu().numpy(), want_state), variant
             outs.append(got)
@@ -107,7 +115,7 @@ def test_equals_zero_stuff_fir_filter_slice_on_gpu(sd, torch_cuda, up, down, pre
         assert np.array_equal(got, want), (taps, precision)
         if precision == "f32":
             ref, _ = resample_ref(h.astype(np.float32), x, up, down)
-            assert rel_max_err(got, ref) <= 1e-6 or np.abs(ref).max() == 0
+            assert _matches(got, ref, "f32")
 
 
 def test_unit_ratio_equals_fir_filter_output_and_state(sd, torch_cuda):
