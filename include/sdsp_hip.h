@@ -242,6 +242,68 @@ int sdsp_hip_fft_plan_get_twiddles(const sdsp_hip_fft_plan *plan, void *host_out
  * (fft_tile.hip), which the tests use as an independent implementation. */
 int sdsp_hip_fft_plan_set_variant(sdsp_hip_fft_plan *plan, int variant);
 
+/*
+ * Column plans: batched transforms along the STRIDED axis.  Where sdsp_hip_fft_exec transforms the contiguous
+ * rows of batch x n, a column plan transforms every column of `batch` compact row-major cubes of n rows x width columns -- the Doppler
+ * step of a pulse-Doppler chain ([cube][pulse][range bin], one transform per range bin across the pulses) and the second axis of a 2-D
+ * transform -- in one read and one write of the cube, with no transpose and no workspace.
+ *   - layout.  in: batch cubes of n rows x width interleaved complex elements of the plan precision (F32 or F64); element [b][p][r] is
+ *     at (b n + p) width + r, and column r of cube b is the sequence x[p] = in[b][p][r], p = 0 .. n - 1.  out has the same [b][k][r]
+ *     layout and holds complex elements (COMPLEX) or real elements (POWER).  Cubes are compact: there is no row pitch.
+ *   - transform.  X[k] = sum_p v[p] W_n^(p k) with the conventions of fft.h:121-146: FORWARD W = e^(-2 pi i / n); REVERSE the
+ *     conjugate and a 1/n scale.  The twiddles are sdsp_hip_calc_twiddles's, rounded once to the precision.  n is a power of two,
+ *     SDSP_HIP_FFT_COLS_MIN_N <= n <= SDSP_HIP_FFT_COLS_MAX_N; width >= 1 is any number; batch n width < 2^40.
+ *   - window.  NULL or n host doubles, each rounded once to the precision at plan creation; v[p] = x[p] w[p], one product per component
+ *     (the kernel may fuse it into the first butterfly).  Without a window v = x.  Only FORWARD plans take a window.
+ *   - shift != 0 puts zero Doppler in the middle: a FORWARD plan writes X[k] to row (k + n/2) mod n, a REVERSE plan reads x[p] from row
+ *     (p + n/2) mod n, so that reverse undoes forward (n is even).
+ *   - POWER writes re re + im im of X[k] as a real row: the layout sdsp_hip_cfar_process takes as batch n channel-major rows of width
+ *     powers.  Only FORWARD plans allow it.
+ *   - in place and overlap.  COMPLEX: out == in (the same pointer) or disjoint ranges.  POWER: disjoint ranges.  Any other overlap is
+ *     SDSP_HIP_ERR_INVALID_ARG.  in is never written out of place.
+ *   - pointers need the alignment of one element of their own type (in: one complex element; out: one complex element, POWER one
+ *     real) and no more.  exec is asynchronous on `stream`, allocates nothing and can be captured in a graph; batch == 0 does nothing.
+ *   - accuracy.  Nothing at bit level is promised against the row plans; the results meet their tolerances: f64 within 4 n eps of the
+ *     double transform relative to max |X| of the column, f32 within 1e-6 normwise.
+ *   - independence.  The bits of a column's n outputs depend on that column's n inputs, the window and the plan (n, direction,
+ *     precision, output, shift, variant) only: not on width, the column's position r, the cube index, batch, the neighbouring columns
+ *     (a NaN stays in its column), in place or out of place, or the alignment of the pointers beyond one element.
+ * Errors: n not a power of two or out of range, width == 0, the size limit exceeded: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an
+ * unknown direction, output or precision, a window or POWER on a REVERSE plan, a window value that is not finite once rounded, a
+ * misaligned pointer, a refused overlap: SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE.  Arguments are checked before a
+ * device is looked for.
+ */
+typedef struct sdsp_hip_fft_cols_plan sdsp_hip_fft_cols_plan;
+#define SDSP_HIP_FFT_COLS_COMPLEX 0
+#define SDSP_HIP_FFT_COLS_POWER 1
+#define SDSP_HIP_FFT_COLS_MIN_N 8
+#define SDSP_HIP_FFT_COLS_MAX_N 1024
+int sdsp_hip_fft_cols_plan_create(sdsp_hip_fft_cols_plan **plan, uint32_t n, uint64_t width, int direction, int precision,
+                                  int output, int shift, const double *window, int device);
+int sdsp_hip_fft_cols_plan_destroy(sdsp_hip_fft_cols_plan *plan);
+/* in, out: DEVICE pointers to batch cubes */
+int sdsp_hip_fft_cols_exec(sdsp_hip_fft_cols_plan *plan, const void *in, void *out, uint64_t batch, void *stream);
+/* same with HOST pointers (synchronous); host_out == host_in transforms in place */
+int sdsp_hip_fft_cols_exec_host(sdsp_hip_fft_cols_plan *plan, const void *host_in, void *host_out, uint64_t batch);
+/* kernel variants (same tolerances, no common bits promised): 0 = sdsp_fft_cols_kernel, whose form depends on n and the precision only
+ * -- n <= 32: one lane per column, the column in registers, no LDS; n >= 64: tiles of 16 adjacent columns, n / 32 threads per column,
+ * two register passes around one exchange through LDS --; 1 = sdsp_fft_cols_plain_kernel, one thread per output summing the DFT from
+ * global memory in double (the cross-check; it shares no staging or butterfly code with variant 0). */
+int sdsp_hip_fft_cols_plan_set_variant(sdsp_hip_fft_cols_plan *plan, int variant);
+/* kernel launches of one exec of `batch` cubes: one where the grid fits, else consecutive launches over whole cubes; 0 for batch == 0 */
+int sdsp_hip_fft_cols_plan_launches(const sdsp_hip_fft_cols_plan *plan, uint64_t batch, uint64_t *launches);
+typedef struct {
+    uint32_t n;
+    uint64_t width;
+    int direction, precision, output, shift, windowed, device, variant;
+    uint32_t tile_columns;      /* adjacent columns that one tile of the variant's kernel transforms together */
+    uint32_t threads;           /* of one workgroup */
+    uint32_t lds_bytes;         /* of one workgroup */
+    uint64_t algorithmic_bytes; /* per cube: n width (complex element + output element), read once plus write once */
+    char kernel[64];            /* the kernel the plan's variant runs */
+} sdsp_hip_fft_cols_plan_info;
+int sdsp_hip_fft_cols_plan_get_info(const sdsp_hip_fft_cols_plan *plan, sdsp_hip_fft_cols_plan_info *info);
+
 /* ------------------------------------------------------------------ cascaded biquads */
 
 /*

@@ -13,9 +13,11 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS, CFAR_POWER, CFAR_IQ,
                    PLL_CROSS, PLL_BPSK, PLL_QPSK,
                    TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK,
+                   FFT_COLS_COMPLEX, FFT_COLS_POWER,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
+from .fft_cols import FftColsPlan, fft2, ifft2
 from .iir import casc_2o_iir, casc_2o_iir_lp, casc_2o_iir_hp, casc_2o_iir_bp
 from .fir import fir_filter, fft_fir_filter, fir_fft_size
 from .resample import fir_resampler

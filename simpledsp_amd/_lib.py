@@ -39,6 +39,18 @@ class PlanInfo(C.Structure):
     ]
 
 
+class FftColsPlanInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32), ("width", C.c_uint64), ("direction", C.c_int), ("precision", C.c_int), ("output", C.c_int),
+        ("shift", C.c_int), ("windowed", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("tile_columns", C.c_uint32),
+        ("threads", C.c_uint32), ("lds_bytes", C.c_uint32), ("algorithmic_bytes", C.c_uint64), ("kernel", C.c_char * 64),
+    ]
+
+
+FFT_COLS_COMPLEX, FFT_COLS_POWER = 0, 1
+FFT_COLS_MIN_N, FFT_COLS_MAX_N = 8, 1024
+
+
 class FirPlanInfo(C.Structure):
     _fields_ = [
         ("taps", C.c_uint32), ("precision", C.c_int), ("device", C.c_int), ("method", C.c_int),
@@ -293,6 +305,13 @@ SIGNATURES = {
     "sdsp_hip_fft_plan_status": (_i, [_vp]),
     "sdsp_hip_fft_plan_set_wait_limit": (_i, [_vp, _u64]),
     "sdsp_hip_fft_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_fft_cols_plan_create": (_i, [_pp, _u32, _u64, _i, _i, _i, _i, _vp, _i]),
+    "sdsp_hip_fft_cols_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_fft_cols_exec": (_i, [_vp, _vp, _vp, _u64, _vp]),
+    "sdsp_hip_fft_cols_exec_host": (_i, [_vp, _vp, _vp, _u64]),
+    "sdsp_hip_fft_cols_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_fft_cols_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_fft_cols_plan_get_info": (_i, [_vp, C.POINTER(FftColsPlanInfo)]),
     "sdsp_hip_set_launch_piece_bytes": (_i, [_u64]),
     "sdsp_hip_get_launch_piece_bytes": (_i, [C.POINTER(_u64)]),
     "sdsp_hip_iir_design_lp": (_i, [_u32, _d, _d, _d, _vp, _vp, C.POINTER(_d)]),

@@ -41,6 +41,7 @@ SOURCES = {
     "fft_wave.hip": ["-fno-slp-vectorize"],
     "fft_mid.hip": ["-fno-slp-vectorize"],
     "fft_2pass.hip": ["-fno-slp-vectorize"],
+    "fft_cols.hip": ["-fno-slp-vectorize"],
     "iir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "iir_filtfilt.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # iir.hip's recurrence (iir_step.h), bit for bit
     "fir.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # f64 taps: multiply then add, like the oracle

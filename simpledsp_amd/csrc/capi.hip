@@ -1,6 +1,6 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
-// transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass), the filters
+// transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass, fft_cols), the filters
 // (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, pll, timing) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
@@ -556,6 +556,14 @@ struct sdsp_hip_timing_plan {
     double max_dev = 0.0;    // rounded to the plan precision
     void *table = nullptr;   // device: H[p][k] = h[k L + p], phases x taps reals of the precision
     void *scratch = nullptr; // a state buffer for the plain kernel of a call without state; made by set_variant(1)
+};
+
+struct sdsp_hip_fft_cols_plan {
+    uint32_t n = 0;
+    uint64_t width = 0;
+    int direction = 0, precision = 0, output = 0, shift = 0, device = 0, variant = 0;
+    void *tw = nullptr;     // device: W_n^j, j < n, direction-folded, plan precision
+    void *window = nullptr; // device: n reals of the plan precision, or null
 };
 
 struct sdsp_hip_arb_plan {
@@ -6813,5 +6821,194 @@ int sdsp_hip_timing_process_host(sdsp_hip_timing_plan *p, const void *host_x, ui
         rc = timing_run(p, st.dev[0], x_stride, st.dev[1], y_stride, st.dev[2], err_stride, st.dev[3], period_stride,
                         static_cast<uint32_t *>(st.dev[4]), samples, alpha, beta, st.dev[5], nullptr);
     return st.out(rc);
+}
+// ------------------------------------------------------------------ column FFT plans (fft_cols.hip)
+
+namespace
+{
+constexpr uint64_t kFftColsMaxElements = 1ull << 40;
+
+uint64_t fft_cols_out_esize(const sdsp_hip_fft_cols_plan *p)
+{
+    return p->output == SDSP_HIP_FFT_COLS_POWER ? real_size(p->precision) : esize(p->precision);
+}
+
+// argument checks shared by exec and exec_host (device pointers or not): in == out is in place (complex output only), any other
+// overlap is refused
+int fft_cols_check(const sdsp_hip_fft_cols_plan *p, const void *in, const void *out, uint64_t batch)
+{
+    if (!p || !in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    const uint64_t cube = static_cast<uint64_t>(p->n) * p->width; // < 2^40
+    if (batch >= kFftColsMaxElements || batch * cube >= kFftColsMaxElements)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "batch n width must be below 2^40");
+    if (batch == 0)
+        return SDSP_HIP_OK;
+    const uint64_t es = esize(p->precision), oes = fft_cols_out_esize(p);
+    if (misaligned(in, es) || misaligned(out, oes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must be aligned to their element size");
+    if (in == out) {
+        if (p->output == SDSP_HIP_FFT_COLS_POWER)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "POWER output runs out of place: in and out ranges overlap");
+    } else if (ranges_overlap(in, batch * cube * es, out, batch * cube * oes)) {
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out ranges overlap (out must equal in or lie apart from it)");
+    }
+    return SDSP_HIP_OK;
+}
+
+fft_cols_args fft_cols_args_of(const sdsp_hip_fft_cols_plan *p, const void *in, void *out, uint64_t batch)
+{
+    fft_cols_args a{};
+    a.in = in;
+    a.out = out;
+    a.tw = p->tw;
+    a.window = p->window;
+    a.width = p->width;
+    a.batch = batch;
+    a.n = p->n;
+    a.reverse = p->direction == SDSP_HIP_REVERSE;
+    a.power = p->output == SDSP_HIP_FFT_COLS_POWER;
+    a.shift = p->shift;
+    return a;
+}
+} // namespace
+
+int sdsp_hip_fft_cols_plan_create(sdsp_hip_fft_cols_plan **out, uint32_t n, uint64_t width, int direction, int precision, int output,
+                                  int shift, const double *window, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (!sdsp_hip_is_power_of_2(n) || n < SDSP_HIP_FFT_COLS_MIN_N || n > SDSP_HIP_FFT_COLS_MAX_N)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n must be a power of 2 in [SDSP_HIP_FFT_COLS_MIN_N, SDSP_HIP_FFT_COLS_MAX_N]");
+    if (width == 0 || width >= kFftColsMaxElements / n)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "width must be at least 1 with n width below 2^40");
+    if (direction != SDSP_HIP_FORWARD && direction != SDSP_HIP_REVERSE)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "direction must be SDSP_HIP_FORWARD or SDSP_HIP_REVERSE");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (output != SDSP_HIP_FFT_COLS_COMPLEX && output != SDSP_HIP_FFT_COLS_POWER)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "output must be SDSP_HIP_FFT_COLS_COMPLEX or SDSP_HIP_FFT_COLS_POWER");
+    if (direction == SDSP_HIP_REVERSE && (window || output == SDSP_HIP_FFT_COLS_POWER))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "only FORWARD plans take a window or POWER output");
+    if (window)
+        for (uint32_t i = 0; i < n; i++) {
+            const double w = precision == SDSP_HIP_F64 ? window[i] : static_cast<double>(static_cast<float>(window[i]));
+            if (!std::isfinite(w))
+                return fail(SDSP_HIP_ERR_INVALID_ARG, "window values must be finite once rounded to the precision");
+        }
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_fft_cols_plan();
+    p->n = n;
+    p->width = width;
+    p->direction = direction;
+    p->precision = precision;
+    p->output = output;
+    p->shift = shift != 0;
+    p->device = device;
+    std::vector<double> w;
+    make_twiddles(n, direction, w);
+    int rc = upload_twiddles(w, precision, &p->tw);
+    if (!rc && window) {
+        const hipError_t e = upload_reals(window, n, precision, &p->window);
+        if (e != hipSuccess)
+            rc = plan_fail(e, "fft_cols");
+    }
+    if (!rc) // the kernel's dynamic-LDS limit, so that exec sets no attribute (it may be captured)
+        rc = launch_fft_cols(precision, fft_cols_args_of(p, nullptr, nullptr, 0), 0, nullptr);
+    if (rc) {
+        sdsp_hip_fft_cols_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fft_cols_plan_destroy(sdsp_hip_fft_cols_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->tw);
+        (void)hipFree(p->window);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fft_cols_exec(sdsp_hip_fft_cols_plan *p, const void *in, void *out, uint64_t batch, void *stream)
+{
+    if (int rc = fft_cols_check(p, in, out, batch))
+        return rc;
+    if (batch == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    return launch_fft_cols(p->precision, fft_cols_args_of(p, in, out, batch), p->variant, stream);
+}
+
+int sdsp_hip_fft_cols_exec_host(sdsp_hip_fft_cols_plan *p, const void *host_in, void *host_out, uint64_t batch)
+{
+    if (int rc = fft_cols_check(p, host_in, host_out, batch))
+        return rc;
+    if (batch == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const uint64_t elements = batch * p->n * p->width;
+    const size_t in_bytes = static_cast<size_t>(elements * esize(p->precision));
+    const size_t out_bytes = static_cast<size_t>(elements * fft_cols_out_esize(p));
+    const bool in_place = host_in == host_out;
+    // in place: one device buffer, read back; else the input and an output buffer
+    host_stage st("fft_cols", { { host_in, in_bytes, in_place }, { in_place ? nullptr : host_out, out_bytes, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = launch_fft_cols(p->precision, fft_cols_args_of(p, st.dev[0], in_place ? st.dev[0] : st.dev[1], batch), p->variant, nullptr);
+    if (!rc) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = hip_fail(e, "fft_cols exec_host");
+    }
+    return st.out(rc);
+}
+
+int sdsp_hip_fft_cols_plan_set_variant(sdsp_hip_fft_cols_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fft_cols_plan_launches(const sdsp_hip_fft_cols_plan *p, uint64_t batch, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = fft_cols_launches(p->precision, p->n, p->width, batch, p->variant);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fft_cols_plan_get_info(const sdsp_hip_fft_cols_plan *p, sdsp_hip_fft_cols_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const fft_cols_shape s = fft_cols_shape_for(p->precision, p->n, p->variant);
+    info->n = p->n;
+    info->width = p->width;
+    info->direction = p->direction;
+    info->precision = p->precision;
+    info->output = p->output;
+    info->shift = p->shift;
+    info->windowed = p->window != nullptr;
+    info->device = p->device;
+    info->variant = p->variant;
+    info->tile_columns = s.tile_columns;
+    info->threads = s.threads;
+    info->lds_bytes = s.lds_bytes;
+    info->algorithmic_bytes = static_cast<uint64_t>(p->n) * p->width * (esize(p->precision) + fft_cols_out_esize(p));
+    std::strncpy(info->kernel, fft_cols_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
 }
 }

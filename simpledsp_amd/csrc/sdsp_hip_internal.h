@@ -494,6 +494,25 @@ const char *timing_kernel_for(int variant);
 uint32_t timing_block(int precision);
 uint32_t timing_waves(int precision, uint32_t phases, uint32_t taps);
 uint32_t timing_lds_bytes(int precision, uint32_t phases, uint32_t taps);
+// Column FFT plans (fft_cols.hip): the launches of one call over compact cubes [batch][n][width]
+struct fft_cols_args {
+    const void *in;     // null: launch nothing, only prepare the kernel (its dynamic-LDS limit) on the current device
+    void *out;          // complex elements, or reals for `power`; may equal `in` for complex output
+    const void *tw;     // W_n^j, j < n, direction-folded, plan precision
+    const void *window; // nullable; n reals of the plan precision (forward only)
+    uint64_t width, batch;
+    uint32_t n;
+    int reverse, power, shift;
+};
+int launch_fft_cols(int precision, const fft_cols_args &a, int variant, void *stream);
+struct fft_cols_shape {
+    uint32_t tile_columns; // columns of one tile
+    uint32_t columns;      // columns of one workgroup (tiles side by side)
+    uint32_t threads, lds_bytes;
+};
+fft_cols_shape fft_cols_shape_for(int precision, uint32_t n, int variant);
+uint64_t fft_cols_launches(int precision, uint32_t n, uint64_t width, uint64_t batch, int variant);
+const char *fft_cols_kernel_for(int variant);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
