@@ -1320,10 +1320,19 @@ static int fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int d
     int rc = SDSP_HIP_OK;
     std::vector<double> w;
     const uint32_t lds_cap_n = (uint32_t)(fft_tile_max_lds_bytes() / esize(precision));
+    // double-precision plans build every table but the reported row from the correctly rounded row (host_math.cpp): the reference's
+    // recipe leaves entries up to 1.85 units of 2^-53 off, which the thread-twiddle kernels multiply in once or twice per stage
+    auto table_row = [&](uint32_t len) {
+        if (precision == SDSP_HIP_F64)
+            make_twiddles_rounded(len, direction, w);
+        else
+            make_twiddles(len, direction, w);
+    };
     if (n > 1) {
         make_twiddles(n, direction, w);
         rc = upload_twiddles(w, precision, &p->tw);
         p->twiddle_bytes = (uint64_t)n * esize(precision);
+        table_row(n);
     }
     // the optional thread-twiddle tables: where some variant of this plan's exec or convolve runs a kernel that reads them
     if (!rc && uses_twt4096(p))
@@ -1340,7 +1349,7 @@ static int fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int d
         p->path = PATH_NOOP;
     } else if (real_mode) { // every size on the split / merge kernels (n = 4096 f32 too: the tuned complex kernels have no split stage)
         p->path = PATH_REG;
-        make_twiddles(2 * n, direction, w);
+        table_row(2 * n);
         if (!rc)
             rc = upload_twiddles(w, precision, &p->tw2); // W_2n
         p->twiddle_bytes += 2ull * n * esize(precision);
@@ -1370,11 +1379,11 @@ static int fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int d
         }
         p->n2 = n / p->n1;
         if (!rc) {
-            make_twiddles(p->n1, direction, w);
+            table_row(p->n1);
             rc = upload_twiddles(w, precision, &p->tw1);
         }
         if (!rc) {
-            make_twiddles(p->n2, direction, w);
+            table_row(p->n2);
             rc = upload_twiddles(w, precision, &p->tw2);
         }
         p->twiddle_bytes += ((uint64_t)p->n1 + p->n2) * esize(precision);
@@ -1408,7 +1417,7 @@ static int fft_plan_create(sdsp_hip_fft_plan **out, uint32_t n, int radix, int d
         const int sub_radix = (radix == 4 && sdsp_hip_is_power_of_4(n2)) ? 4 : 2;
         rc = sdsp_hip_fft_plan_create(&p->mid_rows, n2, sub_radix, direction, precision, p->ws_batch * 16, device);
         if (!rc) {
-            make_twiddles(1024, direction, w);
+            table_row(1024);
             rc = upload_twiddles(w, precision, &p->tw1024);
         }
     }

@@ -65,6 +65,43 @@ void make_twiddles(uint32_t n, int direction, std::vector<double> &out)
     }
 }
 
+// The same row correctly rounded: make_twiddles forms the angle 2 pi j / n in double as the reference does, which leaves entries up
+// to 1.85 units of 2^-53 from W_n^j (the angle's own rounding, worst near pi / 2).  Here the angle is reduced to the first octant in
+// integers, formed and evaluated in long double and rounded once; the other octants are exact mirror images.  The double-precision
+// kernels' own tables (thread twiddles, W_2N, the sub-transforms' rows) are built from this row; the row a plan reports
+// (sdsp_hip_fft_plan_get_twiddles) stays the reference's.
+void make_twiddles_rounded(uint32_t n, int direction, std::vector<double> &out)
+{
+    if (n < 4) {
+        make_twiddles(n, direction, out);
+        return;
+    }
+    out.assign(2 * (size_t)n, 0.0);
+    const double sgn = direction == SDSP_HIP_REVERSE ? -1.0 : 1.0;
+    const long double step = 3.14159265358979323846264338327950288L / (2.0L * (long double)n); // pi / 2 in units of 1 / n
+    for (uint32_t m = 0; m < n; m++) {
+        const uint64_t four = 4ull * m;
+        const uint32_t quad = (uint32_t)(four / n);
+        uint64_t rem = four % n; // angle = (quad + rem / n) pi / 2
+        const bool swap = 2 * rem > n;
+        if (swap)
+            rem = n - rem;
+        const long double th = (long double)rem * step;
+        double c = (double)cosl(th), s = (double)sinl(th);
+        if (swap)
+            std::swap(c, s);
+        double re, im; // exp(-i (quad pi / 2 + th)) = (-i)^quad (c - i s)
+        switch (quad) {
+        case 0: re = c; im = -s; break;
+        case 1: re = -s; im = -c; break;
+        case 2: re = -c; im = s; break;
+        default: re = s; im = c; break;
+        }
+        out[2 * (size_t)m] = re + 0.0; // no negative zeros
+        out[2 * (size_t)m + 1] = sgn * im + 0.0;
+    }
+}
+
 // set_lp_coeff / set_hp_coeff: casc_2o_iir.h:168-194 and :140-166.  Expression order kept so
 // the coefficients equal the reference's doubles.
 static int design_lp_hp(uint32_t m, double f0, double fs, double gain_in, bool high, double *a,

@@ -20,6 +20,7 @@ int ensure_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uint64_t> &
 
 // host_math.cpp
 void make_twiddles(uint32_t n, int direction, std::vector<double> &out);
+void make_twiddles_rounded(uint32_t n, int direction, std::vector<double> &out); // the same row, every entry correctly rounded
 int design_lp(uint32_t m, double f0, double fs, double gain_in, double *a, double *b, double *gain);
 int design_hp(uint32_t m, double f0, double fs, double gain_in, double *a, double *b, double *gain);
 int design_bp(uint32_t m, double f0, double fs, double q, double gain_in, double *a, double *b, double *gain);

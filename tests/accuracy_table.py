@@ -14,6 +14,67 @@ o = Oracle()
 rng = np.random.default_rng(2024)
 
 
+# ---- the transform family in units of u against the extended-precision reference (tests/fft_exact.py): per case
+# of tests/test_gpu_fft_accuracy.py's table and per row kind the worst e2 / einf next to the plain baseline's and the bound
+import fft_exact as fx
+import test_gpu_fft_accuracy as acc
+
+
+def units_of_u_section():
+    print("\n## Transform kernels in units of u (2^-24 f32, 2^-53 f64) against the longdouble DFT\n")
+    print("Per row kind: worst e2 / einf (plain baseline's e2 / einf; bound e2 / einf); `ratio` = the case's worst error over max(baseline, 1 u), bound 3.\n")
+    print("| form | case | kernel | direction | " + " | ".join(("gauss", "impulse", "tone", "exact rows", "matrix")) + " | ratio |\n|---|---|---|---|---|---|---|---|---|---|")
+
+    def _cells(report):
+        w = fx.worst_by_kind(report)
+        for k in ("ones", "alt"):  # the R3 rows in one column
+            if k in w:
+                e = w.setdefault("exact", dict(e2=0.0, einf=0.0, base2=0.0, baseinf=0.0, bound2=0.0, boundinf=0.0, ratio=0.0))
+                for f in e:
+                    e[f] = max(e[f], w[k][f])
+        cells = []
+        for k in ("gauss", "impulse", "tone", "exact", "matrix"):
+            v = w.get(k)
+            cells.append("-" if v is None else f"{v['einf']:.2f} ({v['baseinf']:.2f}; {v['boundinf']:.2f})" if k == "matrix" else
+                         f"{v['e2']:.2f} / {v['einf']:.2f} ({v['base2']:.2f} / {v['baseinf']:.2f}; {v['bound2']:.2f} / {v['boundinf']:.2f})")
+        return cells, max(v["ratio"] for v in w.values())
+
+    def _row(form, case, kernel, direction, report, fails):
+        cells, ratio = _cells(report)
+        print(f"| {form} | {case} | `{kernel}` | {direction} | " + " | ".join(cells) + f" | {ratio:.2f}{' **over**' if fails else ''} |")
+
+    for case in acc.COMPLEX_CASES:
+        for reverse in (False, True):
+            fails, report = acc.run_complex(sd, torch, case, reverse)
+            _row("complex", f"N = {case[0]}, radix {case[1]}, {case[2]}, variant {case[3]}", case[5], "rev" if reverse else "fwd", report, fails)
+    for case in acc.REAL_CASES:
+        for reverse in (False, True):
+            fails, report = acc.run_real(sd, torch, case, reverse)
+            _row("real", f"n_real = {case[0]}, radix {case[1]}, {case[2]}, variant {case[3]}", case[4], "rev" if reverse else "fwd", report, fails)
+    for case in acc.CONV_CASES:
+        fails, report = acc.run_conv(sd, torch, case)
+        by_h = {}
+        for r in report:
+            by_h.setdefault(r["kind"], []).append(r)
+        for h, rows in by_h.items():
+            w = fx.worst_by_kind(rows)[h]
+            print(f"| conv | N = {case[0]}, radix {case[1]}, {case[2]}, variant {case[3]}, {h} | `{case[5]}` | - | all rows: {w['e2']:.2f} / {w['einf']:.2f} "
+                  f"({w['base2']:.2f} / {w['baseinf']:.2f}; {w['bound2']:.2f} / {w['boundinf']:.2f}) | - | - | - | - | "
+                  f"{w['ratio']:.2f}{' **over**' if any(f[1].startswith(h) for f in fails) else ''} |")
+    for n in acc.COLS_NS:
+        for prec in ("f32", "f64"):
+            for variant in (0, 1):
+                for reverse in (False, True):
+                    fails, report = acc.run_cols(sd, torch, n, prec, variant, reverse)
+                    _row("cols", f"n = {n}, width {acc.COLS_WIDTH}, {prec}, variant {variant}", "sdsp_fft_cols_plain_kernel" if variant else "sdsp_fft_cols_kernel",
+                         "rev" if reverse else "fwd", report, fails)
+
+
+if "--units-of-u" in sys.argv:  # that section alone (profiles/fft_accuracy_u.md)
+    units_of_u_section()
+    sys.exit(0)
+
+
 def rel(got, ref):
     got = np.asarray(got, dtype=np.complex128 if np.iscomplexobj(ref) else np.float64)
     return float((np.abs(got - ref).max(axis=-1) / np.abs(ref).max(axis=-1)).max())
@@ -109,3 +170,5 @@ for n, radix in ((4096, 4), (1024, 2)):
     torch.cuda.synchronize()
     ref = o.fft(o.fft(xb.astype(np.complex128), radix) * hh.astype(np.complex128), radix, True)
     print(f"| fused convolution | N = {n}, radix {radix} | {rel(d.cpu().numpy(), ref):.2e} | 2e-6 (two transforms) |")
+
+units_of_u_section()
