@@ -36,13 +36,6 @@ public:
           m_step(max_step < (1ull << 32) ? max_step : (1ull << 32))
     {
     }
-    ~arb_resampler_bank()
-    {
-        if (m_plan)
-            sdsp_hip_arb_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     arb_resampler_bank(const arb_resampler_bank &) = delete;
     arb_resampler_bank &operator=(const arb_resampler_bank &) = delete;
 
@@ -52,13 +45,13 @@ public:
         if (h.size() != m_coeff.size())
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: coefficient count differs from phases * taps_per_phase");
         m_coeff = h;
-        drop_plan();
+        m_plan.reset();
     }
     // Hamming low-pass for ratios up to max_in_per_out, gain phases (sdsp_hip_arb_design)
     void set_default_coeff(double max_in_per_out)
     {
         detail::check(sdsp_hip_arb_design(m_phases, m_taps, max_in_per_out, m_coeff.data()));
-        drop_plan();
+        m_plan.reset();
     }
     // forget the history and the stream time
     void reset()
@@ -85,8 +78,8 @@ public:
         ensure_state();
         std::uint64_t n = 0, next = 0;
         detail::check(sdsp_hip_arb_out_samples(m_step, m_time, samples, &n, &next));
-        detail::check(sdsp_hip_arb_process(m_plan, device_in, in_stride, device_out, out_stride, m_channels, samples, m_step, m_time, m_state,
-                                           stream));
+        detail::check(sdsp_hip_arb_process(m_plan.get(), device_in, in_stride, device_out, out_stride, m_channels, samples, m_step, m_time,
+                                           m_state.get(), stream));
         m_time = next;
         return n;
     }
@@ -101,21 +94,13 @@ public:
             return 0;
         const std::size_t in_bytes = static_cast<std::size_t>(m_channels * samples) * elem_bytes();
         const std::size_t out_bytes = static_cast<std::size_t>(m_channels * n) * elem_bytes();
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = out_bytes ? sdsp_hip_malloc(&dout, out_bytes, m_device) : 0;
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_arb_process(m_plan, di, samples, dout, n, m_channels, samples, m_step, m_time, m_state, nullptr);
-        if (!rc && out_bytes)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        if (!rc && !out_bytes)
-            rc = sdsp_hip_device_synchronize(m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        // a call that yields no output has no output buffer and waits for the device instead of copying back
+        const detail::stage_item items[] = { { host_in, nullptr, in_bytes }, { nullptr, out_bytes ? host_out : nullptr, out_bytes } };
+        detail::host_stage(m_device, items, [&](void *const *dev) {
+            const int rc = sdsp_hip_arb_process(m_plan.get(), dev[0], samples, dev[1], n, m_channels, samples, m_step, m_time,
+                                                m_state.get(), nullptr);
+            return rc || out_bytes ? rc : sdsp_hip_device_synchronize(m_device);
+        });
         m_time = next;
         return n;
     }
@@ -135,35 +120,30 @@ public:
     {
         ensure_plan();
         sdsp_hip_arb_plan_info i{};
-        detail::check(sdsp_hip_arb_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_arb_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
     std::size_t elem_bytes() const noexcept { return (m_complex ? 2u : 1u) * sizeof(real_t); }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_arb_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_arb_plan_create(&m_plan, m_phases, m_taps, m_coeff.data(), m_max_step,
-                                                   m_complex ? SDSP_HIP_ARB_COMPLEX : SDSP_HIP_ARB_REAL,
-                                                   m_linear ? SDSP_HIP_ARB_LINEAR : SDSP_HIP_ARB_NEAREST,
-                                                   detail::precision_of<real_t>::value, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_arb_plan *plan = nullptr;
+        detail::check(sdsp_hip_arb_plan_create(&plan, m_phases, m_taps, m_coeff.data(), m_max_step,
+                                               m_complex ? SDSP_HIP_ARB_COMPLEX : SDSP_HIP_ARB_REAL,
+                                               m_linear ? SDSP_HIP_ARB_LINEAR : SDSP_HIP_ARB_NEAREST, detail::precision_of<real_t>::value,
+                                               m_device));
+        m_plan.reset(plan);
     }
     void zero_state()
     {
         const std::size_t len = m_taps > 1 ? m_taps - 1 : 1;
         const std::size_t bytes = len * static_cast<std::size_t>(m_channels) * elem_bytes();
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-        const std::vector<unsigned char> host(bytes, 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), bytes, m_device));
+            m_state.alloc(bytes, m_device);
+        m_state.fill<unsigned char>(bytes, 0);
     }
     void ensure_state()
     {
@@ -178,8 +158,8 @@ private:
     std::vector<double> m_coeff;
     std::uint64_t m_step;
     std::uint64_t m_time{ 0 };
-    sdsp_hip_arb_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_arb_plan, sdsp_hip_arb_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

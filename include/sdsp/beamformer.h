@@ -35,11 +35,6 @@ public:
         : m_sensors(sensors), m_beams(beams), m_taps(n_taps), m_groups(groups), m_complex(complex_rows), m_device(device)
     {
     }
-    ~beamformer_bank()
-    {
-        drop_plan();
-        drop_state();
-    }
     beamformer_bank(const beamformer_bank &) = delete;
     beamformer_bank &operator=(const beamformer_bank &) = delete;
 
@@ -51,8 +46,8 @@ public:
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: tap count differs from entries x n_taps");
         m_entries = std::move(entries);
         m_coeff = std::move(taps);
-        drop_plan();
-        drop_state();
+        m_plan.reset();
+        m_state.reset();
     }
     // every beam uses every sensor with a designed fractional delay: tau and weights are beams x sensors, row-major (real rows, or
     // complex rows with real weights)
@@ -86,7 +81,7 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_beam_process(m_plan, device_in, in_stride, device_out, out_stride, samples, m_state, stream));
+        detail::check(sdsp_hip_beam_process(m_plan.get(), device_in, in_stride, device_out, out_stride, samples, m_state.get(), stream));
     }
     // host pointers: in = groups x sensors x samples elements, out = groups x beams x samples elements, both contiguous
     void process_host(const real_t *host_in, real_t *host_out, std::uint64_t samples)
@@ -97,19 +92,9 @@ public:
             return;
         const std::size_t in_bytes = static_cast<std::size_t>(m_groups) * m_sensors * samples * elem_bytes();
         const std::size_t out_bytes = static_cast<std::size_t>(m_groups) * m_beams * samples * elem_bytes();
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_beam_process(m_plan, di, samples, dout, samples, samples, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes }, { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_beam_process(m_plan.get(), dev[0], samples, dev[1], samples, samples, m_state.get(), nullptr);
+        });
     }
     std::uint32_t sensors() const noexcept { return m_sensors; }
     std::uint32_t beams() const noexcept { return m_beams; }
@@ -127,48 +112,35 @@ public:
     void set_variant(int variant)
     {
         ensure_plan();
-        detail::check(sdsp_hip_beam_plan_set_variant(m_plan, variant));
+        detail::check(sdsp_hip_beam_plan_set_variant(m_plan.get(), variant));
     }
     sdsp_hip_beam_plan_info info()
     {
         ensure_plan();
         sdsp_hip_beam_plan_info i{};
-        detail::check(sdsp_hip_beam_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_beam_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
     std::size_t elem_bytes() const noexcept { return (m_complex ? 2u : 1u) * sizeof(real_t); }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_beam_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
-    void drop_state()
-    {
-        if (m_state) {
-            sdsp_hip_free(m_state, m_device);
-            m_state = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_beam_plan_create(&m_plan, m_sensors, m_beams, m_groups, m_taps,
-                                                    static_cast<std::uint32_t>(m_entries.size()), m_entries.data(), m_coeff.data(),
-                                                    m_complex ? SDSP_HIP_BEAM_COMPLEX : SDSP_HIP_BEAM_REAL,
-                                                    detail::precision_of<real_t>::value, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_beam_plan *plan = nullptr;
+        detail::check(sdsp_hip_beam_plan_create(&plan, m_sensors, m_beams, m_groups, m_taps, static_cast<std::uint32_t>(m_entries.size()),
+                                                m_entries.data(), m_coeff.data(), m_complex ? SDSP_HIP_BEAM_COMPLEX : SDSP_HIP_BEAM_REAL,
+                                                detail::precision_of<real_t>::value, m_device));
+        m_plan.reset(plan);
     }
     void zero_state()
     {
         const std::size_t len = std::max<std::size_t>(hist(), 1);
         const std::size_t bytes = len * m_groups * m_sensors * elem_bytes();
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-        const std::vector<unsigned char> host(bytes, 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), bytes, m_device));
+            m_state.alloc(bytes, m_device);
+        m_state.fill<unsigned char>(bytes, 0);
     }
     void ensure_state()
     {
@@ -181,8 +153,8 @@ private:
     int m_device;
     std::vector<sdsp_hip_beam_entry> m_entries;
     std::vector<double> m_coeff;
-    sdsp_hip_beam_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_beam_plan, sdsp_hip_beam_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

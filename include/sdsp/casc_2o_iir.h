@@ -48,33 +48,17 @@ public:
         drop_plan(); // the design may differ after an assignment
         return *this;
     }
-    ~stream_ctx()
-    {
-        drop_plan();
-        if (m_dev)
-            sdsp_hip_free(m_dev, 0);
-    }
-    void drop_plan() noexcept
-    {
-        if (m_plan)
-            sdsp_hip_iir_plan_destroy(m_plan);
-        m_plan = nullptr;
-    }
-    sdsp_hip_iir_plan *&plan() noexcept { return m_plan; }
+    void drop_plan() noexcept { m_plan.reset(); }
+    plan_ptr<sdsp_hip_iir_plan, sdsp_hip_iir_plan_destroy> &plan() noexcept { return m_plan; }
     // device buffer of at least `doubles` doubles (grow-only)
-    double *device(std::size_t doubles)
+    device_buffer &device(std::size_t doubles)
     {
         if (doubles > m_cap) {
-            if (m_dev)
-                sdsp_hip_free(m_dev, 0);
-            m_dev = nullptr;
             m_cap = 0;
             std::size_t want = 256;
             while (want < doubles)
                 want *= 2;
-            void *d = nullptr;
-            check(sdsp_hip_malloc(&d, want * sizeof(double), 0));
-            m_dev = static_cast<double *>(d);
+            m_dev.alloc(want * sizeof(double), 0);
             m_cap = want;
         }
         return m_dev;
@@ -82,8 +66,8 @@ public:
     std::vector<double> &host() noexcept { return m_host; }
 
 private:
-    sdsp_hip_iir_plan *m_plan{ nullptr };
-    double *m_dev{ nullptr };
+    plan_ptr<sdsp_hip_iir_plan, sdsp_hip_iir_plan_destroy> m_plan;
+    device_buffer m_dev;
     std::size_t m_cap{ 0 };
     std::vector<double> m_host; // [state | samples] staging image
 };
@@ -119,13 +103,15 @@ void process_single(stream_ctx &ctx, int kind, double gain, const coeff3_array<m
                 af[3 * j + i] = a[j][i];
                 bf[3 * j + i] = b ? (*b)[j][i] : 0.0;
             }
-        check(sdsp_hip_iir_plan_create(&ctx.plan(), static_cast<std::uint32_t>(m_t), kind, af.data(), b ? bf.data() : nullptr,
-                                       gain, SDSP_HIP_F64, 0));
+        sdsp_hip_iir_plan *plan = nullptr;
+        check(sdsp_hip_iir_plan_create(&plan, static_cast<std::uint32_t>(m_t), kind, af.data(), b ? bf.data() : nullptr, gain,
+                                       SDSP_HIP_F64, 0));
+        ctx.plan().reset(plan);
     }
-    double *dev = ctx.device(img.size());
-    check(sdsp_hip_memcpy_h2d(dev, img.data(), img.size() * sizeof(double), 0));
-    check(sdsp_hip_iir_process(ctx.plan(), dev + kState, 1, n, n, dev, nullptr));
-    check(sdsp_hip_memcpy_d2h(img.data(), dev, img.size() * sizeof(double), 0)); // synchronises with the launch
+    device_buffer &dev = ctx.device(img.size());
+    dev.upload(img.data(), img.size() * sizeof(double));
+    check(sdsp_hip_iir_process(ctx.plan().get(), static_cast<double *>(dev.get()) + kState, 1, n, n, dev.get(), nullptr));
+    dev.download(img.data(), img.size() * sizeof(double)); // synchronises with the launch
 
     std::size_t k = kState;
     for (iter_t it = begin; it != end; ++it)
@@ -343,13 +329,6 @@ public:
     {
         static_assert(m_t % 2 == 0, "M must be even!");
     }
-    ~casc_2o_iir_bank()
-    {
-        if (m_plan)
-            sdsp_hip_iir_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     casc_2o_iir_bank(const casc_2o_iir_bank &) = delete;
     casc_2o_iir_bank &operator=(const casc_2o_iir_bank &) = delete;
 
@@ -392,15 +371,13 @@ public:
             for (std::uint64_t c = 0; c < m_channels; ++c)
                 host[r * m_channels + c] = static_cast<real_t>(mem[r]);
         ensure_state();
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size() * sizeof(real_t), m_device));
+        m_state.upload(host.data(), host.size() * sizeof(real_t));
     }
     // forget the history (zero state)
     void reset()
     {
-        if (m_state) {
-            std::vector<real_t> zeros(3 * (m_t + 1) * m_channels, real_t(0));
-            detail::check(sdsp_hip_memcpy_h2d(m_state, zeros.data(), zeros.size() * sizeof(real_t), m_device));
-        }
+        if (m_state)
+            m_state.fill(3 * (m_t + 1) * m_channels, real_t(0));
     }
 
     // device pointer, asynchronous on `stream`; continues every channel's stream
@@ -408,7 +385,7 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_iir_process(m_plan, device_data, m_channels, samples, stride, m_state, stream));
+        detail::check(sdsp_hip_iir_process(m_plan.get(), device_data, m_channels, samples, stride, m_state.get(), stream));
     }
     // the sample-major "wire" layout: sample s of channel c at device_data[s*stride + c];
     // no transpose, bit-identical to process() on the transposed data
@@ -416,7 +393,7 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_iir_process_interleaved(m_plan, device_data, m_channels, samples, stride, m_state, stream));
+        detail::check(sdsp_hip_iir_process_interleaved(m_plan.get(), device_data, m_channels, samples, stride, m_state.get(), stream));
     }
     // host pointer convenience: channels x samples, contiguous
     void process_host(real_t *host_data, std::uint64_t samples)
@@ -424,15 +401,9 @@ public:
         ensure_plan();
         ensure_state();
         const size_t bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
-        void *d = nullptr;
-        detail::check(sdsp_hip_malloc(&d, bytes, m_device));
-        int rc = sdsp_hip_memcpy_h2d(d, host_data, bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_iir_process(m_plan, d, m_channels, samples, samples, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_data, d, bytes, m_device);
-        sdsp_hip_free(d, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_data, host_data, bytes } }, [&](void *const *dev) {
+            return sdsp_hip_iir_process(m_plan.get(), dev[0], m_channels, samples, samples, m_state.get(), nullptr);
+        });
     }
     std::uint64_t channels() const noexcept { return m_channels; }
 
@@ -441,24 +412,22 @@ private:
     void redesign(filter_type t)
     {
         m_f_type = t;
-        if (m_plan) {
-            sdsp_hip_iir_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
+        m_plan.reset();
     }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_iir_plan_create(&m_plan, m_t, m_kind, m_a.data(), m_b.data(), m_gain,
-                                                   detail::precision_of<real_t>::value, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_iir_plan *plan = nullptr;
+        detail::check(sdsp_hip_iir_plan_create(&plan, m_t, m_kind, m_a.data(), m_b.data(), m_gain, detail::precision_of<real_t>::value,
+                                               m_device));
+        m_plan.reset(plan);
     }
     void ensure_state()
     {
         if (!m_state) {
-            const size_t bytes = 3 * (m_t + 1) * m_channels * sizeof(real_t);
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-            std::vector<real_t> zeros(3 * (m_t + 1) * m_channels, real_t(0));
-            detail::check(sdsp_hip_memcpy_h2d(m_state, zeros.data(), bytes, m_device));
+            m_state.alloc(3 * (m_t + 1) * m_channels * sizeof(real_t), m_device);
+            m_state.fill(3 * (m_t + 1) * m_channels, real_t(0));
         }
     }
 
@@ -468,7 +437,7 @@ private:
     std::array<double, 3 * m_t> m_a{}, m_b{};
     double m_gain{ 1.0 };
     filter_type m_f_type{ filter_type::none };
-    sdsp_hip_iir_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_iir_plan, sdsp_hip_iir_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp

@@ -35,16 +35,11 @@ public:
         d.rank = rank;
         d.input = static_cast<int>(input);
         d.alpha = alpha;
-        detail::check(sdsp_hip_cfar_plan_create(&m_plan, channels, &d, detail::precision_of<real_t>::value, device));
+        sdsp_hip_cfar_plan *plan = nullptr;
+        detail::check(sdsp_hip_cfar_plan_create(&plan, channels, &d, detail::precision_of<real_t>::value, device));
+        m_plan.reset(plan);
     }
     static std::uint32_t default_rank(std::uint32_t train) noexcept { return (3u * 2u * train) / 4u; }
-    ~cfar_bank()
-    {
-        if (m_plan)
-            sdsp_hip_cfar_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     cfar_bank(const cfar_bank &) = delete;
     cfar_bank &operator=(const cfar_bank &) = delete;
 
@@ -61,8 +56,8 @@ public:
                  std::uint64_t det_stride, std::uint64_t samples, void *stream = nullptr)
     {
         ensure_state();
-        detail::check(sdsp_hip_cfar_process(m_plan, device_x, x_stride, device_thr, thr_stride, device_det, det_stride, samples, m_state,
-                                            stream));
+        detail::check(sdsp_hip_cfar_process(m_plan.get(), device_x, x_stride, device_thr, thr_stride, device_det, det_stride, samples,
+                                            m_state.get(), stream));
     }
     // host pointers: contiguous channels x samples elements each (x: one real per element for power, an interleaved pair for I/Q);
     // thr or det may be null, not both
@@ -72,25 +67,13 @@ public:
         if (samples == 0)
             return;
         const std::size_t n = static_cast<std::size_t>(m_channels * samples);
-        const std::size_t bytes[3] = { n * sizeof(real_t) * reals_per_element(), host_thr ? n * sizeof(real_t) : 0, host_det ? n : 0 };
-        void *dev[3] = { nullptr, nullptr, nullptr };
-        int rc = 0;
-        for (int i = 0; i < 3 && !rc; i++)
-            if (bytes[i])
-                rc = sdsp_hip_malloc(&dev[i], bytes[i], m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(dev[0], host_x, bytes[0], m_device);
-        if (!rc)
-            rc = sdsp_hip_cfar_process(m_plan, dev[0], samples, dev[1], samples, static_cast<std::uint8_t *>(dev[2]), samples, samples,
-                                       m_state, nullptr);
-        if (!rc && host_thr)
-            rc = sdsp_hip_memcpy_d2h(host_thr, dev[1], bytes[1], m_device);
-        if (!rc && host_det)
-            rc = sdsp_hip_memcpy_d2h(host_det, dev[2], bytes[2], m_device);
-        for (void *p : dev)
-            if (p)
-                sdsp_hip_free(p, m_device);
-        detail::check(rc);
+        const detail::stage_item items[] = { { host_x, nullptr, n * sizeof(real_t) * reals_per_element() },
+                                             { nullptr, host_thr, n * sizeof(real_t) },
+                                             { nullptr, host_det, n } };
+        detail::host_stage(m_device, items, [&](void *const *dev) {
+            return sdsp_hip_cfar_process(m_plan.get(), dev[0], samples, dev[1], samples, static_cast<std::uint8_t *>(dev[2]), samples,
+                                         samples, m_state.get(), nullptr);
+        });
     }
     // the x history, [channel][window - 1] elements (I/Q: interleaved pairs), newest first, copied from the device state
     std::vector<real_t> history()
@@ -98,7 +81,7 @@ public:
         ensure_state();
         std::vector<real_t> h(history_reals());
         if (!h.empty())
-            detail::check(sdsp_hip_memcpy_d2h(h.data(), m_state, h.size() * sizeof(real_t), m_device));
+            m_state.download(h.data(), h.size() * sizeof(real_t));
         return h;
     }
     // ... copied into it
@@ -108,20 +91,20 @@ public:
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: history must be channels x (window - 1) elements");
         ensure_state();
         if (!h.empty())
-            detail::check(sdsp_hip_memcpy_h2d(m_state, h.data(), h.size() * sizeof(real_t), m_device));
+            m_state.upload(h.data(), h.size() * sizeof(real_t));
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     std::uint32_t train() const noexcept { return m_train; }
     std::uint32_t guard() const noexcept { return m_guard; }
     std::uint32_t delay() const noexcept { return m_train + m_guard; }
     std::uint32_t window() const noexcept { return 2u * (m_train + m_guard) + 1u; }
-    void set_alpha(double alpha) { detail::check(sdsp_hip_cfar_plan_set_alpha(m_plan, alpha)); }
-    void set_variant(int variant) { detail::check(sdsp_hip_cfar_plan_set_variant(m_plan, variant)); }
-    void set_run(std::uint64_t run) { detail::check(sdsp_hip_cfar_plan_set_run(m_plan, run)); }
+    void set_alpha(double alpha) { detail::check(sdsp_hip_cfar_plan_set_alpha(m_plan.get(), alpha)); }
+    void set_variant(int variant) { detail::check(sdsp_hip_cfar_plan_set_variant(m_plan.get(), variant)); }
+    void set_run(std::uint64_t run) { detail::check(sdsp_hip_cfar_plan_set_run(m_plan.get(), run)); }
     sdsp_hip_cfar_plan_info info() const
     {
         sdsp_hip_cfar_plan_info i{};
-        detail::check(sdsp_hip_cfar_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_cfar_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -132,9 +115,8 @@ private:
     {
         const std::size_t bytes = history_reals() * sizeof(real_t);
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-        const std::vector<unsigned char> host(bytes, 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size(), m_device));
+            m_state.alloc(bytes, m_device);
+        m_state.fill<unsigned char>(bytes, 0);
     }
     void ensure_state()
     {
@@ -146,8 +128,8 @@ private:
     std::uint32_t m_train, m_guard;
     bool m_iq;
     int m_device;
-    sdsp_hip_cfar_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_cfar_plan, sdsp_hip_cfar_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

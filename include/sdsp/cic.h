@@ -56,13 +56,6 @@ public:
         m_scale = is_float ? (scale != 0.0 ? scale : cic_unity_scale(order, down, delay)) : 1.0;
         m_hist = order * delay * down;
     }
-    ~cic_decimator_bank()
-    {
-        if (m_plan)
-            sdsp_hip_cic_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     cic_decimator_bank(const cic_decimator_bank &) = delete;
     cic_decimator_bank &operator=(const cic_decimator_bank &) = delete;
 
@@ -90,8 +83,8 @@ public:
         ensure_plan();
         ensure_state();
         const std::uint64_t n = out_samples(samples);
-        detail::check(sdsp_hip_cic_process(m_plan, device_in, in_stride, device_out, out_stride, m_channels, samples, m_position, m_state,
-                                           stream));
+        detail::check(sdsp_hip_cic_process(m_plan.get(), device_in, in_stride, device_out, out_stride, m_channels, samples, m_position,
+                                           m_state.get(), stream));
         m_position += samples;
         return n;
     }
@@ -106,21 +99,13 @@ public:
         const std::size_t width = m_complex ? 2u : 1u;
         const std::size_t in_bytes = static_cast<std::size_t>(m_channels * samples) * width * sizeof(in_t);
         const std::size_t out_bytes = static_cast<std::size_t>(m_channels * n) * width * sizeof(out_t);
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = out_bytes ? sdsp_hip_malloc(&dout, out_bytes, m_device) : 0;
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_cic_process(m_plan, di, samples, dout, n, m_channels, samples, m_position, m_state, nullptr);
-        if (!rc && out_bytes)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        if (!rc && !out_bytes)
-            rc = sdsp_hip_device_synchronize(m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        // a call that yields no output has no output buffer and waits for the device instead of copying back
+        const detail::stage_item items[] = { { host_in, nullptr, in_bytes }, { nullptr, out_bytes ? host_out : nullptr, out_bytes } };
+        detail::host_stage(m_device, items, [&](void *const *dev) {
+            const int rc = sdsp_hip_cic_process(m_plan.get(), dev[0], samples, dev[1], n, m_channels, samples, m_position, m_state.get(),
+                                                nullptr);
+            return rc || out_bytes ? rc : sdsp_hip_device_synchronize(m_device);
+        });
         m_position += samples;
         return n;
     }
@@ -133,38 +118,40 @@ public:
     void set_variant(int variant)
     {
         ensure_plan();
-        detail::check(sdsp_hip_cic_plan_set_variant(m_plan, variant));
+        detail::check(sdsp_hip_cic_plan_set_variant(m_plan.get(), variant));
     }
     // chunks of input per workgroup of the fused kernel, 0 = automatic
     void set_segment(std::uint32_t chunks)
     {
         ensure_plan();
-        detail::check(sdsp_hip_cic_plan_set_segment(m_plan, chunks));
+        detail::check(sdsp_hip_cic_plan_set_segment(m_plan.get(), chunks));
     }
     sdsp_hip_cic_plan_info info()
     {
         ensure_plan();
         sdsp_hip_cic_plan_info i{};
-        detail::check(sdsp_hip_cic_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_cic_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_cic_plan_create(&m_plan, m_order, m_down, m_delay, sizeof(in_t) == 4 ? SDSP_HIP_CIC_I32 : SDSP_HIP_CIC_I16,
-                                                   m_in_bits, m_complex ? SDSP_HIP_CIC_COMPLEX : SDSP_HIP_CIC_REAL,
-                                                   std::is_same<out_t, float>::value ? SDSP_HIP_CIC_OUT_F32 : SDSP_HIP_CIC_OUT_INT, m_scale,
-                                                   m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_cic_plan *plan = nullptr;
+        detail::check(sdsp_hip_cic_plan_create(&plan, m_order, m_down, m_delay, sizeof(in_t) == 4 ? SDSP_HIP_CIC_I32 : SDSP_HIP_CIC_I16,
+                                               m_in_bits, m_complex ? SDSP_HIP_CIC_COMPLEX : SDSP_HIP_CIC_REAL,
+                                               std::is_same<out_t, float>::value ? SDSP_HIP_CIC_OUT_F32 : SDSP_HIP_CIC_OUT_INT, m_scale,
+                                               m_device));
+        m_plan.reset(plan);
     }
     void zero_state()
     {
         const std::size_t bytes = static_cast<std::size_t>(m_hist) * static_cast<std::size_t>(m_channels) * (m_complex ? 2u : 1u) * sizeof(in_t);
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-        const std::vector<unsigned char> host(bytes, 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), bytes, m_device));
+            m_state.alloc(bytes, m_device);
+        m_state.fill<unsigned char>(bytes, 0);
     }
     void ensure_state()
     {
@@ -179,8 +166,8 @@ private:
     std::uint32_t m_hist{ 0 };
     double m_scale{ 1.0 };
     std::uint64_t m_position{ 0 };
-    sdsp_hip_cic_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_cic_plan, sdsp_hip_cic_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

@@ -38,27 +38,19 @@ public:
         }
         set_window(SDSP_HIP_WINDOW_HANN);
     }
-    ~csd_bank()
-    {
-        if (m_plan)
-            sdsp_hip_csd_plan_destroy(m_plan);
-        for (void *p : { m_state, m_acc_xy, m_acc_auto })
-            if (p)
-                sdsp_hip_free(p, m_device);
-    }
     csd_bank(const csd_bank &) = delete;
     csd_bank &operator=(const csd_bank &) = delete;
 
     void set_window(const std::array<double, n_fft> &w)
     {
         m_window = w;
-        drop_plan();
+        m_plan.reset();
     }
     // periodic SDSP_HIP_WINDOW_RECT / HANN / HAMMING / BLACKMAN (sdsp_hip_stft_window)
     void set_window(int kind)
     {
         detail::check(sdsp_hip_stft_window(kind, n_fft, m_window.data()));
-        drop_plan();
+        m_plan.reset();
     }
     // a new stream: position, segment count, history and sums back to zero
     void reset()
@@ -86,8 +78,8 @@ public:
     {
         ensure();
         const std::uint64_t f = segments(samples);
-        detail::check(sdsp_hip_csd_process(m_plan, device_in, in_stride, samples, m_position, m_state, static_cast<double *>(m_acc_xy),
-                                           2 * bins, static_cast<double *>(m_acc_auto), bins, stream));
+        detail::check(sdsp_hip_csd_process(m_plan.get(), device_in, in_stride, samples, m_position, m_state.get(), acc_xy(), 2 * bins,
+                                           acc_auto(), bins, stream));
         m_position += samples;
         m_frames += f;
     }
@@ -97,18 +89,13 @@ public:
         ensure();
         if (samples == 0)
             return;
-        const size_t in_bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
-        void *di = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
         const std::uint64_t f = segments(samples);
-        if (!rc)
-            rc = sdsp_hip_csd_process(m_plan, di, samples, samples, m_position, m_state, static_cast<double *>(m_acc_xy), 2 * bins,
-                                      static_cast<double *>(m_acc_auto), bins, nullptr);
-        if (!rc)
-            rc = sdsp_hip_device_synchronize(m_device);
-        sdsp_hip_free(di, m_device);
-        detail::check(rc);
+        const size_t in_bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes } }, [&](void *const *dev) {
+            const int rc = sdsp_hip_csd_process(m_plan.get(), dev[0], samples, samples, m_position, m_state.get(), acc_xy(), 2 * bins,
+                                                acc_auto(), bins, nullptr);
+            return rc ? rc : sdsp_hip_device_synchronize(m_device);
+        });
         m_position += samples;
         m_frames += f;
     }
@@ -131,7 +118,7 @@ public:
     {
         ensure();
         sdsp_hip_csd_plan_info i{};
-        detail::check(sdsp_hip_csd_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_csd_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -139,49 +126,40 @@ private:
     void finalize(int mode, real_t *device_out, std::uint64_t out_stride, void *stream)
     {
         ensure();
-        detail::check(sdsp_hip_csd_finalize(m_plan, mode, static_cast<const double *>(m_acc_xy), 2 * bins,
-                                            static_cast<const double *>(m_acc_auto), bins, m_frames, device_out, out_stride, stream));
+        detail::check(sdsp_hip_csd_finalize(m_plan.get(), mode, acc_xy(), 2 * bins, acc_auto(), bins, m_frames, device_out, out_stride,
+                                            stream));
     }
     void finalize_host(int mode, real_t *host_out, std::uint64_t row)
     {
         ensure();
         const size_t out_bytes = static_cast<size_t>(npairs() * row) * sizeof(real_t);
-        void *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&dout, out_bytes, m_device));
-        int rc = sdsp_hip_csd_finalize(m_plan, mode, static_cast<const double *>(m_acc_xy), 2 * bins,
-                                       static_cast<const double *>(m_acc_auto), bins, m_frames, dout, row, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_csd_finalize(m_plan.get(), mode, acc_xy(), 2 * bins, acc_auto(), bins, m_frames, dev[0], row, nullptr);
+        });
     }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_csd_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
+    double *acc_xy() const noexcept { return static_cast<double *>(m_acc_xy.get()); }
+    double *acc_auto() const noexcept { return static_cast<double *>(m_acc_auto.get()); }
     void zero_buffers()
     {
-        std::vector<real_t> st(static_cast<size_t>(hist * m_channels), real_t(0));
-        std::vector<double> acc(static_cast<size_t>(bins * (2 * npairs() + m_channels)), 0.0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, st.data(), st.size() * sizeof(real_t), m_device));
-        detail::check(sdsp_hip_memcpy_h2d(m_acc_xy, acc.data(), static_cast<size_t>(2 * bins * npairs()) * sizeof(double), m_device));
-        detail::check(sdsp_hip_memcpy_h2d(m_acc_auto, acc.data(), static_cast<size_t>(bins * m_channels) * sizeof(double), m_device));
+        m_state.fill(static_cast<size_t>(hist * m_channels), real_t(0));
+        m_acc_xy.fill(static_cast<size_t>(2 * bins * npairs()), 0.0);
+        m_acc_auto.fill(static_cast<size_t>(bins * m_channels), 0.0);
     }
     void ensure()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_csd_plan_create(&m_plan, n_fft, hop, m_window.data(), m_detrend, m_scaling, m_fs,
+        if (!m_plan) {
+            sdsp_hip_csd_plan *plan = nullptr;
+            detail::check(sdsp_hip_csd_plan_create(&plan, n_fft, hop, m_window.data(), m_detrend, m_scaling, m_fs,
                                                    detail::precision_of<real_t>::value, m_channels, npairs(), m_pairs.data(), 0,
                                                    m_device));
+            m_plan.reset(plan);
+        }
         if (!m_acc_auto) {
             if (!m_state)
-                detail::check(sdsp_hip_malloc(&m_state, static_cast<size_t>(hist * m_channels) * sizeof(real_t), m_device));
+                m_state.alloc(static_cast<size_t>(hist * m_channels) * sizeof(real_t), m_device);
             if (!m_acc_xy)
-                detail::check(sdsp_hip_malloc(&m_acc_xy, static_cast<size_t>(2 * bins * npairs()) * sizeof(double), m_device));
-            detail::check(sdsp_hip_malloc(&m_acc_auto, static_cast<size_t>(bins * m_channels) * sizeof(double), m_device));
+                m_acc_xy.alloc(static_cast<size_t>(2 * bins * npairs()) * sizeof(double), m_device);
+            m_acc_auto.alloc(static_cast<size_t>(bins * m_channels) * sizeof(double), m_device);
             zero_buffers();
         }
     }
@@ -192,10 +170,8 @@ private:
     int m_device;
     std::vector<std::uint32_t> m_pairs; // a_0, b_0, a_1, b_1 ..
     std::array<double, n_fft> m_window{};
-    sdsp_hip_csd_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
-    void *m_acc_xy{ nullptr };
-    void *m_acc_auto{ nullptr };
+    detail::plan_ptr<sdsp_hip_csd_plan, sdsp_hip_csd_plan_destroy> m_plan;
+    detail::device_buffer m_state, m_acc_xy, m_acc_auto;
     std::uint64_t m_position{ 0 }, m_frames{ 0 };
 };
 } // namespace sdsp

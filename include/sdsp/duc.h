@@ -27,13 +27,6 @@ public:
           m_coeff(n_taps, 0.0)
     {
     }
-    ~duc_bank()
-    {
-        if (m_plan)
-            sdsp_hip_duc_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     duc_bank(const duc_bank &) = delete;
     duc_bank &operator=(const duc_bank &) = delete;
 
@@ -42,13 +35,13 @@ public:
         if (h.size() != m_taps)
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: coefficient count differs from n_taps");
         m_coeff = h;
-        drop_plan();
+        m_plan.reset();
     }
     // Hamming low-pass at 1 / (2 up) of the output rate with gain up (sdsp_hip_resample_design(n_taps, up, 1)); needs up >= 2
     void set_antiimage_coeff()
     {
         detail::check(sdsp_hip_resample_design(m_taps, m_up, 1, m_coeff.data()));
-        drop_plan();
+        m_plan.reset();
     }
     // forget the history and the stream position
     void reset()
@@ -72,7 +65,8 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_duc_process(m_plan, device_in, in_stride, device_out, out_stride, samples, m_position, m_state, stream));
+        detail::check(sdsp_hip_duc_process(m_plan.get(), device_in, in_stride, device_out, out_stride, samples, m_position, m_state.get(),
+                                           stream));
         m_position += samples;
     }
     // host pointers: in = bands x samples I/Q pairs, out = channels x out_samples(samples) elements, both contiguous
@@ -85,19 +79,9 @@ public:
         const std::size_t out_bytes = static_cast<std::size_t>(m_channels * outs) * out_elem_bytes();
         if (samples == 0)
             return;
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_duc_process(m_plan, di, samples, dout, outs, samples, m_position, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes }, { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_duc_process(m_plan.get(), dev[0], samples, dev[1], outs, samples, m_position, m_state.get(), nullptr);
+        });
         m_position += samples;
     }
     std::uint32_t channels() const noexcept { return m_channels; }
@@ -107,42 +91,36 @@ public:
     void set_variant(int variant)
     {
         ensure_plan();
-        detail::check(sdsp_hip_duc_plan_set_variant(m_plan, variant));
+        detail::check(sdsp_hip_duc_plan_set_variant(m_plan.get(), variant));
     }
     const std::vector<double> &coeff() const { return m_coeff; }
     sdsp_hip_duc_plan_info info()
     {
         ensure_plan();
         sdsp_hip_duc_plan_info i{};
-        detail::check(sdsp_hip_duc_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_duc_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
     std::size_t out_elem_bytes() const noexcept { return (m_real ? 1u : 2u) * sizeof(real_t); }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_duc_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_duc_plan_create(&m_plan, m_taps, m_coeff.data(), m_up, m_channels,
-                                                   static_cast<std::uint32_t>(m_bands.size()), m_bands.data(),
-                                                   m_real ? SDSP_HIP_DUC_REAL : SDSP_HIP_DUC_COMPLEX,
-                                                   detail::precision_of<real_t>::value, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_duc_plan *plan = nullptr;
+        detail::check(sdsp_hip_duc_plan_create(&plan, m_taps, m_coeff.data(), m_up, m_channels, static_cast<std::uint32_t>(m_bands.size()),
+                                               m_bands.data(), m_real ? SDSP_HIP_DUC_REAL : SDSP_HIP_DUC_COMPLEX,
+                                               detail::precision_of<real_t>::value, m_device));
+        m_plan.reset(plan);
     }
     void zero_state()
     {
         const std::size_t hist = m_taps && m_up ? (m_taps - 1) / m_up : 0;
         const std::size_t bytes = (hist ? hist : 1) * m_bands.size() * 2 * sizeof(real_t);
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-        const std::vector<unsigned char> host(bytes, 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), bytes, m_device));
+            m_state.alloc(bytes, m_device);
+        m_state.fill<unsigned char>(bytes, 0);
     }
     void ensure_state()
     {
@@ -156,8 +134,8 @@ private:
     std::vector<sdsp_hip_duc_band> m_bands;
     std::vector<double> m_coeff;
     std::uint64_t m_position{ 0 };
-    sdsp_hip_duc_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_duc_plan, sdsp_hip_duc_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

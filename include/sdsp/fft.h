@@ -218,22 +218,22 @@ public:
     rfft_plan_t(std::uint32_t n_real, int radix = 2, int direction = SDSP_HIP_FORWARD, std::uint64_t max_batch = 1, int device = 0)
         : m_n_real(n_real)
     {
-        detail::check(sdsp_hip_rfft_plan_create_p(&m_plan, n_real, radix, direction, detail::precision_of<real_t>::value,
-                                                  max_batch, device));
+        sdsp_hip_fft_plan *plan = nullptr;
+        detail::check(sdsp_hip_rfft_plan_create_p(&plan, n_real, radix, direction, detail::precision_of<real_t>::value, max_batch, device));
+        m_plan.reset(plan);
     }
-    ~rfft_plan_t() { sdsp_hip_fft_plan_destroy(m_plan); }
     rfft_plan_t(const rfft_plan_t &) = delete;
     rfft_plan_t &operator=(const rfft_plan_t &) = delete;
     std::uint32_t size() const noexcept { return m_n_real; }
     void exec(real_t *device_data, std::uint64_t batch, void *stream = nullptr)
     {
-        detail::check(sdsp_hip_fft_exec(m_plan, device_data, batch, stream));
+        detail::check(sdsp_hip_fft_exec(m_plan.get(), device_data, batch, stream));
     }
-    void exec_host(real_t *host_data, std::uint64_t batch) { detail::check(sdsp_hip_fft_exec_host(m_plan, host_data, batch)); }
+    void exec_host(real_t *host_data, std::uint64_t batch) { detail::check(sdsp_hip_fft_exec_host(m_plan.get(), host_data, batch)); }
 
 private:
     std::uint32_t m_n_real;
-    sdsp_hip_fft_plan *m_plan{ nullptr };
+    detail::plan_ptr<sdsp_hip_fft_plan, sdsp_hip_fft_plan_destroy> m_plan;
 };
 using rfft_plan = rfft_plan_t<float>;
 

@@ -23,7 +23,6 @@ public:
         : m_n(n), m_width(width), m_direction(direction), m_output(output), m_shift(shift), m_device(device)
     {
     }
-    ~fft_cols_plan() { drop_plan(); }
     fft_cols_plan(const fft_cols_plan &) = delete;
     fft_cols_plan &operator=(const fft_cols_plan &) = delete;
 
@@ -31,13 +30,13 @@ public:
     void set_window(const std::vector<double> &w)
     {
         m_window = w;
-        drop_plan();
+        m_plan.reset();
     }
     // 0 = the tuned kernel, 1 = the plain cross-check kernel
     void set_variant(int variant)
     {
         ensure_plan();
-        detail::check(sdsp_hip_fft_cols_plan_set_variant(m_plan, variant));
+        detail::check(sdsp_hip_fft_cols_plan_set_variant(m_plan.get(), variant));
     }
     // real_t values per output element: 2 for complex output, 1 for power
     std::uint32_t out_values() const noexcept { return m_output == SDSP_HIP_FFT_COLS_COMPLEX ? 2u : 1u; }
@@ -48,44 +47,40 @@ public:
     void exec(const void *device_in, void *device_out, std::uint64_t batch, void *stream = nullptr)
     {
         ensure_plan();
-        detail::check(sdsp_hip_fft_cols_exec(m_plan, device_in, device_out, batch, stream));
+        detail::check(sdsp_hip_fft_cols_exec(m_plan.get(), device_in, device_out, batch, stream));
     }
     // host pointers: in = batch x n x width complex (interleaved), out = batch x n x width x out_values() reals, both contiguous
     void exec_host(const real_t *host_in, real_t *host_out, std::uint64_t batch)
     {
         ensure_plan();
-        detail::check(sdsp_hip_fft_cols_exec_host(m_plan, host_in, host_out, batch));
+        detail::check(sdsp_hip_fft_cols_exec_host(m_plan.get(), host_in, host_out, batch));
     }
     std::uint64_t launches(std::uint64_t batch)
     {
         ensure_plan();
         std::uint64_t v = 0;
-        detail::check(sdsp_hip_fft_cols_plan_launches(m_plan, batch, &v));
+        detail::check(sdsp_hip_fft_cols_plan_launches(m_plan.get(), batch, &v));
         return v;
     }
     sdsp_hip_fft_cols_plan_info info()
     {
         ensure_plan();
         sdsp_hip_fft_cols_plan_info i{};
-        detail::check(sdsp_hip_fft_cols_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_fft_cols_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_fft_cols_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
         if (!m_window.empty() && m_window.size() != m_n)
             throw hip_error(SDSP_HIP_ERR_INVALID_ARG, "sdsp::fft_cols_plan: the window must hold n values");
-        if (!m_plan)
-            detail::check(sdsp_hip_fft_cols_plan_create(&m_plan, m_n, m_width, m_direction, detail::precision_of<real_t>::value, m_output,
-                                                        m_shift ? 1 : 0, m_window.empty() ? nullptr : m_window.data(), m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_fft_cols_plan *plan = nullptr;
+        detail::check(sdsp_hip_fft_cols_plan_create(&plan, m_n, m_width, m_direction, detail::precision_of<real_t>::value, m_output,
+                                                    m_shift ? 1 : 0, m_window.empty() ? nullptr : m_window.data(), m_device));
+        m_plan.reset(plan);
     }
 
     std::uint32_t m_n;
@@ -95,7 +90,7 @@ private:
     bool m_shift;
     int m_device;
     std::vector<double> m_window;
-    sdsp_hip_fft_cols_plan *m_plan{ nullptr };
+    detail::plan_ptr<sdsp_hip_fft_cols_plan, sdsp_hip_fft_cols_plan_destroy> m_plan;
 };
 } // namespace sdsp
 

@@ -28,7 +28,6 @@ public:
         : m_padtype(padtype), m_padlen(padlen), m_device(device)
     {
     }
-    ~filtfilt_bank() { drop_plan(); }
     filtfilt_bank(const filtfilt_bank &) = delete;
     filtfilt_bank &operator=(const filtfilt_bank &) = delete;
 
@@ -61,13 +60,13 @@ public:
     void process(real_t *device_data, std::uint64_t channels, std::uint64_t samples, std::uint64_t stride, void *stream = nullptr)
     {
         ensure_plan();
-        detail::check(sdsp_hip_filtfilt_process(m_plan, device_data, channels, samples, stride, stream));
+        detail::check(sdsp_hip_filtfilt_process(m_plan.get(), device_data, channels, samples, stride, stream));
     }
     // host pointer, contiguous rows; synchronous
     void process_host(real_t *host_data, std::uint64_t channels, std::uint64_t samples)
     {
         ensure_plan();
-        detail::check(sdsp_hip_filtfilt_process_host(m_plan, host_data, channels, samples, samples));
+        detail::check(sdsp_hip_filtfilt_process_host(m_plan.get(), host_data, channels, samples, samples));
     }
     std::array<double, m_t + 1> steady_state() const
     {
@@ -79,7 +78,7 @@ public:
     {
         ensure_plan();
         sdsp_hip_filtfilt_plan_info i{};
-        detail::check(sdsp_hip_filtfilt_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_filtfilt_plan_get_info(m_plan.get(), &i));
         return i;
     }
     int kind() const noexcept { return m_kind; }
@@ -91,20 +90,16 @@ private:
     void designed(int kind)
     {
         m_kind = kind;
-        drop_plan();
-    }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_filtfilt_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
+        m_plan.reset();
     }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_filtfilt_plan_create(&m_plan, m_t, m_kind, m_a.data(), m_b.data(), m_gain,
-                                                        detail::precision_of<real_t>::value, m_padtype, m_padlen, 0, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_filtfilt_plan *plan = nullptr;
+        detail::check(sdsp_hip_filtfilt_plan_create(&plan, m_t, m_kind, m_a.data(), m_b.data(), m_gain, detail::precision_of<real_t>::value,
+                                                    m_padtype, m_padlen, 0, m_device));
+        m_plan.reset(plan);
     }
 
     int m_padtype;
@@ -114,7 +109,7 @@ private:
     double m_gain{ 1.0 };
     coeff_array m_a{};
     coeff_array m_b{};
-    sdsp_hip_filtfilt_plan *m_plan{ nullptr };
+    detail::plan_ptr<sdsp_hip_filtfilt_plan, sdsp_hip_filtfilt_plan_destroy> m_plan;
 };
 } // namespace sdsp
 

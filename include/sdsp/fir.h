@@ -50,11 +50,10 @@ public:
         const auto n = static_cast<std::uint64_t>(std::distance(begin, end));
         if (n == 0)
             return;
-        sdsp_hip_fir_plan *plan = nullptr;
-        detail::check(sdsp_hip_fir_plan_create(&plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(), SDSP_HIP_F64, 0));
-        const int rc = sdsp_hip_fir_process_host(plan, &*begin, 1, n, n, m_mem.data());
-        sdsp_hip_fir_plan_destroy(plan);
-        detail::check(rc);
+        sdsp_hip_fir_plan *created = nullptr;
+        detail::check(sdsp_hip_fir_plan_create(&created, static_cast<std::uint32_t>(n_taps), m_coeff.data(), SDSP_HIP_F64, 0));
+        const detail::plan_ptr<sdsp_hip_fir_plan, sdsp_hip_fir_plan_destroy> plan(created);
+        detail::check(sdsp_hip_fir_process_host(plan.get(), &*begin, 1, n, n, m_mem.data()));
     }
 
     void set_coeff(const std::array<double, n_taps> &h, double gain_in = 1.0)
@@ -79,13 +78,6 @@ public:
 template <size_t n_taps, typename real_t = float> class fir_bank {
 public:
     explicit fir_bank(std::uint64_t channels, int device = 0) : m_channels(channels), m_device(device) {}
-    ~fir_bank()
-    {
-        if (m_plan)
-            sdsp_hip_fir_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     fir_bank(const fir_bank &) = delete;
     fir_bank &operator=(const fir_bank &) = delete;
 
@@ -111,7 +103,7 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_fir_process(m_plan, device_data, m_channels, samples, stride, m_state, stream));
+        detail::check(sdsp_hip_fir_process(m_plan.get(), device_data, m_channels, samples, stride, m_state.get(), stream));
     }
     // host pointer convenience: channels x samples, contiguous
     void process_host(real_t *host_data, std::uint64_t samples)
@@ -119,15 +111,9 @@ public:
         ensure_plan();
         ensure_state();
         const size_t bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
-        void *d = nullptr;
-        detail::check(sdsp_hip_malloc(&d, bytes, m_device));
-        int rc = sdsp_hip_memcpy_h2d(d, host_data, bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_fir_process(m_plan, d, m_channels, samples, samples, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_data, d, bytes, m_device);
-        sdsp_hip_free(d, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_data, host_data, bytes } }, [&](void *const *dev) {
+            return sdsp_hip_fir_process(m_plan.get(), dev[0], m_channels, samples, samples, m_state.get(), nullptr);
+        });
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     const std::array<double, n_taps> &coeff() const { return m_coeff; }
@@ -136,7 +122,7 @@ public:
     {
         ensure_plan();
         sdsp_hip_fir_plan_info i{};
-        detail::check(sdsp_hip_fir_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_fir_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -157,29 +143,26 @@ private:
     void redesign(filter_type t)
     {
         m_f_type = t;
-        if (m_plan) {
-            sdsp_hip_fir_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
+        m_plan.reset();
     }
     void ensure_plan()
     {
         if (m_plan)
             return;
+        sdsp_hip_fir_plan *plan = nullptr;
         if (m_fft)
-            detail::check(sdsp_hip_fir_fft_plan_create(&m_plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(),
+            detail::check(sdsp_hip_fir_fft_plan_create(&plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(),
                                                        detail::precision_of<real_t>::value, m_fft_n, m_workspace_bytes, m_device));
         else
-            detail::check(sdsp_hip_fir_plan_create(&m_plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(),
+            detail::check(sdsp_hip_fir_plan_create(&plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(),
                                                    detail::precision_of<real_t>::value, m_device));
+        m_plan.reset(plan);
     }
     void fill_state(real_t v)
     {
-        const bool fresh = !m_state;
-        if (fresh)
-            detail::check(sdsp_hip_malloc(&m_state, hist * m_channels * sizeof(real_t), m_device));
-        std::vector<real_t> host(hist * m_channels, v);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size() * sizeof(real_t), m_device));
+        if (!m_state)
+            m_state.alloc(hist * m_channels * sizeof(real_t), m_device);
+        m_state.fill(hist * m_channels, v);
     }
     void ensure_state()
     {
@@ -191,8 +174,8 @@ private:
     int m_device;
     std::array<double, n_taps> m_coeff{};
     filter_type m_f_type{ filter_type::none };
-    sdsp_hip_fir_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_fir_plan, sdsp_hip_fir_plan_destroy> m_plan;
+    detail::device_buffer m_state;
     bool m_fft{ false };
     std::uint32_t m_fft_n{ 0 };
     std::uint64_t m_workspace_bytes{ 0 };

@@ -25,16 +25,11 @@ public:
              int device = 0)
         : m_channels(channels), m_taps(n_taps), m_complex(complex_rows), m_device(device)
     {
-        detail::check(sdsp_hip_lms_plan_create(&m_plan, channels, n_taps, complex_rows ? SDSP_HIP_LMS_COMPLEX : SDSP_HIP_LMS_REAL,
+        sdsp_hip_lms_plan *plan = nullptr;
+        detail::check(sdsp_hip_lms_plan_create(&plan, channels, n_taps, complex_rows ? SDSP_HIP_LMS_COMPLEX : SDSP_HIP_LMS_REAL,
                                                detail::precision_of<real_t>::value, normalised ? SDSP_HIP_LMS_NLMS : SDSP_HIP_LMS_LMS, eps,
                                                device));
-    }
-    ~lms_bank()
-    {
-        if (m_plan)
-            sdsp_hip_lms_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
+        m_plan.reset(plan);
     }
     lms_bank(const lms_bank &) = delete;
     lms_bank &operator=(const lms_bank &) = delete;
@@ -52,8 +47,8 @@ public:
                  std::uint64_t y_stride, real_t *device_e, std::uint64_t e_stride, std::uint64_t samples, double mu, void *stream = nullptr)
     {
         ensure_state();
-        detail::check(sdsp_hip_lms_process(m_plan, device_x, x_stride, device_d, d_stride, device_y, y_stride, device_e, e_stride, samples,
-                                           mu, m_state, stream));
+        detail::check(sdsp_hip_lms_process(m_plan.get(), device_x, x_stride, device_d, d_stride, device_y, y_stride, device_e, e_stride,
+                                           samples, mu, m_state.get(), stream));
     }
     // host pointers: contiguous channels x samples elements each; y and e may be null
     void process_host(const real_t *host_x, const real_t *host_d, real_t *host_y, real_t *host_e, std::uint64_t samples, double mu)
@@ -62,34 +57,19 @@ public:
         if (samples == 0)
             return;
         const std::size_t bytes = static_cast<std::size_t>(m_channels * samples) * elem_bytes();
-        void *dev[4] = { nullptr, nullptr, nullptr, nullptr };
-        const bool want[4] = { true, true, host_y != nullptr, host_e != nullptr };
-        int rc = 0;
-        for (int i = 0; i < 4 && !rc; i++)
-            if (want[i])
-                rc = sdsp_hip_malloc(&dev[i], bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(dev[0], host_x, bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(dev[1], host_d, bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_lms_process(m_plan, dev[0], samples, dev[1], samples, dev[2], samples, dev[3], samples, samples, mu, m_state,
-                                      nullptr);
-        if (!rc && host_y)
-            rc = sdsp_hip_memcpy_d2h(host_y, dev[2], bytes, m_device);
-        if (!rc && host_e)
-            rc = sdsp_hip_memcpy_d2h(host_e, dev[3], bytes, m_device);
-        for (void *p : dev)
-            if (p)
-                sdsp_hip_free(p, m_device);
-        detail::check(rc);
+        const detail::stage_item items[] = { { host_x, nullptr, bytes }, { host_d, nullptr, bytes }, { nullptr, host_y, bytes },
+                                             { nullptr, host_e, bytes } };
+        detail::host_stage(m_device, items, [&](void *const *dev) {
+            return sdsp_hip_lms_process(m_plan.get(), dev[0], samples, dev[1], samples, dev[2], samples, dev[3], samples, samples, mu,
+                                        m_state.get(), nullptr);
+        });
     }
     // the weights, [channel][tap] (x 2, interleaved re, im, for complex rows), copied from the device state: the identified systems
     std::vector<real_t> weights()
     {
         ensure_state();
         std::vector<real_t> w(weight_elems() * (m_complex ? 2u : 1u));
-        detail::check(sdsp_hip_memcpy_d2h(w.data(), m_state, weight_elems() * elem_bytes(), m_device));
+        m_state.download(w.data(), weight_elems() * elem_bytes());
         return w;
     }
     // ... copied into it; the history stays
@@ -98,15 +78,15 @@ public:
         if (w.size() != weight_elems() * (m_complex ? 2u : 1u))
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: weights must be channels x n_taps");
         ensure_state();
-        detail::check(sdsp_hip_memcpy_h2d(m_state, w.data(), weight_elems() * elem_bytes(), m_device));
+        m_state.upload(w.data(), weight_elems() * elem_bytes());
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     std::uint32_t taps() const noexcept { return m_taps; }
-    void set_variant(int variant) { detail::check(sdsp_hip_lms_plan_set_variant(m_plan, variant)); }
+    void set_variant(int variant) { detail::check(sdsp_hip_lms_plan_set_variant(m_plan.get(), variant)); }
     sdsp_hip_lms_plan_info info() const
     {
         sdsp_hip_lms_plan_info i{};
-        detail::check(sdsp_hip_lms_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_lms_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -116,11 +96,10 @@ private:
     void zero_state()
     {
         std::uint64_t bytes = 0;
-        detail::check(sdsp_hip_lms_state_bytes(m_plan, &bytes));
+        detail::check(sdsp_hip_lms_state_bytes(m_plan.get(), &bytes));
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, static_cast<std::size_t>(bytes), m_device));
-        const std::vector<unsigned char> host(static_cast<std::size_t>(bytes), 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size(), m_device));
+            m_state.alloc(static_cast<std::size_t>(bytes), m_device);
+        m_state.fill<unsigned char>(static_cast<std::size_t>(bytes), 0);
     }
     void ensure_state()
     {
@@ -132,8 +111,8 @@ private:
     std::uint32_t m_taps;
     bool m_complex;
     int m_device;
-    sdsp_hip_lms_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_lms_plan, sdsp_hip_lms_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

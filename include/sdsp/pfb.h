@@ -27,13 +27,6 @@ public:
     {
         set_prototype(SDSP_HIP_WINDOW_HAMMING);
     }
-    ~pfb_bank()
-    {
-        if (m_plan)
-            sdsp_hip_pfb_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     pfb_bank(const pfb_bank &) = delete;
     pfb_bank &operator=(const pfb_bank &) = delete;
 
@@ -43,7 +36,7 @@ public:
         if (h.size() != static_cast<std::size_t>(m_m) * m_p)
             detail::check(SDSP_HIP_ERR_INVALID_SIZE);
         m_taps = h;
-        drop_plan();
+        m_plan.reset();
     }
     // windowed-sinc prototype, cutoff at half the sub-band spacing, unit DC gain (sdsp_hip_pfb_prototype): SDSP_HIP_WINDOW_*
     void set_prototype(int window_kind)
@@ -52,7 +45,7 @@ public:
         detail::check(sdsp_hip_pfb_prototype(window_kind, m_m, m_p, h.data()));
         h.pop_back();
         m_taps = h;
-        drop_plan();
+        m_plan.reset();
     }
     void preload_filter(double value) { fill_state(static_cast<real_t>(value)); }
     // forget the history and the stream position
@@ -84,8 +77,8 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_pfb_process(m_plan, device_in, in_stride, device_out, out_stride, m_streams, samples, m_position, m_state,
-                                           stream));
+        detail::check(sdsp_hip_pfb_process(m_plan.get(), device_in, in_stride, device_out, out_stride, m_streams, samples, m_position,
+                                           m_state.get(), stream));
         m_position += samples;
     }
     // host pointers: in = streams x samples x sample_values(), out = streams x frames(samples) x bins() x 2, both contiguous
@@ -98,26 +91,16 @@ public:
         const std::size_t out_bytes = static_cast<std::size_t>(m_streams * row * 2) * sizeof(real_t);
         if (in_bytes == 0)
             return;
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_pfb_process(m_plan, di, samples, dout, row, m_streams, samples, m_position, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes }, { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_pfb_process(m_plan.get(), dev[0], samples, dev[1], row, m_streams, samples, m_position, m_state.get(), nullptr);
+        });
         m_position += samples;
     }
     sdsp_hip_pfb_plan_info info()
     {
         ensure_plan();
         sdsp_hip_pfb_plan_info i{};
-        detail::check(sdsp_hip_pfb_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_pfb_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -127,28 +110,24 @@ private:
         const std::size_t h = hist() > 0 ? hist() : 1;
         return h * static_cast<std::size_t>(m_streams) * sample_values();
     }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_pfb_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_pfb_plan_create(&m_plan, m_m, m_p, m_hop, m_taps.data(), m_kind, m_phase,
-                                                   detail::precision_of<real_t>::value, 0, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_pfb_plan *plan = nullptr;
+        detail::check(sdsp_hip_pfb_plan_create(&plan, m_m, m_p, m_hop, m_taps.data(), m_kind, m_phase, detail::precision_of<real_t>::value,
+                                               0, m_device));
+        m_plan.reset(plan);
     }
     void fill_state(real_t v)
     {
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, state_values() * sizeof(real_t), m_device));
+            m_state.alloc(state_values() * sizeof(real_t), m_device);
         std::vector<real_t> host(state_values(), v);
         if (m_kind == SDSP_HIP_PFB_COMPLEX) // a steady real value: zero imaginary parts
             for (std::size_t i = 1; i < host.size(); i += 2)
                 host[i] = real_t(0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size() * sizeof(real_t), m_device));
+        m_state.upload(host.data(), host.size() * sizeof(real_t));
     }
     void ensure_state()
     {
@@ -161,8 +140,8 @@ private:
     int m_kind, m_phase, m_device;
     std::uint64_t m_position{ 0 };
     std::vector<double> m_taps;
-    sdsp_hip_pfb_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_pfb_plan, sdsp_hip_pfb_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

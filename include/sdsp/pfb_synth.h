@@ -38,13 +38,6 @@ public:
     {
         set_dual_of_prototype(SDSP_HIP_WINDOW_HAMMING);
     }
-    ~pfb_synthesis_bank()
-    {
-        if (m_plan)
-            sdsp_hip_pfb_synth_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     pfb_synthesis_bank(const pfb_synthesis_bank &) = delete;
     pfb_synthesis_bank &operator=(const pfb_synthesis_bank &) = delete;
 
@@ -54,7 +47,7 @@ public:
         if (g.size() != static_cast<std::size_t>(m_m) * m_p)
             detail::check(SDSP_HIP_ERR_INVALID_SIZE);
         m_taps = g;
-        drop_plan();
+        m_plan.reset();
     }
     // the dual of an analysis prototype h
     void set_dual_of(const std::vector<double> &h) { set_taps(pfb_dual_prototype(h, m_m, m_p, m_hop)); }
@@ -88,8 +81,8 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_pfb_synth_process(m_plan, device_in, in_stride, device_out, out_stride, m_streams, frames, m_position,
-                                                 m_state, stream));
+        detail::check(sdsp_hip_pfb_synth_process(m_plan.get(), device_in, in_stride, device_out, out_stride, m_streams, frames, m_position,
+                                                 m_state.get(), stream));
         m_position += frames * m_hop;
     }
     // host pointers: in = streams x frames x bins() x 2, out = streams x frames * hop x sample_values(), both contiguous
@@ -102,26 +95,17 @@ public:
         const std::size_t out_bytes = static_cast<std::size_t>(m_streams * out_row * sample_values()) * sizeof(real_t);
         if (in_bytes == 0)
             return;
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_pfb_synth_process(m_plan, di, in_row, dout, out_row, m_streams, frames, m_position, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes }, { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_pfb_synth_process(m_plan.get(), dev[0], in_row, dev[1], out_row, m_streams, frames, m_position, m_state.get(),
+                                              nullptr);
+        });
         m_position += out_row;
     }
     sdsp_hip_pfb_synth_plan_info info()
     {
         ensure_plan();
         sdsp_hip_pfb_synth_plan_info i{};
-        detail::check(sdsp_hip_pfb_synth_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_pfb_synth_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -131,25 +115,20 @@ private:
         const std::size_t h = hist() > 0 ? hist() : 1;
         return h * static_cast<std::size_t>(m_streams) * sample_values();
     }
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_pfb_synth_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_pfb_synth_plan_create(&m_plan, m_m, m_p, m_hop, m_taps.data(), m_kind, m_phase,
-                                                         detail::precision_of<real_t>::value, 0, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_pfb_synth_plan *plan = nullptr;
+        detail::check(sdsp_hip_pfb_synth_plan_create(&plan, m_m, m_p, m_hop, m_taps.data(), m_kind, m_phase,
+                                                     detail::precision_of<real_t>::value, 0, m_device));
+        m_plan.reset(plan);
     }
     void zero_state()
     {
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, state_values() * sizeof(real_t), m_device));
-        const std::vector<real_t> host(state_values(), real_t(0));
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size() * sizeof(real_t), m_device));
+            m_state.alloc(state_values() * sizeof(real_t), m_device);
+        m_state.fill(state_values(), real_t(0));
     }
     void ensure_state()
     {
@@ -162,8 +141,8 @@ private:
     int m_kind, m_phase, m_device;
     std::uint64_t m_position{ 0 };
     std::vector<double> m_taps;
-    sdsp_hip_pfb_synth_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_pfb_synth_plan, sdsp_hip_pfb_synth_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

@@ -25,21 +25,13 @@ public:
     pll_bank(std::uint64_t channels, int mode, const std::vector<std::uint32_t> &fcw0, double max_dev = 0.5, int device = 0)
         : m_channels(channels), m_device(device)
     {
-        detail::check(sdsp_hip_pll_plan_create(&m_plan, channels, detail::precision_of<real_t>::value, mode, fcw0.data(), fcw0.size(), max_dev,
-                                               device));
+        create(mode, fcw0.data(), fcw0.size(), max_dev);
     }
     // one centre-frequency word shared by every channel
     pll_bank(std::uint64_t channels, int mode, std::uint32_t fcw0, double max_dev = 0.5, int device = 0)
         : m_channels(channels), m_device(device)
     {
-        detail::check(sdsp_hip_pll_plan_create(&m_plan, channels, detail::precision_of<real_t>::value, mode, &fcw0, 1, max_dev, device));
-    }
-    ~pll_bank()
-    {
-        if (m_plan)
-            sdsp_hip_pll_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
+        create(mode, &fcw0, 1, max_dev);
     }
     pll_bank(const pll_bank &) = delete;
     pll_bank &operator=(const pll_bank &) = delete;
@@ -58,8 +50,8 @@ public:
                  void *stream = nullptr)
     {
         ensure_state();
-        detail::check(sdsp_hip_pll_process(m_plan, device_x, x_stride, device_y, y_stride, device_err, err_stride, device_freq, freq_stride,
-                                           samples, alpha, beta, m_state, stream));
+        detail::check(sdsp_hip_pll_process(m_plan.get(), device_x, x_stride, device_y, y_stride, device_err, err_stride, device_freq,
+                                           freq_stride, samples, alpha, beta, m_state.get(), stream));
     }
     // host pointers: contiguous channels x samples elements each (x and y: interleaved re, im); y, err and freq may be null
     void process_host(const real_t *host_x, real_t *host_y, real_t *host_err, real_t *host_freq, std::uint64_t samples, double alpha,
@@ -69,32 +61,19 @@ public:
         if (samples == 0)
             return;
         const std::size_t reals = static_cast<std::size_t>(m_channels * samples) * sizeof(real_t);
-        const std::size_t bytes[4] = { 2 * reals, 2 * reals, reals, reals };
-        void *dev[4] = { nullptr, nullptr, nullptr, nullptr };
-        void *const host_out[4] = { nullptr, host_y, host_err, host_freq };
-        int rc = 0;
-        for (int i = 0; i < 4 && !rc; i++)
-            if (i == 0 || host_out[i])
-                rc = sdsp_hip_malloc(&dev[i], bytes[i], m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(dev[0], host_x, bytes[0], m_device);
-        if (!rc)
-            rc = sdsp_hip_pll_process(m_plan, dev[0], samples, dev[1], samples, dev[2], samples, dev[3], samples, samples, alpha, beta,
-                                      m_state, nullptr);
-        for (int i = 1; i < 4 && !rc; i++)
-            if (host_out[i])
-                rc = sdsp_hip_memcpy_d2h(host_out[i], dev[i], bytes[i], m_device);
-        for (void *p : dev)
-            if (p)
-                sdsp_hip_free(p, m_device);
-        detail::check(rc);
+        const detail::stage_item items[] = { { host_x, nullptr, 2 * reals }, { nullptr, host_y, 2 * reals }, { nullptr, host_err, reals },
+                                             { nullptr, host_freq, reals } };
+        detail::host_stage(m_device, items, [&](void *const *dev) {
+            return sdsp_hip_pll_process(m_plan.get(), dev[0], samples, dev[1], samples, dev[2], samples, dev[3], samples, samples, alpha,
+                                        beta, m_state.get(), nullptr);
+        });
     }
     // the integrators, copied from the device state: the tracked frequency offsets in cycles per sample
     std::vector<real_t> freq()
     {
         ensure_state();
         std::vector<real_t> f(static_cast<std::size_t>(m_channels));
-        detail::check(sdsp_hip_memcpy_d2h(f.data(), m_state, f.size() * sizeof(real_t), m_device));
+        m_state.download(f.data(), f.size() * sizeof(real_t));
         return f;
     }
     // the phase words, copied from the device state
@@ -102,7 +81,7 @@ public:
     {
         ensure_state();
         std::vector<std::uint32_t> t(static_cast<std::size_t>(m_channels));
-        detail::check(sdsp_hip_memcpy_d2h(t.data(), words(), t.size() * sizeof(std::uint32_t), m_device));
+        m_state.download(t.data(), t.size() * sizeof(std::uint32_t), words());
         return t;
     }
     // ... copied into it; the other half of the state stays
@@ -111,34 +90,41 @@ public:
         if (f.size() != m_channels)
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: freq must hold one value per channel");
         ensure_state();
-        detail::check(sdsp_hip_memcpy_h2d(m_state, f.data(), f.size() * sizeof(real_t), m_device));
+        m_state.upload(f.data(), f.size() * sizeof(real_t));
     }
     void set_phase(const std::vector<std::uint32_t> &t)
     {
         if (t.size() != m_channels)
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: phase must hold one word per channel");
         ensure_state();
-        detail::check(sdsp_hip_memcpy_h2d(words(), t.data(), t.size() * sizeof(std::uint32_t), m_device));
+        m_state.upload(t.data(), t.size() * sizeof(std::uint32_t), words());
     }
     std::uint64_t channels() const noexcept { return m_channels; }
-    void set_variant(int variant) { detail::check(sdsp_hip_pll_plan_set_variant(m_plan, variant)); }
+    void set_variant(int variant) { detail::check(sdsp_hip_pll_plan_set_variant(m_plan.get(), variant)); }
     sdsp_hip_pll_plan_info info() const
     {
         sdsp_hip_pll_plan_info i{};
-        detail::check(sdsp_hip_pll_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_pll_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
-    void *words() const noexcept { return static_cast<unsigned char *>(m_state) + static_cast<std::size_t>(m_channels) * sizeof(real_t); }
+    void create(int mode, const std::uint32_t *fcw0, std::size_t n_fcw0, double max_dev)
+    {
+        sdsp_hip_pll_plan *plan = nullptr;
+        detail::check(sdsp_hip_pll_plan_create(&plan, m_channels, detail::precision_of<real_t>::value, mode, fcw0, n_fcw0, max_dev,
+                                               m_device));
+        m_plan.reset(plan);
+    }
+    // byte offset of the phase words in the state, behind the integrators
+    std::size_t words() const noexcept { return static_cast<std::size_t>(m_channels) * sizeof(real_t); }
     void zero_state()
     {
         std::uint64_t bytes = 0;
-        detail::check(sdsp_hip_pll_state_bytes(m_plan, &bytes));
+        detail::check(sdsp_hip_pll_state_bytes(m_plan.get(), &bytes));
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, static_cast<std::size_t>(bytes), m_device));
-        const std::vector<unsigned char> host(static_cast<std::size_t>(bytes), 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size(), m_device));
+            m_state.alloc(static_cast<std::size_t>(bytes), m_device);
+        m_state.fill<unsigned char>(static_cast<std::size_t>(bytes), 0);
     }
     void ensure_state()
     {
@@ -148,8 +134,8 @@ private:
 
     std::uint64_t m_channels;
     int m_device;
-    sdsp_hip_pll_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_pll_plan, sdsp_hip_pll_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

@@ -23,17 +23,12 @@ public:
     rank_filter_bank(std::uint64_t channels, std::uint32_t window, std::uint32_t rank, int device = 0)
         : m_channels(channels), m_window(window), m_rank(rank), m_device(device)
     {
-        detail::check(sdsp_hip_rank_plan_create(&m_plan, channels, window, rank, detail::precision_of<real_t>::value, device));
+        sdsp_hip_rank_plan *plan = nullptr;
+        detail::check(sdsp_hip_rank_plan_create(&plan, channels, window, rank, detail::precision_of<real_t>::value, device));
+        m_plan.reset(plan);
     }
     // the running median of an odd window
     static std::uint32_t median_rank(std::uint32_t window) noexcept { return (window - 1u) / 2u; }
-    ~rank_filter_bank()
-    {
-        if (m_plan)
-            sdsp_hip_rank_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     rank_filter_bank(const rank_filter_bank &) = delete;
     rank_filter_bank &operator=(const rank_filter_bank &) = delete;
 
@@ -50,7 +45,7 @@ public:
                  void *stream = nullptr)
     {
         ensure_state();
-        detail::check(sdsp_hip_rank_process(m_plan, device_x, x_stride, device_y, y_stride, samples, m_state, stream));
+        detail::check(sdsp_hip_rank_process(m_plan.get(), device_x, x_stride, device_y, y_stride, samples, m_state.get(), stream));
     }
     // host pointers: contiguous channels x samples elements each
     void process_host(const real_t *host_x, real_t *host_y, std::uint64_t samples)
@@ -59,20 +54,9 @@ public:
         if (samples == 0)
             return;
         const std::size_t bytes = static_cast<std::size_t>(m_channels * samples) * sizeof(real_t);
-        void *dev[2] = { nullptr, nullptr };
-        int rc = 0;
-        for (int i = 0; i < 2 && !rc; i++)
-            rc = sdsp_hip_malloc(&dev[i], bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(dev[0], host_x, bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_rank_process(m_plan, dev[0], samples, dev[1], samples, samples, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_y, dev[1], bytes, m_device);
-        for (void *p : dev)
-            if (p)
-                sdsp_hip_free(p, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_x, nullptr, bytes }, { nullptr, host_y, bytes } }, [&](void *const *dev) {
+            return sdsp_hip_rank_process(m_plan.get(), dev[0], samples, dev[1], samples, samples, m_state.get(), nullptr);
+        });
     }
     // the x history, [channel][window - 1], newest first, copied from the device state
     std::vector<real_t> history()
@@ -80,7 +64,7 @@ public:
         ensure_state();
         std::vector<real_t> h(history_elems());
         if (!h.empty())
-            detail::check(sdsp_hip_memcpy_d2h(h.data(), m_state, h.size() * sizeof(real_t), m_device));
+            m_state.download(h.data(), h.size() * sizeof(real_t));
         return h;
     }
     // ... copied into it
@@ -90,17 +74,17 @@ public:
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: history must be channels x (window - 1)");
         ensure_state();
         if (!h.empty())
-            detail::check(sdsp_hip_memcpy_h2d(m_state, h.data(), h.size() * sizeof(real_t), m_device));
+            m_state.upload(h.data(), h.size() * sizeof(real_t));
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     std::uint32_t window() const noexcept { return m_window; }
     std::uint32_t rank() const noexcept { return m_rank; }
-    void set_variant(int variant) { detail::check(sdsp_hip_rank_plan_set_variant(m_plan, variant)); }
-    void set_run(std::uint64_t run) { detail::check(sdsp_hip_rank_plan_set_run(m_plan, run)); }
+    void set_variant(int variant) { detail::check(sdsp_hip_rank_plan_set_variant(m_plan.get(), variant)); }
+    void set_run(std::uint64_t run) { detail::check(sdsp_hip_rank_plan_set_run(m_plan.get(), run)); }
     sdsp_hip_rank_plan_info info() const
     {
         sdsp_hip_rank_plan_info i{};
-        detail::check(sdsp_hip_rank_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_rank_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -112,9 +96,8 @@ private:
         if (bytes == 0)
             return;
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, bytes, m_device));
-        const std::vector<unsigned char> host(bytes, 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size(), m_device));
+            m_state.alloc(bytes, m_device);
+        m_state.fill<unsigned char>(bytes, 0);
     }
     void ensure_state()
     {
@@ -125,8 +108,8 @@ private:
     std::uint64_t m_channels;
     std::uint32_t m_window, m_rank;
     int m_device;
-    sdsp_hip_rank_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_rank_plan, sdsp_hip_rank_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

@@ -25,26 +25,19 @@ public:
     static constexpr size_t hist = (n_taps - 1) / up; // history per channel, newest first
 
     explicit fir_resampler_bank(std::uint64_t channels, int device = 0) : m_channels(channels), m_device(device) {}
-    ~fir_resampler_bank()
-    {
-        if (m_plan)
-            sdsp_hip_resample_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     fir_resampler_bank(const fir_resampler_bank &) = delete;
     fir_resampler_bank &operator=(const fir_resampler_bank &) = delete;
 
     void set_coeff(const std::array<double, n_taps> &h)
     {
         m_coeff = h;
-        drop_plan();
+        m_plan.reset();
     }
     // Hamming low-pass at 1 / (2 max(up, down)) of the intermediate rate, gain up (sdsp_hip_resample_design)
     void set_antialias_coeff()
     {
         detail::check(sdsp_hip_resample_design(static_cast<std::uint32_t>(n_taps), up, down, m_coeff.data()));
-        drop_plan();
+        m_plan.reset();
     }
     void preload_filter(double value) { fill_state(static_cast<real_t>(value)); }
     void reset()
@@ -67,7 +60,8 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_resample_process(m_plan, device_in, in_stride, device_out, out_stride, m_channels, samples, m_state, stream));
+        detail::check(sdsp_hip_resample_process(m_plan.get(), device_in, in_stride, device_out, out_stride, m_channels, samples,
+                                                m_state.get(), stream));
     }
     // host pointers: in = channels x samples, out = channels x out_samples(samples), both contiguous
     void process_host(const real_t *host_in, real_t *host_out, std::uint64_t samples)
@@ -77,19 +71,9 @@ public:
         const std::uint64_t outs = out_samples(samples);
         const size_t in_bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
         const size_t out_bytes = static_cast<size_t>(m_channels * outs) * sizeof(real_t);
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_resample_process(m_plan, di, samples, dout, outs, m_channels, samples, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes }, { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_resample_process(m_plan.get(), dev[0], samples, dev[1], outs, m_channels, samples, m_state.get(), nullptr);
+        });
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     const std::array<double, n_taps> &coeff() const { return m_coeff; }
@@ -97,31 +81,26 @@ public:
     {
         ensure_plan();
         sdsp_hip_resample_plan_info i{};
-        detail::check(sdsp_hip_resample_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_resample_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
     static constexpr size_t state_len = hist > 0 ? hist : 1;
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_resample_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_resample_plan_create(&m_plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(), up, down,
-                                                        detail::precision_of<real_t>::value, m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_resample_plan *plan = nullptr;
+        detail::check(sdsp_hip_resample_plan_create(&plan, static_cast<std::uint32_t>(n_taps), m_coeff.data(), up, down,
+                                                    detail::precision_of<real_t>::value, m_device));
+        m_plan.reset(plan);
     }
     void fill_state(real_t v)
     {
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, state_len * m_channels * sizeof(real_t), m_device));
-        std::vector<real_t> host(state_len * m_channels, v);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size() * sizeof(real_t), m_device));
+            m_state.alloc(state_len * m_channels * sizeof(real_t), m_device);
+        m_state.fill(state_len * m_channels, v);
     }
     void ensure_state()
     {
@@ -132,8 +111,8 @@ private:
     std::uint64_t m_channels;
     int m_device;
     std::array<double, n_taps> m_coeff{};
-    sdsp_hip_resample_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_resample_plan, sdsp_hip_resample_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

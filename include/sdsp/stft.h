@@ -31,26 +31,19 @@ public:
     {
         set_window(SDSP_HIP_WINDOW_HANN);
     }
-    ~stft_bank()
-    {
-        if (m_plan)
-            sdsp_hip_stft_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-    }
     stft_bank(const stft_bank &) = delete;
     stft_bank &operator=(const stft_bank &) = delete;
 
     void set_window(const std::array<double, n_fft> &w)
     {
         m_window = w;
-        drop_plan();
+        m_plan.reset();
     }
     // periodic SDSP_HIP_WINDOW_RECT / HANN / HAMMING / BLACKMAN (sdsp_hip_stft_window)
     void set_window(int kind)
     {
         detail::check(sdsp_hip_stft_window(kind, n_fft, m_window.data()));
-        drop_plan();
+        m_plan.reset();
     }
     void preload_filter(double value) { fill_state(static_cast<real_t>(value)); }
     void reset()
@@ -75,7 +68,8 @@ public:
     {
         ensure_plan();
         ensure_state();
-        detail::check(sdsp_hip_stft_process(m_plan, device_in, in_stride, device_out, out_stride, m_channels, samples, m_state, stream));
+        detail::check(sdsp_hip_stft_process(m_plan.get(), device_in, in_stride, device_out, out_stride, m_channels, samples,
+                                            m_state.get(), stream));
     }
     // host pointers: in = channels x samples, out = channels x frames(samples) x bins x bin_values(), both contiguous
     void process_host(const real_t *host_in, real_t *host_out, std::uint64_t samples)
@@ -85,19 +79,9 @@ public:
         const std::uint64_t row = frames(samples) * bins;
         const size_t in_bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
         const size_t out_bytes = static_cast<size_t>(m_channels * row * bin_values()) * sizeof(real_t);
-        void *di = nullptr, *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_malloc(&dout, out_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
-        if (!rc)
-            rc = sdsp_hip_stft_process(m_plan, di, samples, dout, row, m_channels, samples, m_state, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(di, m_device);
-        if (dout)
-            sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes }, { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_stft_process(m_plan.get(), dev[0], samples, dev[1], row, m_channels, samples, m_state.get(), nullptr);
+        });
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     const std::array<double, n_fft> &window() const { return m_window; }
@@ -105,31 +89,26 @@ public:
     {
         ensure_plan();
         sdsp_hip_stft_plan_info i{};
-        detail::check(sdsp_hip_stft_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_stft_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
     static constexpr size_t state_len = hist > 0 ? hist : 1;
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_stft_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
     void ensure_plan()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_stft_plan_create(&m_plan, n_fft, hop, m_window.data(), m_output, detail::precision_of<real_t>::value, 0,
-                                                    m_device));
+        if (m_plan)
+            return;
+        sdsp_hip_stft_plan *plan = nullptr;
+        detail::check(sdsp_hip_stft_plan_create(&plan, n_fft, hop, m_window.data(), m_output, detail::precision_of<real_t>::value, 0,
+                                                m_device));
+        m_plan.reset(plan);
     }
     void fill_state(real_t v)
     {
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, state_len * m_channels * sizeof(real_t), m_device));
-        std::vector<real_t> host(state_len * m_channels, v);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size() * sizeof(real_t), m_device));
+            m_state.alloc(state_len * m_channels * sizeof(real_t), m_device);
+        m_state.fill(state_len * m_channels, v);
     }
     void ensure_state()
     {
@@ -141,8 +120,8 @@ private:
     int m_output;
     int m_device;
     std::array<double, n_fft> m_window{};
-    sdsp_hip_stft_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_stft_plan, sdsp_hip_stft_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

@@ -30,15 +30,10 @@ public:
         if (phases == 0 || h.empty() || h.size() % phases)
             throw hip_error(SDSP_HIP_ERR_INVALID_SIZE, "sdsp_hip: h must hold phases x taps values");
         detail::check(sdsp_hip_timing_step(sps, &m_step0));
-        detail::check(sdsp_hip_timing_plan_create(&m_plan, channels, detail::precision_of<real_t>::value, mode, phases,
+        sdsp_hip_timing_plan *plan = nullptr;
+        detail::check(sdsp_hip_timing_plan_create(&plan, channels, detail::precision_of<real_t>::value, mode, phases,
                                                   static_cast<std::uint32_t>(h.size() / phases), h.data(), m_step0, max_dev, device));
-    }
-    ~timing_bank()
-    {
-        if (m_plan)
-            sdsp_hip_timing_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
+        m_plan.reset(plan);
     }
     timing_bank(const timing_bank &) = delete;
     timing_bank &operator=(const timing_bank &) = delete;
@@ -54,7 +49,7 @@ public:
     std::uint64_t max_out(std::uint64_t samples) const
     {
         std::uint64_t n = 0;
-        detail::check(sdsp_hip_timing_max_out(m_plan, samples, &n));
+        detail::check(sdsp_hip_timing_max_out(m_plan.get(), samples, &n));
         return n;
     }
 
@@ -65,8 +60,8 @@ public:
                  std::uint64_t samples, double alpha, double beta, void *stream = nullptr)
     {
         ensure_state();
-        detail::check(sdsp_hip_timing_process(m_plan, device_x, x_stride, device_y, y_stride, device_err, err_stride, device_period,
-                                              period_stride, device_counts, samples, alpha, beta, m_state, stream));
+        detail::check(sdsp_hip_timing_process(m_plan.get(), device_x, x_stride, device_y, y_stride, device_err, err_stride, device_period,
+                                              period_stride, device_counts, samples, alpha, beta, m_state.get(), stream));
     }
     // host pointers: x holds channels x samples elements (interleaved re, im), y, err and period channels x max_out(samples); err and
     // period may be null.  Returns the counts: row c holds counts[c] symbols, the rest of it is left as it was
@@ -80,28 +75,17 @@ public:
         const std::uint64_t cap = max_out(samples);
         const std::size_t in_bytes = static_cast<std::size_t>(m_channels * samples) * 2 * sizeof(real_t);
         const std::size_t reals = static_cast<std::size_t>(m_channels * cap) * sizeof(real_t);
-        const std::size_t bytes[5] = { in_bytes, 2 * reals, reals, reals, counts.size() * sizeof(std::uint32_t) };
-        void *dev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-        void *const host[5] = { nullptr, host_y, host_err, host_period, counts.data() };
-        int rc = host_y ? 0 : SDSP_HIP_ERR_INVALID_ARG;
-        for (int i = 0; i < 5 && !rc; i++)
-            if (i == 0 || host[i])
-                rc = sdsp_hip_malloc(&dev[i], bytes[i], m_device);
-        if (!rc)
-            rc = sdsp_hip_memcpy_h2d(dev[0], host_x, bytes[0], m_device);
-        for (int i = 1; i < 4 && !rc; i++) // what lies behind a row's count keeps the caller's values
-            if (host[i])
-                rc = sdsp_hip_memcpy_h2d(dev[i], host[i], bytes[i], m_device);
-        if (!rc)
-            rc = sdsp_hip_timing_process(m_plan, dev[0], samples, dev[1], cap, dev[2], cap, dev[3], cap, static_cast<std::uint32_t *>(dev[4]),
-                                         samples, alpha, beta, m_state, nullptr);
-        for (int i = 1; i < 5 && !rc; i++)
-            if (host[i])
-                rc = sdsp_hip_memcpy_d2h(host[i], dev[i], bytes[i], m_device);
-        for (void *p : dev)
-            if (p)
-                sdsp_hip_free(p, m_device);
-        detail::check(rc);
+        detail::check(host_y ? SDSP_HIP_OK : SDSP_HIP_ERR_INVALID_ARG);
+        // y, err and period go in as well as out: what lies behind a row's count keeps the caller's values
+        const detail::stage_item items[] = { { host_x, nullptr, in_bytes },
+                                             { host_y, host_y, 2 * reals },
+                                             { host_err, host_err, reals },
+                                             { host_period, host_period, reals },
+                                             { nullptr, counts.data(), counts.size() * sizeof(std::uint32_t) } };
+        detail::host_stage(m_device, items, [&](void *const *dev) {
+            return sdsp_hip_timing_process(m_plan.get(), dev[0], samples, dev[1], cap, dev[2], cap, dev[3], cap,
+                                           static_cast<std::uint32_t *>(dev[4]), samples, alpha, beta, m_state.get(), nullptr);
+        });
         return counts;
     }
     // the integrators, copied from the device state: the tracked offsets of the half-symbol period, in samples
@@ -109,7 +93,7 @@ public:
     {
         ensure_state();
         std::vector<real_t> f(static_cast<std::size_t>(m_channels));
-        detail::check(sdsp_hip_memcpy_d2h(f.data(), at(integ_offset()), f.size() * sizeof(real_t), m_device));
+        m_state.download(f.data(), f.size() * sizeof(real_t), integ_offset());
         return f;
     }
     // the Q32.32 stream times, copied from the device state
@@ -117,16 +101,16 @@ public:
     {
         ensure_state();
         std::vector<std::uint64_t> t(static_cast<std::size_t>(m_channels));
-        detail::check(sdsp_hip_memcpy_d2h(t.data(), m_state, t.size() * sizeof(std::uint64_t), m_device));
+        m_state.download(t.data(), t.size() * sizeof(std::uint64_t));
         return t;
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     std::uint64_t step0() const noexcept { return m_step0; }
-    void set_variant(int variant) { detail::check(sdsp_hip_timing_plan_set_variant(m_plan, variant)); }
+    void set_variant(int variant) { detail::check(sdsp_hip_timing_plan_set_variant(m_plan.get(), variant)); }
     sdsp_hip_timing_plan_info info() const
     {
         sdsp_hip_timing_plan_info i{};
-        detail::check(sdsp_hip_timing_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_timing_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
@@ -138,15 +122,13 @@ private:
         const std::size_t ch = static_cast<std::size_t>(m_channels);
         return ch * 8 + 2 * up8(ch * 2 * sizeof(real_t));
     }
-    void *at(std::size_t offset) const noexcept { return static_cast<unsigned char *>(m_state) + offset; }
     void zero_state()
     {
         std::uint64_t bytes = 0;
-        detail::check(sdsp_hip_timing_state_bytes(m_plan, &bytes));
+        detail::check(sdsp_hip_timing_state_bytes(m_plan.get(), &bytes));
         if (!m_state)
-            detail::check(sdsp_hip_malloc(&m_state, static_cast<std::size_t>(bytes), m_device));
-        const std::vector<unsigned char> host(static_cast<std::size_t>(bytes), 0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, host.data(), host.size(), m_device));
+            m_state.alloc(static_cast<std::size_t>(bytes), m_device);
+        m_state.fill<unsigned char>(static_cast<std::size_t>(bytes), 0);
     }
     void ensure_state()
     {
@@ -157,8 +139,8 @@ private:
     std::uint64_t m_channels;
     int m_device;
     std::uint64_t m_step0{ 0 };
-    sdsp_hip_timing_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
+    detail::plan_ptr<sdsp_hip_timing_plan, sdsp_hip_timing_plan_destroy> m_plan;
+    detail::device_buffer m_state;
 };
 } // namespace sdsp
 

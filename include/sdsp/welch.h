@@ -32,28 +32,19 @@ public:
     {
         set_window(SDSP_HIP_WINDOW_HANN);
     }
-    ~welch_bank()
-    {
-        if (m_plan)
-            sdsp_hip_welch_plan_destroy(m_plan);
-        if (m_state)
-            sdsp_hip_free(m_state, m_device);
-        if (m_acc)
-            sdsp_hip_free(m_acc, m_device);
-    }
     welch_bank(const welch_bank &) = delete;
     welch_bank &operator=(const welch_bank &) = delete;
 
     void set_window(const std::array<double, n_fft> &w)
     {
         m_window = w;
-        drop_plan();
+        m_plan.reset();
     }
     // periodic SDSP_HIP_WINDOW_RECT / HANN / HAMMING / BLACKMAN (sdsp_hip_stft_window)
     void set_window(int kind)
     {
         detail::check(sdsp_hip_stft_window(kind, n_fft, m_window.data()));
-        drop_plan();
+        m_plan.reset();
     }
     // a new stream: position, segment count, history and sums back to zero
     void reset()
@@ -79,8 +70,8 @@ public:
     {
         ensure();
         const std::uint64_t f = segments(samples);
-        detail::check(sdsp_hip_welch_process(m_plan, device_in, in_stride, m_channels, samples, m_position, m_state,
-                                             static_cast<double *>(m_acc), bins, stream));
+        detail::check(sdsp_hip_welch_process(m_plan.get(), device_in, in_stride, m_channels, samples, m_position, m_state.get(), acc(),
+                                             bins, stream));
         m_position += samples;
         m_frames += f;
     }
@@ -90,18 +81,13 @@ public:
         ensure();
         if (samples == 0)
             return;
-        const size_t in_bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
-        void *di = nullptr;
-        detail::check(sdsp_hip_malloc(&di, in_bytes, m_device));
-        int rc = sdsp_hip_memcpy_h2d(di, host_in, in_bytes, m_device);
         const std::uint64_t f = segments(samples);
-        if (!rc)
-            rc = sdsp_hip_welch_process(m_plan, di, samples, m_channels, samples, m_position, m_state, static_cast<double *>(m_acc), bins,
-                                        nullptr);
-        if (!rc)
-            rc = sdsp_hip_device_synchronize(m_device);
-        sdsp_hip_free(di, m_device);
-        detail::check(rc);
+        const size_t in_bytes = static_cast<size_t>(m_channels * samples) * sizeof(real_t);
+        detail::host_stage(m_device, { { host_in, nullptr, in_bytes } }, [&](void *const *dev) {
+            const int rc = sdsp_hip_welch_process(m_plan.get(), dev[0], samples, m_channels, samples, m_position, m_state.get(), acc(),
+                                                  bins, nullptr);
+            return rc ? rc : sdsp_hip_device_synchronize(m_device);
+        });
         m_position += samples;
         m_frames += f;
     }
@@ -109,21 +95,16 @@ public:
     void psd(real_t *device_out, std::uint64_t out_stride, void *stream = nullptr)
     {
         ensure();
-        detail::check(sdsp_hip_welch_finalize(m_plan, static_cast<const double *>(m_acc), bins, m_frames, device_out, out_stride,
-                                              m_channels, stream));
+        detail::check(sdsp_hip_welch_finalize(m_plan.get(), acc(), bins, m_frames, device_out, out_stride, m_channels, stream));
     }
     // host pointer: out = channels x bins, contiguous (synchronous)
     void psd_host(real_t *host_out)
     {
         ensure();
         const size_t out_bytes = static_cast<size_t>(m_channels * bins) * sizeof(real_t);
-        void *dout = nullptr;
-        detail::check(sdsp_hip_malloc(&dout, out_bytes, m_device));
-        int rc = sdsp_hip_welch_finalize(m_plan, static_cast<const double *>(m_acc), bins, m_frames, dout, bins, m_channels, nullptr);
-        if (!rc)
-            rc = sdsp_hip_memcpy_d2h(host_out, dout, out_bytes, m_device);
-        sdsp_hip_free(dout, m_device);
-        detail::check(rc);
+        detail::host_stage(m_device, { { nullptr, host_out, out_bytes } }, [&](void *const *dev) {
+            return sdsp_hip_welch_finalize(m_plan.get(), acc(), bins, m_frames, dev[0], bins, m_channels, nullptr);
+        });
     }
     std::uint64_t channels() const noexcept { return m_channels; }
     const std::array<double, n_fft> &window() const { return m_window; }
@@ -131,34 +112,29 @@ public:
     {
         ensure();
         sdsp_hip_welch_plan_info i{};
-        detail::check(sdsp_hip_welch_plan_get_info(m_plan, &i));
+        detail::check(sdsp_hip_welch_plan_get_info(m_plan.get(), &i));
         return i;
     }
 
 private:
-    void drop_plan()
-    {
-        if (m_plan) {
-            sdsp_hip_welch_plan_destroy(m_plan);
-            m_plan = nullptr;
-        }
-    }
+    double *acc() const noexcept { return static_cast<double *>(m_acc.get()); }
     void zero_buffers()
     {
-        std::vector<real_t> st(static_cast<size_t>(hist * m_channels), real_t(0));
-        std::vector<double> acc(static_cast<size_t>(bins * m_channels), 0.0);
-        detail::check(sdsp_hip_memcpy_h2d(m_state, st.data(), st.size() * sizeof(real_t), m_device));
-        detail::check(sdsp_hip_memcpy_h2d(m_acc, acc.data(), acc.size() * sizeof(double), m_device));
+        m_state.fill(static_cast<size_t>(hist * m_channels), real_t(0));
+        m_acc.fill(static_cast<size_t>(bins * m_channels), 0.0);
     }
     void ensure()
     {
-        if (!m_plan)
-            detail::check(sdsp_hip_welch_plan_create(&m_plan, n_fft, hop, m_window.data(), m_detrend, m_scaling, m_fs,
+        if (!m_plan) {
+            sdsp_hip_welch_plan *plan = nullptr;
+            detail::check(sdsp_hip_welch_plan_create(&plan, n_fft, hop, m_window.data(), m_detrend, m_scaling, m_fs,
                                                      detail::precision_of<real_t>::value, 0, m_device));
+            m_plan.reset(plan);
+        }
         if (!m_acc) {
             if (!m_state)
-                detail::check(sdsp_hip_malloc(&m_state, static_cast<size_t>(hist * m_channels) * sizeof(real_t), m_device));
-            detail::check(sdsp_hip_malloc(&m_acc, static_cast<size_t>(bins * m_channels) * sizeof(double), m_device));
+                m_state.alloc(static_cast<size_t>(hist * m_channels) * sizeof(real_t), m_device);
+            m_acc.alloc(static_cast<size_t>(bins * m_channels) * sizeof(double), m_device);
             zero_buffers();
         }
     }
@@ -168,9 +144,8 @@ private:
     double m_fs;
     int m_device;
     std::array<double, n_fft> m_window{};
-    sdsp_hip_welch_plan *m_plan{ nullptr };
-    void *m_state{ nullptr };
-    void *m_acc{ nullptr };
+    detail::plan_ptr<sdsp_hip_welch_plan, sdsp_hip_welch_plan_destroy> m_plan;
+    detail::device_buffer m_state, m_acc;
     std::uint64_t m_position{ 0 }, m_frames{ 0 };
 };
 } // namespace sdsp
