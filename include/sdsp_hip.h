@@ -1812,6 +1812,112 @@ typedef struct {
 } sdsp_hip_cfar_plan_info;
 int sdsp_hip_cfar_plan_get_info(const sdsp_hip_cfar_plan *plan, sdsp_hip_cfar_plan_info *info);
 
+/* ------------------------------------------------------------------ 2-D CFAR plans on range-Doppler maps */
+
+/*
+ * 2-D cell-averaging CFAR: a detector over `maps` compact maps of D rows (Doppler, the circular axis) by R
+ * columns (range, with edges), with an ordered list of detections per map.  Stateless: a map is complete in itself.
+ *   - layout.  Rows are real, F32 or F64; element [m][d][r] is at (m D + d) R + r: exactly the POWER output of a column plan with
+ *     n = D, width = R.  Maps are compact: there is no row pitch and no row-distance parameter (as for the column plans), so every
+ *     size is a uint32_t (D, R) or the uint64_t count of maps.
+ *   - window.  A plan fixes train_d = Ld, guard_d = Gd, train_r = Lr, guard_r = Gr (Hd = Ld + Gd, Hr = Lr + Gr), an edge mode, a peak
+ *     flag, and alpha or a scale table.  The training set of cell (d, r) is every ((d + i) mod D, r + j) with |i| <= Hd and |j| <= Hr
+ *     except the guard box |i| <= Gd and |j| <= Gr.  Cells with r + j outside [0, R) count as +0 in the sums and are left out of the
+ *     cell count n(r) = (2 Hd + 1) wf(r) - (2 Gd + 1) wg(r), where wf(r) is the number of in-map columns in r - Hr .. r + Hr and wg(r)
+ *     that in r - Gr .. r + Gr.
+ *   - sums.  Every sum starts from +0 and adds in ascending index, one rounding per addition, never an FMA.  Per row:
+ *         lag(d, r)  = sum_{j = -Hr .. -Gr - 1} p[d][r + j]      mid(d, r) = sum_{j = -Gr .. Gr} p[d][r + j]
+ *         lead(d, r) = sum_{j = Gr + 1 .. Hr} p[d][r + j]        side = fl(lag + lead)      full = fl(fl(lag + mid) + lead)
+ *     and across rows, with d + i taken mod D:
+ *         top = sum_{i = -Hd .. -Gd - 1} full(d + i, r)    band = sum_{i = -Gd .. Gd} side(d + i, r)
+ *         bottom = sum_{i = Gd + 1 .. Hd} full(d + i, r)   T = fl(fl(top + band) + bottom).
+ *     There is no subtraction, hence no cancellation; an empty sum is +0.
+ *   - threshold.  thr = fl(T c(r)); c(r) is a host double rounded once to the precision: alpha / n(r), or entry r of the caller's
+ *     table of R doubles when one is given (each finite once rounded).  A NaN threshold is written as the canonical quiet NaN (sign 0,
+ *     the top mantissa bit alone), as sdsp_hip_cfar_process does.
+ *   - edges.  SDSP_HIP_CFAR2D_EDGE_MARK: the cells with r < Hr or r >= R - Hr get thr = +inf, det = 0 and no hit (what
+ *     simpledsp_amd.cfar does).  SDSP_HIP_CFAR2D_EDGE_CLIP: those cells are tested against their clipped training set with c(r) as above.
+ *   - detection.  det = (p > thr) ? 1 : 0: a NaN on either side gives 0.  With peak != 0 a hit must also be the local maximum of its
+ *     eight neighbours (d + i mod D, r + j), |i|, |j| <= 1; out-of-map columns are ignored; D = 1 or 2 compares with the wrapped cells
+ *     as they fall (for D = 1 that includes the cell itself, which it never exceeds).  The comparison is p > q for the neighbours that
+ *     precede the cell in (i, j) lexicographic order and p >= q for those that follow: a plateau yields exactly one hit, and a NaN
+ *     neighbour suppresses the hit.  det then carries the peak condition too.
+ *   - outputs.  Each may be NULL; all NULL is SDSP_HIP_ERR_INVALID_ARG.  thr: a map of the precision.  det: a uint8_t map.  The hit
+ *     list: hits[m][0 .. cap) records and counts[m], which go together.  counts[m] is the total number of hits of map m, even when it
+ *     exceeds cap (a total above 2^32 - 1 is written as 2^32 - 1); records k < min(counts[m], cap) are the hits in ascending
+ *     (doppler, range); nothing at or past that index is written.
+ *   - outputs may not overlap the input or each other; the input is never written.  Pointers need the alignment of one element of
+ *     their type (hits: 4 bytes in F32, 8 in F64; counts: 4) and no more.
+ *   - independence.  The bits of cell (m, d, r) depend only on its own window and the plan: not on maps, m, which outputs were asked
+ *     for, the variant, or pointer alignment.
+ *   - limits.  Lr, Gr <= SDSP_HIP_CFAR2D_MAX_R; Ld <= SDSP_HIP_CFAR2D_MAX_TRAIN_D, Gd <= SDSP_HIP_CFAR2D_MAX_GUARD_D; Ld + Lr >= 1;
+ *     2 Hd + 1 <= D <= 2^20; 1 <= R < 2^31; maps D R < 2^40; cap < 2^31.
+ *   - process is asynchronous on `stream`, allocates nothing and can be captured in a graph: the list's workspace (12 bytes per row and
+ *     strip of 64 columns) is allocated at plan creation from max_maps.  maps > max_maps is SDSP_HIP_ERR_INVALID_SIZE; maps == 0 does
+ *     nothing.
+ * Errors: a window, D, R, max_maps, maps or cap outside the limits: SDSP_HIP_ERR_INVALID_SIZE; a null plan, descriptor or input, all
+ * outputs null, hits without counts or counts without hits, an unknown edge mode or precision, a table value that is not
+ * finite once rounded (alpha / n(r) is not checked), a misaligned pointer, an overlap: SDSP_HIP_ERR_INVALID_ARG; set_alpha on a plan made with a
+ * table: SDSP_HIP_ERR_INVALID_ARG; a map that needs more than 2^31 - 1 workgroups: SDSP_HIP_ERR_UNSUPPORTED; no device:
+ * SDSP_HIP_ERR_NO_DEVICE.  Arguments are checked before a device is looked for.
+ */
+typedef struct sdsp_hip_cfar2d_plan sdsp_hip_cfar2d_plan;
+#define SDSP_HIP_CFAR2D_EDGE_MARK 0
+#define SDSP_HIP_CFAR2D_EDGE_CLIP 1
+#define SDSP_HIP_CFAR2D_MAX_R 64       /* train_r and guard_r, each */
+#define SDSP_HIP_CFAR2D_MAX_TRAIN_D 32
+#define SDSP_HIP_CFAR2D_MAX_GUARD_D 16
+#define SDSP_HIP_CFAR2D_MAX_D (1u << 20)
+typedef struct {
+    uint32_t train_d, guard_d, train_r, guard_r;
+    int edge;     /* SDSP_HIP_CFAR2D_EDGE_MARK or _CLIP */
+    int peak;     /* != 0: the 3 x 3 peak rule */
+    double alpha; /* c(r) = alpha / n(r); unused with a scale table */
+} sdsp_hip_cfar2d_desc;
+typedef struct {
+    uint32_t doppler, range;
+    float power, thr;
+} sdsp_hip_cfar2d_hit_f32; /* 16 bytes */
+typedef struct {
+    uint32_t doppler, range;
+    double power, thr;
+} sdsp_hip_cfar2d_hit_f64; /* 24 bytes */
+/* scale_or_null: R host doubles c(r) that replace alpha / n(r) */
+int sdsp_hip_cfar2d_plan_create(sdsp_hip_cfar2d_plan **plan, uint32_t D, uint32_t R, uint64_t max_maps, const sdsp_hip_cfar2d_desc *desc,
+                                const double *scale_or_null, int precision, int device);
+int sdsp_hip_cfar2d_plan_destroy(sdsp_hip_cfar2d_plan *plan);
+/* DEVICE pointers; hits: maps x cap records of the precision, counts: maps totals */
+int sdsp_hip_cfar2d_process(sdsp_hip_cfar2d_plan *plan, const void *p, void *thr, uint8_t *det, void *hits, uint32_t *counts, uint64_t cap,
+                            uint64_t maps, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_cfar2d_process_host(sdsp_hip_cfar2d_plan *plan, const void *host_p, void *host_thr, uint8_t *host_det, void *host_hits,
+                                 uint32_t *host_counts, uint64_t cap, uint64_t maps);
+/* a new alpha: c(r) = alpha / n(r) again (synchronous: it uploads the table; not for plans made with a scale table) */
+int sdsp_hip_cfar2d_plan_set_alpha(sdsp_hip_cfar2d_plan *plan, double alpha);
+/* kernel variants (the same bits): 0 = sdsp_cfar2d_kernel, tiles of tile_rows x 64 cells through LDS, the list by a scan of the
+ * per-(row, strip) counts and a placement launch; 1 = sdsp_cfar2d_plain_kernel, one thread per cell from global memory with plain
+ * loops in the contract's order, the list by a count, a sequential scan and a placement with one thread per row (the cross-check) */
+int sdsp_hip_cfar2d_plan_set_variant(sdsp_hip_cfar2d_plan *plan, int variant);
+/* kernel launches of one process of maps >= 1 maps: variant 0: 1, with a list 3; variant 1: 1 for thr / det plus 3 for a list */
+int sdsp_hip_cfar2d_plan_launches(const sdsp_hip_cfar2d_plan *plan, int with_thr_or_det, int with_hits, uint64_t *launches);
+typedef struct {
+    uint32_t D, R;
+    uint64_t max_maps;
+    uint32_t train_d, guard_d, train_r, guard_r;
+    uint32_t cells;             /* n(r) of an interior column: (2 Hd + 1)(2 Hr + 1) - (2 Gd + 1)(2 Gr + 1) */
+    int edge, peak, tabled, precision, device, variant;
+    double alpha;
+    uint32_t tile_rows, tile_cols; /* the cells one workgroup of the variant's kernel computes */
+    uint32_t threads;              /* of one workgroup */
+    uint32_t lds_bytes;            /* of one workgroup */
+    uint64_t workspace_bytes;      /* the list's workspace, allocated at creation */
+    char kernel[64];               /* the kernel the plan's variant runs */
+} sdsp_hip_cfar2d_plan_info;
+int sdsp_hip_cfar2d_plan_get_info(const sdsp_hip_cfar2d_plan *plan, sdsp_hip_cfar2d_plan_info *info);
+/* host designer: the constant-false-alarm table c(r) = pfa^(-1 / n(r)) - 1, r < R (the CA formula alpha_n / n for n independent
+ * exponential cells), for the clipped counts n(r); a column with n(r) = 0 gets +inf.  0 < pfa < 1, else SDSP_HIP_ERR_INVALID_ARG */
+int sdsp_hip_cfar2d_scale(uint32_t D, uint32_t R, const sdsp_hip_cfar2d_desc *desc, double pfa, double *scale);
+
 /* ------------------------------------------------------------------ carrier-recovery PLL / Costas loop banks */
 
 /*

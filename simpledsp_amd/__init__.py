@@ -14,6 +14,7 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    PLL_CROSS, PLL_BPSK, PLL_QPSK,
                    TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK,
                    FFT_COLS_COMPLEX, FFT_COLS_POWER,
+                   CFAR2D_EDGE_MARK, CFAR2D_EDGE_CLIP,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -37,6 +38,7 @@ from .beamformer import beamformer_bank, beam_delay_taps, plane_wave_delays
 from .lms import lms_bank
 from .rank_filter import rank_filter_bank, medfilt
 from .cfar import cfar_bank, cfar_alpha, cfar
+from .cfar2d import cfar2d_plan, cfar2d, cfar2d_scale, range_doppler_detect, Cfar2dHits, Cfar2dResult
 from .pll import pll_bank, pll_gains
 from .timing import timing_bank, timing_step, timing_max_out, timing_gains, timing_design
 

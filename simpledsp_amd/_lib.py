@@ -226,6 +226,23 @@ class CfarPlanInfo(C.Structure):
     ]
 
 
+class Cfar2dDesc(C.Structure):
+    _fields_ = [
+        ("train_d", C.c_uint32), ("guard_d", C.c_uint32), ("train_r", C.c_uint32), ("guard_r", C.c_uint32), ("edge", C.c_int),
+        ("peak", C.c_int), ("alpha", C.c_double),
+    ]
+
+
+class Cfar2dPlanInfo(C.Structure):
+    _fields_ = [
+        ("D", C.c_uint32), ("R", C.c_uint32), ("max_maps", C.c_uint64), ("train_d", C.c_uint32), ("guard_d", C.c_uint32),
+        ("train_r", C.c_uint32), ("guard_r", C.c_uint32), ("cells", C.c_uint32), ("edge", C.c_int), ("peak", C.c_int),
+        ("tabled", C.c_int), ("precision", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("alpha", C.c_double),
+        ("tile_rows", C.c_uint32), ("tile_cols", C.c_uint32), ("threads", C.c_uint32), ("lds_bytes", C.c_uint32),
+        ("workspace_bytes", C.c_uint64), ("kernel", C.c_char * 64),
+    ]
+
+
 class PllPlanInfo(C.Structure):
     _fields_ = [
         ("channels", C.c_uint64), ("block", C.c_uint32), ("waves", C.c_uint32), ("lds_bytes", C.c_uint32), ("max_dev", C.c_double),
@@ -247,6 +264,8 @@ PLL_CROSS, PLL_BPSK, PLL_QPSK = 0, 1, 2
 CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3
 CFAR_POWER, CFAR_IQ = 0, 1
 CFAR_MAX_TRAIN, CFAR_MAX_GUARD = 128, 255
+CFAR2D_EDGE_MARK, CFAR2D_EDGE_CLIP = 0, 1
+CFAR2D_MAX_R, CFAR2D_MAX_TRAIN_D, CFAR2D_MAX_GUARD_D, CFAR2D_MAX_D = 64, 32, 16, 1 << 20
 CIC_REAL, CIC_COMPLEX = 0, 1
 CIC_I16, CIC_I32 = 0, 1
 CIC_OUT_INT, CIC_OUT_F32 = 0, 1
@@ -510,6 +529,15 @@ SIGNATURES = {
     "sdsp_hip_cfar_plan_set_run": (_i, [_vp, _u64]),
     "sdsp_hip_cfar_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_cfar_plan_get_info": (_i, [_vp, C.POINTER(CfarPlanInfo)]),
+    "sdsp_hip_cfar2d_plan_create": (_i, [_pp, _u32, _u32, _u64, C.POINTER(Cfar2dDesc), _vp, _i, _i]),
+    "sdsp_hip_cfar2d_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_cfar2d_process": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_cfar2d_process_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64]),
+    "sdsp_hip_cfar2d_plan_set_alpha": (_i, [_vp, _d]),
+    "sdsp_hip_cfar2d_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_cfar2d_plan_launches": (_i, [_vp, _i, _i, C.POINTER(_u64)]),
+    "sdsp_hip_cfar2d_plan_get_info": (_i, [_vp, C.POINTER(Cfar2dPlanInfo)]),
+    "sdsp_hip_cfar2d_scale": (_i, [_u32, _u32, C.POINTER(Cfar2dDesc), _d, _vp]),
     "sdsp_hip_pll_oscillator": (_i, [_vp, _vp]),
     "sdsp_hip_pll_gains": (_i, [_d, _d, _d, _i, C.POINTER(_d), C.POINTER(_d)]),
     "sdsp_hip_pll_plan_create": (_i, [_pp, _u64, _i, _i, C.POINTER(_u32), _u64, _d, _i]),

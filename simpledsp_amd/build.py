@@ -56,6 +56,7 @@ SOURCES = {
     "lms.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip; no fast-math either: the NLMS step divides with a correctly rounded `/`
     "rank_filter.hip": [],  # compare-and-select on integer keys only: there is no arithmetic to pin
     "cfar.hip": ["-ffp-contract=off"],  # the I/Q power as stft.hip's; thr = fl(fl(lag + lead) c): a sum then a product, never an FMA
+    "cfar2d.hip": ["-ffp-contract=off"],  # as cfar.hip: sums then one product, never an FMA
     "pll.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: the complex products and the f64 loop filter never contract; no fast-math
     "timing.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as pll.hip: the f64 taps, detector and loop filter never contract; no fast-math
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass, fft_cols), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, pll, timing) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -564,6 +564,17 @@ struct sdsp_hip_fft_cols_plan {
     int direction = 0, precision = 0, output = 0, shift = 0, device = 0, variant = 0;
     void *tw = nullptr;     // device: W_n^j, j < n, direction-folded, plan precision
     void *window = nullptr; // device: n reals of the plan precision, or null
+};
+
+struct sdsp_hip_cfar2d_plan {
+    uint32_t D = 0, R = 0;
+    uint64_t max_maps = 0;
+    sdsp_hip_cfar2d_desc desc{};
+    int tabled = 0, precision = 0, device = 0, variant = 0;
+    void *scale = nullptr;   // device: c(r), R reals of the plan precision
+    void *ws_mask = nullptr; // device: the list's workspace (cfar2d_workspace)
+    void *ws_cnt = nullptr;
+    uint64_t ws_bytes = 0;
 };
 
 struct sdsp_hip_arb_plan {
@@ -7018,6 +7029,298 @@ int sdsp_hip_fft_cols_plan_get_info(const sdsp_hip_fft_cols_plan *p, sdsp_hip_ff
     info->lds_bytes = s.lds_bytes;
     info->algorithmic_bytes = static_cast<uint64_t>(p->n) * p->width * (esize(p->precision) + fft_cols_out_esize(p));
     std::strncpy(info->kernel, fft_cols_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+// ------------------------------------------------------------------ 2-D CFAR plans (cfar2d.hip)
+
+namespace
+{
+constexpr uint64_t kCfar2dMaxCells = 1ull << 40;
+
+// the window and the map sizes of a descriptor, without a device
+int cfar2d_check_shape(uint32_t D, uint32_t R, const sdsp_hip_cfar2d_desc *d)
+{
+    if (!d)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "descriptor is null");
+    if (d->train_r > SDSP_HIP_CFAR2D_MAX_R || d->guard_r > SDSP_HIP_CFAR2D_MAX_R)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "train_r and guard_r must be at most SDSP_HIP_CFAR2D_MAX_R");
+    if (d->train_d > SDSP_HIP_CFAR2D_MAX_TRAIN_D || d->guard_d > SDSP_HIP_CFAR2D_MAX_GUARD_D)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "train_d must be at most SDSP_HIP_CFAR2D_MAX_TRAIN_D, guard_d at most SDSP_HIP_CFAR2D_MAX_GUARD_D");
+    if (d->train_d + d->train_r == 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "train_d + train_r must be at least 1");
+    if (D < 2 * (d->train_d + d->guard_d) + 1 || D > SDSP_HIP_CFAR2D_MAX_D)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "D must be in [2 (train_d + guard_d) + 1, SDSP_HIP_CFAR2D_MAX_D]");
+    if (R == 0 || R >= (1u << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "R must be in [1, 2^31)");
+    if (d->edge != SDSP_HIP_CFAR2D_EDGE_MARK && d->edge != SDSP_HIP_CFAR2D_EDGE_CLIP)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "edge must be SDSP_HIP_CFAR2D_EDGE_MARK or SDSP_HIP_CFAR2D_EDGE_CLIP");
+    return SDSP_HIP_OK;
+}
+
+// n(r): the training cells of column r that lie inside the map
+uint64_t cfar2d_cells(uint32_t R, const sdsp_hip_cfar2d_desc *d, uint32_t r)
+{
+    auto inside = [&](int64_t half) { return std::min<int64_t>(r + half, static_cast<int64_t>(R) - 1) - std::max<int64_t>(r - half, 0) + 1; };
+    const int64_t Hd = d->train_d + d->guard_d, Hr = d->train_r + d->guard_r;
+    return static_cast<uint64_t>((2 * Hd + 1) * inside(Hr) - (2 * int64_t(d->guard_d) + 1) * inside(d->guard_r));
+}
+
+int cfar2d_upload_alpha(sdsp_hip_cfar2d_plan *p, double alpha)
+{
+    std::vector<double> c(p->R);
+    for (uint32_t r = 0; r < p->R; r++)
+        c[r] = alpha / static_cast<double>(cfar2d_cells(p->R, &p->desc, r));
+    if (!p->scale)
+        return upload_reals(c.data(), c.size(), p->precision, &p->scale) == hipSuccess ? SDSP_HIP_OK : fail(SDSP_HIP_ERR_NOMEM, "cfar2d plan: the scale table");
+    if (p->precision == SDSP_HIP_F64) {
+        HIP_TRY(hipMemcpy(p->scale, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+        const std::vector<float> f(c.begin(), c.end());
+        HIP_TRY(hipMemcpy(p->scale, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return SDSP_HIP_OK;
+}
+
+size_t cfar2d_record(int precision) { return precision == SDSP_HIP_F64 ? sizeof(sdsp_hip_cfar2d_hit_f64) : sizeof(sdsp_hip_cfar2d_hit_f32); }
+
+// argument checks shared by process and process_host (device pointers or not)
+int cfar2d_check(const sdsp_hip_cfar2d_plan *p, const void *in, const void *thr, const void *det, const void *hits, const void *counts,
+                 uint64_t cap, uint64_t maps)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (maps > p->max_maps)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "maps must be at most the plan's max_maps");
+    if (cap >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "cap must be below 2^31");
+    if (maps == 0)
+        return SDSP_HIP_OK;
+    if (!in)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "p is null");
+    if (!thr && !det && !hits && !counts)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "every output is null");
+    if (!hits != !counts)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "hits and counts go together");
+    const uint64_t rs = real_size(p->precision), cells = maps * p->D * p->R;
+    if (misaligned(in, rs) || misaligned(thr, rs) || misaligned(hits, rs) || misaligned(counts, 4))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "p, thr, hits and counts must be aligned to their element size");
+    const void *ptr[5] = { in, thr, det, hits, counts };
+    const uint64_t bytes[5] = { cells * rs, cells * rs, cells, maps * cap * cfar2d_record(p->precision), maps * 4 };
+    for (int i = 0; i < 5; i++)
+        for (int j = i + 1; j < 5; j++)
+            if (ranges_overlap(ptr[i], bytes[i], ptr[j], bytes[j]))
+                return fail(SDSP_HIP_ERR_INVALID_ARG, "the input and the outputs must not overlap one another");
+    return SDSP_HIP_OK;
+}
+
+cfar2d_args cfar2d_args_of(const sdsp_hip_cfar2d_plan *p, const void *in, void *thr, uint8_t *det, void *hits, uint32_t *counts, uint64_t cap,
+                           uint64_t maps)
+{
+    cfar2d_args a{};
+    a.p = in;
+    a.thr = thr;
+    a.det = det;
+    a.hits = hits;
+    a.counts = counts;
+    a.scale = p->scale;
+    a.ws_mask = p->ws_mask;
+    a.ws_cnt = static_cast<uint32_t *>(p->ws_cnt);
+    a.maps = maps;
+    a.cap = cap;
+    a.D = p->D;
+    a.R = p->R;
+    a.Ld = p->desc.train_d;
+    a.Gd = p->desc.guard_d;
+    a.Lr = p->desc.train_r;
+    a.Gr = p->desc.guard_r;
+    a.clip = p->desc.edge == SDSP_HIP_CFAR2D_EDGE_CLIP;
+    a.peak = p->desc.peak != 0;
+    return a;
+}
+} // namespace
+
+int sdsp_hip_cfar2d_scale(uint32_t D, uint32_t R, const sdsp_hip_cfar2d_desc *d, double pfa, double *scale)
+{
+    if (int rc = cfar2d_check_shape(D, R, d))
+        return rc;
+    if (!scale || !(pfa > 0.0 && pfa < 1.0))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scale must not be null and pfa must lie in (0, 1)");
+    for (uint32_t r = 0; r < R; r++) {
+        const uint64_t n = cfar2d_cells(R, d, r);
+        scale[r] = n ? std::pow(pfa, -1.0 / static_cast<double>(n)) - 1.0 : HUGE_VAL;
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar2d_plan_create(sdsp_hip_cfar2d_plan **out, uint32_t D, uint32_t R, uint64_t max_maps, const sdsp_hip_cfar2d_desc *d,
+                                const double *scale, int precision, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (int rc = cfar2d_check_shape(D, R, d))
+        return rc;
+    if (max_maps == 0 || max_maps >= kCfar2dMaxCells || max_maps * D >= kCfar2dMaxCells || max_maps * D * R >= kCfar2dMaxCells)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "max_maps must be at least 1 with max_maps D R below 2^40");
+    if (precision != SDSP_HIP_F32 && precision != SDSP_HIP_F64)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "precision must be SDSP_HIP_F32 or SDSP_HIP_F64");
+    if (scale)
+        for (uint32_t r = 0; r < R; r++) {
+            const double c = precision == SDSP_HIP_F64 ? scale[r] : static_cast<double>(static_cast<float>(scale[r]));
+            if (!std::isfinite(c))
+                return fail(SDSP_HIP_ERR_INVALID_ARG, "scale values must be finite once rounded to the precision");
+        }
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_cfar2d_plan();
+    p->D = D;
+    p->R = R;
+    p->max_maps = max_maps;
+    p->desc = *d;
+    p->desc.peak = d->peak != 0;
+    p->tabled = scale != nullptr;
+    p->precision = precision;
+    p->device = device;
+    int rc = SDSP_HIP_OK;
+    if (scale) {
+        const hipError_t e = upload_reals(scale, R, precision, &p->scale);
+        if (e != hipSuccess)
+            rc = plan_fail(e, "cfar2d");
+    } else {
+        rc = cfar2d_upload_alpha(p, d->alpha);
+    }
+    if (!rc) {
+        uint64_t mask_bytes = 0, cnt_bytes = 0;
+        cfar2d_workspace(D, R, max_maps, &mask_bytes, &cnt_bytes);
+        p->ws_bytes = mask_bytes + cnt_bytes;
+        hipError_t e = hipMalloc(&p->ws_mask, mask_bytes);
+        if (e == hipSuccess)
+            e = hipMalloc(&p->ws_cnt, cnt_bytes);
+        if (e != hipSuccess)
+            rc = plan_fail(e, "cfar2d");
+    }
+    if (!rc) // the kernel's dynamic-LDS limit, so that process sets no attribute (it may be captured)
+        rc = launch_cfar2d(precision, cfar2d_args{}, 0, nullptr);
+    if (rc) {
+        sdsp_hip_cfar2d_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar2d_plan_destroy(sdsp_hip_cfar2d_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->scale);
+        (void)hipFree(p->ws_mask);
+        (void)hipFree(p->ws_cnt);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar2d_process(sdsp_hip_cfar2d_plan *p, const void *in, void *thr, uint8_t *det, void *hits, uint32_t *counts, uint64_t cap,
+                            uint64_t maps, void *stream)
+{
+    if (int rc = cfar2d_check(p, in, thr, det, hits, counts, cap, maps))
+        return rc;
+    if (maps == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    return launch_cfar2d(p->precision, cfar2d_args_of(p, in, thr, det, hits, counts, cap, maps), p->variant, stream);
+}
+
+int sdsp_hip_cfar2d_process_host(sdsp_hip_cfar2d_plan *p, const void *host_p, void *host_thr, uint8_t *host_det, void *host_hits,
+                                 uint32_t *host_counts, uint64_t cap, uint64_t maps)
+{
+    if (int rc = cfar2d_check(p, host_p, host_thr, host_det, host_hits, host_counts, cap, maps))
+        return rc;
+    if (maps == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t rs = real_size(p->precision), cells = static_cast<size_t>(maps * p->D * p->R);
+    const size_t list_bytes = static_cast<size_t>(maps * cap) * cfar2d_record(p->precision);
+    // a list of cap == 0 has no bytes to stage: the kernels still need a pointer that says "with a list", and write nothing through it
+    host_stage st("cfar2d", { { host_p, cells * rs, false }, { host_thr, cells * rs, true }, { host_det, cells, true },
+                          { list_bytes ? host_hits : nullptr, list_bytes, true }, { host_counts, static_cast<size_t>(maps) * 4, true } });
+    int rc = st.in();
+    if (!rc) {
+        void *hits = host_hits && !list_bytes ? p->ws_mask : st.dev[3];
+        rc = launch_cfar2d(p->precision,
+                           cfar2d_args_of(p, st.dev[0], st.dev[1], static_cast<uint8_t *>(st.dev[2]), hits, static_cast<uint32_t *>(st.dev[4]), cap, maps),
+                           p->variant, nullptr);
+    }
+    if (!rc) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = hip_fail(e, "cfar2d process_host");
+    }
+    return st.out(rc);
+}
+
+int sdsp_hip_cfar2d_plan_set_alpha(sdsp_hip_cfar2d_plan *p, double alpha)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (p->tabled)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the plan was made with a scale table");
+    if (int rc = use_device(p->device))
+        return rc;
+    if (int rc = cfar2d_upload_alpha(p, alpha))
+        return rc;
+    p->desc.alpha = alpha;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar2d_plan_set_variant(sdsp_hip_cfar2d_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar2d_plan_launches(const sdsp_hip_cfar2d_plan *p, int with_thr_or_det, int with_hits, uint64_t *launches)
+{
+    if (!p || !launches || (!with_thr_or_det && !with_hits))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument, or no output");
+    *launches = cfar2d_launches(p->variant, with_thr_or_det != 0, with_hits != 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_cfar2d_plan_get_info(const sdsp_hip_cfar2d_plan *p, sdsp_hip_cfar2d_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const sdsp_hip_cfar2d_desc &d = p->desc;
+    const cfar2d_shape s = cfar2d_shape_for(p->precision, p->D, d.train_d, d.guard_d, d.train_r, d.guard_r, p->variant);
+    info->D = p->D;
+    info->R = p->R;
+    info->max_maps = p->max_maps;
+    info->train_d = d.train_d;
+    info->guard_d = d.guard_d;
+    info->train_r = d.train_r;
+    info->guard_r = d.guard_r;
+    info->cells = (2 * (d.train_d + d.guard_d) + 1) * (2 * (d.train_r + d.guard_r) + 1) - (2 * d.guard_d + 1) * (2 * d.guard_r + 1);
+    info->edge = d.edge;
+    info->peak = d.peak;
+    info->tabled = p->tabled;
+    info->precision = p->precision;
+    info->device = p->device;
+    info->variant = p->variant;
+    info->alpha = d.alpha;
+    info->tile_rows = s.tile_rows;
+    info->tile_cols = s.tile_cols;
+    info->threads = s.threads;
+    info->lds_bytes = s.lds_bytes;
+    info->workspace_bytes = p->ws_bytes;
+    std::strncpy(info->kernel, cfar2d_kernel_for(p->variant), sizeof(info->kernel) - 1);
     return SDSP_HIP_OK;
 }
 }

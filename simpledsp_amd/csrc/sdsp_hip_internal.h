@@ -514,6 +514,28 @@ struct fft_cols_shape {
 fft_cols_shape fft_cols_shape_for(int precision, uint32_t n, int variant);
 uint64_t fft_cols_launches(int precision, uint32_t n, uint64_t width, uint64_t batch, int variant);
 const char *fft_cols_kernel_for(int variant);
+// 2-D CFAR plans (cfar2d.hip): the launches of one call over compact maps [maps][D][R]
+struct cfar2d_args {
+    const void *p;       // null: launch nothing, only prepare the kernel (its dynamic-LDS limit) on the current device
+    void *thr;           // nullable
+    uint8_t *det;        // nullable
+    void *hits;          // nullable: maps x cap records of the precision
+    uint32_t *counts;    // with hits: maps totals
+    const void *scale;   // device: R values c(r) of the plan precision
+    void *ws_mask;       // the plan's workspace (cfar2d_workspace)
+    uint32_t *ws_cnt;
+    uint64_t maps, cap;
+    uint32_t D, R, Ld, Gd, Lr, Gr;
+    int clip, peak;
+};
+int launch_cfar2d(int precision, const cfar2d_args &a, int variant, void *stream);
+struct cfar2d_shape {
+    uint32_t tile_rows, tile_cols, threads, lds_bytes;
+};
+cfar2d_shape cfar2d_shape_for(int precision, uint32_t D, uint32_t Ld, uint32_t Gd, uint32_t Lr, uint32_t Gr, int variant);
+void cfar2d_workspace(uint32_t D, uint32_t R, uint64_t max_maps, uint64_t *mask_bytes, uint64_t *cnt_bytes);
+uint64_t cfar2d_launches(int variant, bool maps_out, bool list);
+const char *cfar2d_kernel_for(int variant);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
