@@ -2132,6 +2132,106 @@ typedef struct {
 } sdsp_hip_timing_plan_info;
 int sdsp_hip_timing_plan_get_info(const sdsp_hip_timing_plan *plan, sdsp_hip_timing_plan_info *info);
 
+/*
+ * ---- streaming Viterbi decoder banks for convolutional codes (viterbi.hip) ----
+ *
+ * A bank of soft-decision Viterbi decoders for one rate-1/n convolutional code: `channels` compact rows of steps n soft values in,
+ * `steps` decoded bits per row out, the decoder state carried from call to call.  Every operation is on integers: both kernel
+ * variants and tests/viterbi_ref.py give the same bits and the same state, with no tolerance.
+ * Code: constraint length K = 3 .. 9, n = 2 or 3 generators, each a K-bit integer in the usual octal convention: the most significant
+ * bit multiplies the newest input bit (K = 7: 0171, 0133).  The state s holds the last K - 1 input bits, the newest in bit 0: input b
+ * takes s to s' = ((s << 1) | b) mod S with S = 2^(K-1), and the predecessors of s' are p0 = s' >> 1 and p1 = p0 + S / 2.
+ * Input: row c starts at in + c steps n elements (no stride: the row length is the row distance); the n values of a step are
+ * adjacent.  I8: int8, positive favours coded bit 0, -128 is read as -127, 0 is an erasure (a punctured position).  F32: quantised on
+ * the way in as q = clamp(rint(fl32(x scale)), -127, 127) with the plan's float `scale`, ties to even, NaN becomes 0.
+ * Metrics: path metrics are 32-bit integers that wrap.  The branch from p to s' with coded bits c_j has the metric
+ * sum_j (c_j ? -q_j : +q_j); a0 = m[p0] + bm0, a1 = m[p1] + bm1, d = 1 iff (int32)(a1 - a0) > 0 (a tie takes p0), m'[s'] = d ? a1 : a0.
+ * Nothing is ever normalised: the spread stays at or below (K - 1) n 254, so the comparison modulo 2^32 is exact.  The best state of a
+ * step is the lowest s with the largest (int32)(m[s] - m[0]).  A fresh stream has every metric 0, or with a known start state s0
+ * m[s0] = 0 and every other metric -2^20.
+ * Traceback: the plan fixes a block B (a multiple of 32, 32 .. 1024) and a depth D (K - 1 .. 4096); Dr = B ceil(D / B).  Every call
+ * takes a multiple of B steps, so blocks are aligned to the start of the stream whatever its split into calls.  Block m covers steps
+ * [m B, (m + 1) B) and is decided when step e = (m + 1) B - 1 + D has been processed: from the best state of step e walk back D steps
+ * and drop them, then walk back B steps and emit them, with s_{t-1} = (s_t >> 1) + d_t[s_t] S / 2 and the bit of step t = bit 0 of
+ * s_t.  A call writes `steps` outputs per row: out[t] is the bit of stream step (start of the call + t - Dr); the first Dr outputs of
+ * a stream are 0.
+ * Output: BYTES: one 0 / 1 byte per bit, row c at out + c steps.  PACKED: uint32 words, least significant bit first, steps / 32 words
+ * per row.
+ * State: one plan-owned device buffer of sdsp_hip_viterbi_plan_state_bytes, for max_channels channels, in this order: the metrics
+ * (max_channels x S int32), the count of steps held (max_channels uint32, at most Dr: outputs in front of it are the zeros of the
+ * stream's start), padding to 8 bytes, the decisions (max_channels x Dr x W uint64 with W = max(1, S / 64), oldest step first; bit
+ * s % 64 of word s / 64 is d[s]).  Both kernels read it at entry and write it at exit, so a stream may change variant between calls;
+ * any split of a stream into calls gives the same bits and the same final state.  process touches the first `channels` channels only.
+ * Limits: 1 <= max_channels < 2^31, steps < 2^31.
+ */
+#define SDSP_HIP_VITERBI_I8 0
+#define SDSP_HIP_VITERBI_F32 1
+#define SDSP_HIP_VITERBI_BYTES 0
+#define SDSP_HIP_VITERBI_PACKED 1
+#define SDSP_HIP_VITERBI_MIN_K 3
+#define SDSP_HIP_VITERBI_MAX_K 9
+#define SDSP_HIP_VITERBI_MAX_BLOCK 1024
+#define SDSP_HIP_VITERBI_MAX_DEPTH 4096
+#define SDSP_HIP_VITERBI_START_METRIC (-(1 << 20))
+typedef struct sdsp_hip_viterbi_plan sdsp_hip_viterbi_plan;
+/* host helper: Dr = block ceil(depth / block), the delay in steps between a row's input and its output.  Errors: a null pointer:
+ * SDSP_HIP_ERR_INVALID_ARG; block not a multiple of 32 in [32, 1024] or depth outside [1, 4096]: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_viterbi_delay(uint32_t block, uint32_t depth, uint32_t *delay);
+/* host helper: the encoder of the code above from state 0.  bits: nbits bytes (non-zero counts as 1); with `terminate` K - 1 zero bits
+ * follow them; out receives n coded bits (0 / 1 bytes) per input bit, generator 0 first.  Errors: k or n out of range:
+ * SDSP_HIP_ERR_INVALID_SIZE; a null pointer (bits may be null with nbits == 0), a generator of 0 or >= 2^k: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_conv_encode(uint32_t k, uint32_t n, const uint32_t *generators, const uint8_t *bits, uint64_t nbits, int terminate, uint8_t *out);
+/* generators: n HOST values.  scale is read by F32 plans only and must then be finite and > 0.  The plan starts as after
+ * sdsp_hip_viterbi_plan_reset(plan, -1), in variant 0 where K = 7 and in variant 1 elsewhere.  Errors: k, n, block, depth or
+ * max_channels out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an unknown kind, a generator of 0 or >= 2^k, a bad scale:
+ * SDSP_HIP_ERR_INVALID_ARG; no device: SDSP_HIP_ERR_NO_DEVICE; no memory for the state: SDSP_HIP_ERR_NOMEM. */
+int sdsp_hip_viterbi_plan_create(sdsp_hip_viterbi_plan **plan, uint32_t k, uint32_t n, const uint32_t *generators, uint32_t block,
+                                 uint32_t depth, int in_kind, int out_kind, float scale, uint64_t max_channels, int device);
+int sdsp_hip_viterbi_plan_destroy(sdsp_hip_viterbi_plan *plan);
+/*
+ * in, out: DEVICE pointers, aligned to their element (F32: 4 bytes, PACKED: 4 bytes; I8 and BYTES: any byte).  Asynchronous on
+ * `stream`, one plain launch, allocates nothing (stream-capturable); one call per plan in flight.  Errors: steps not a multiple of the
+ * block, steps >= 2^31, channels above max_channels: SDSP_HIP_ERR_INVALID_SIZE; null plan, null in or out with work to do, a
+ * misaligned pointer, in overlapping out, in or out overlapping the state: SDSP_HIP_ERR_INVALID_ARG.  channels == 0 or steps == 0:
+ * nothing to do, nothing is touched.
+ */
+int sdsp_hip_viterbi_process(sdsp_hip_viterbi_plan *plan, const void *in, void *out, uint64_t channels, uint64_t steps, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_viterbi_process_host(sdsp_hip_viterbi_plan *plan, const void *host_in, void *host_out, uint64_t channels, uint64_t steps);
+/* a fresh stream in every channel: no steps held, and every metric 0 (start_state == -1) or the known start state 0 <= start_state < S.
+ * Synchronous.  Errors: any other start_state: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_viterbi_plan_reset(sdsp_hip_viterbi_plan *plan, int start_state);
+/* the metrics of the first `channels` channels, channels x S int32, to or from HOST memory; synchronous.  set_metrics leaves the
+ * decisions held alone.  Errors: null pointers: SDSP_HIP_ERR_INVALID_ARG; channels above max_channels: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_viterbi_plan_get_metrics(sdsp_hip_viterbi_plan *plan, int32_t *host_metrics, uint64_t channels);
+int sdsp_hip_viterbi_plan_set_metrics(sdsp_hip_viterbi_plan *plan, const int32_t *host_metrics, uint64_t channels);
+/* bytes of the plan's state buffer (the layout above) */
+int sdsp_hip_viterbi_plan_state_bytes(const sdsp_hip_viterbi_plan *plan, uint64_t *bytes);
+/* kernel variants (identical bits, one state layout): 0 = sdsp_viterbi_wave_kernel, K = 7 only (a wave per channel, lane = state, the
+ * metrics exchanged by ds_bpermute, a step's decisions one ballot word in an LDS ring, the tracebacks of a chunk side by side on the
+ * lanes); 1 = sdsp_viterbi_plain_kernel, every K (a workgroup of S threads per channel, the metrics in LDS with a barrier per step).
+ * Errors: variant 0 where K != 7: SDSP_HIP_ERR_UNSUPPORTED; any other value: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_viterbi_plan_set_variant(sdsp_hip_viterbi_plan *plan, int variant);
+/* kernel launches of one process call: 1; 0 for channels == 0 or steps == 0 */
+int sdsp_hip_viterbi_plan_launches(const sdsp_hip_viterbi_plan *plan, uint64_t channels, uint64_t steps, uint64_t *launches);
+typedef struct {
+    uint32_t k, n, generators[3];
+    uint32_t states;      /* S = 2^(k-1) */
+    uint32_t block, depth;
+    uint32_t delay;       /* Dr */
+    uint32_t chunk;       /* steps between two rounds of tracebacks in the variant's kernel: a multiple of block */
+    uint32_t threads;     /* per workgroup */
+    uint32_t waves;       /* variant 0: channels per workgroup */
+    uint32_t lds_bytes;   /* dynamic LDS of one workgroup */
+    uint32_t ring_in_lds; /* 0: the plain kernel's decision ring lies in a plan-owned buffer in global memory */
+    uint64_t max_channels;
+    uint64_t state_bytes;
+    float scale;
+    int in_kind, out_kind, device, variant;
+    char kernel[64];      /* the kernel the plan's variant runs */
+} sdsp_hip_viterbi_plan_info;
+int sdsp_hip_viterbi_plan_get_info(const sdsp_hip_viterbi_plan *plan, sdsp_hip_viterbi_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

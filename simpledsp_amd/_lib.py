@@ -258,7 +258,20 @@ class TimingPlanInfo(C.Structure):
     ]
 
 
+class ViterbiPlanInfo(C.Structure):
+    _fields_ = [
+        ("k", C.c_uint32), ("n", C.c_uint32), ("generators", C.c_uint32 * 3), ("states", C.c_uint32), ("block", C.c_uint32),
+        ("depth", C.c_uint32), ("delay", C.c_uint32), ("chunk", C.c_uint32), ("threads", C.c_uint32), ("waves", C.c_uint32),
+        ("lds_bytes", C.c_uint32), ("ring_in_lds", C.c_uint32), ("max_channels", C.c_uint64), ("state_bytes", C.c_uint64),
+        ("scale", C.c_float), ("in_kind", C.c_int), ("out_kind", C.c_int), ("device", C.c_int), ("variant", C.c_int),
+        ("kernel", C.c_char * 64),
+    ]
+
+
 TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK = 0, 1, 2
+VITERBI_I8, VITERBI_F32 = 0, 1
+VITERBI_BYTES, VITERBI_PACKED = 0, 1
+VITERBI_MIN_K, VITERBI_MAX_K, VITERBI_MAX_BLOCK, VITERBI_MAX_DEPTH, VITERBI_START_METRIC = 3, 9, 1024, 4096, -(1 << 20)
 TIMING_MAX_PHASES, TIMING_MAX_TAPS, TIMING_MAX_TABLE = 128, 64, 4096
 PLL_CROSS, PLL_BPSK, PLL_QPSK = 0, 1, 2
 CFAR_CA, CFAR_GO, CFAR_SO, CFAR_OS = 0, 1, 2, 3
@@ -561,6 +574,19 @@ SIGNATURES = {
     "sdsp_hip_timing_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_timing_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_timing_plan_get_info": (_i, [_vp, C.POINTER(TimingPlanInfo)]),
+    "sdsp_hip_viterbi_delay": (_i, [_u32, _u32, C.POINTER(_u32)]),
+    "sdsp_hip_conv_encode": (_i, [_u32, _u32, C.POINTER(_u32), _vp, _u64, _i, _vp]),
+    "sdsp_hip_viterbi_plan_create": (_i, [_pp, _u32, _u32, C.POINTER(_u32), _u32, _u32, _i, _i, C.c_float, _u64, _i]),
+    "sdsp_hip_viterbi_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_viterbi_process": (_i, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_viterbi_process_host": (_i, [_vp, _vp, _vp, _u64, _u64]),
+    "sdsp_hip_viterbi_plan_reset": (_i, [_vp, _i]),
+    "sdsp_hip_viterbi_plan_get_metrics": (_i, [_vp, _vp, _u64]),
+    "sdsp_hip_viterbi_plan_set_metrics": (_i, [_vp, _vp, _u64]),
+    "sdsp_hip_viterbi_plan_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_viterbi_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_viterbi_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_viterbi_plan_get_info": (_i, [_vp, C.POINTER(ViterbiPlanInfo)]),
 }
 
 _lib = None

@@ -59,6 +59,7 @@ SOURCES = {
     "cfar2d.hip": ["-ffp-contract=off"],  # as cfar.hip: sums then one product, never an FMA
     "pll.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as ddc.hip: the complex products and the f64 loop filter never contract; no fast-math
     "timing.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],  # as pll.hip: the f64 taps, detector and loop filter never contract; no fast-math
+    "viterbi.hip": [],  # integers throughout; the one float step is the product of the F32 quantiser, with nothing to contract
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA

@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass, fft_cols), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing, viterbi) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -547,6 +547,16 @@ struct sdsp_hip_pll_plan {
     uint32_t *fcw0 = nullptr;  // device: channels centre-frequency words
     void *osc = nullptr;       // device: the tables C then F, 2 x 2048 complex values of the precision
     void *scratch = nullptr;   // a state buffer for the plain kernel of a call without state; made by set_variant(1)
+};
+
+struct sdsp_hip_viterbi_plan {
+    uint32_t k = 0, n = 0, generators[3] = {}, block = 0, depth = 0, dr = 0;
+    int in_kind = 0, out_kind = 0, device = 0, variant = 0;
+    float scale = 1.0f;
+    uint64_t max_channels = 0, state_bytes = 0;
+    void *state = nullptr;   // device: metrics, counts, decisions (the layout of sdsp_hip.h)
+    void *ring_ws = nullptr; // device: the plain kernel's ring where it does not fit LDS
+    uint64_t ring_bytes = 0;
 };
 
 struct sdsp_hip_timing_plan {
@@ -7321,6 +7331,339 @@ int sdsp_hip_cfar2d_plan_get_info(const sdsp_hip_cfar2d_plan *p, sdsp_hip_cfar2d
     info->lds_bytes = s.lds_bytes;
     info->workspace_bytes = p->ws_bytes;
     std::strncpy(info->kernel, cfar2d_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+// ------------------------------------------------------------------ Viterbi decoder banks (viterbi.hip)
+
+namespace
+{
+// the code of a plan or of the encoder, without a device
+int viterbi_check_code(uint32_t k, uint32_t n, const uint32_t *generators)
+{
+    if (k < SDSP_HIP_VITERBI_MIN_K || k > SDSP_HIP_VITERBI_MAX_K)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "k must be in [3, 9]");
+    if (n < 2 || n > 3)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n must be 2 or 3");
+    if (!generators)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "generators is null");
+    for (uint32_t j = 0; j < n; j++)
+        if (generators[j] == 0 || generators[j] >= (1u << k))
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "every generator must be in [1, 2^k)");
+    return SDSP_HIP_OK;
+}
+
+int viterbi_check_traceback(uint32_t block, uint32_t depth, uint32_t min_depth)
+{
+    if (block < 32 || block > SDSP_HIP_VITERBI_MAX_BLOCK || block % 32 != 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "block must be a multiple of 32 in [32, 1024]");
+    if (depth < min_depth || depth > SDSP_HIP_VITERBI_MAX_DEPTH)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "depth must be in [k - 1, 4096]");
+    return SDSP_HIP_OK;
+}
+
+struct viterbi_layout {
+    uint64_t filled_off, hist_off, bytes;
+};
+viterbi_layout viterbi_layout_of(uint32_t k, uint32_t dr, uint64_t max_channels)
+{
+    const uint64_t S = 1ull << (k - 1), W = S > 64 ? S / 64 : 1;
+    viterbi_layout l{};
+    l.filled_off = max_channels * S * 4;
+    l.hist_off = (l.filled_off + max_channels * 4 + 7) / 8 * 8;
+    l.bytes = l.hist_off + max_channels * dr * W * 8;
+    return l;
+}
+
+size_t viterbi_in_size(const sdsp_hip_viterbi_plan *p) { return p->in_kind == SDSP_HIP_VITERBI_F32 ? 4 : 1; }
+// bytes of a row of `steps` outputs
+uint64_t viterbi_out_row(const sdsp_hip_viterbi_plan *p, uint64_t steps) { return p->out_kind == SDSP_HIP_VITERBI_PACKED ? steps / 8 : steps; }
+
+// argument checks shared by process and process_host (device pointers or not)
+int viterbi_check(const sdsp_hip_viterbi_plan *p, const void *in, const void *out, uint64_t channels, uint64_t steps, bool device_ptrs)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (channels > p->max_channels)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be at most the plan's max_channels");
+    if (steps >= (1ull << 31) || steps % p->block != 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "steps must be a multiple of the plan's block, below 2^31");
+    if (channels == 0 || steps == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must not be null");
+    if (misaligned(in, viterbi_in_size(p)) || misaligned(out, p->out_kind == SDSP_HIP_VITERBI_PACKED ? 4 : 1))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must be aligned to their element size");
+    const uint64_t in_bytes = channels * steps * p->n * viterbi_in_size(p), out_bytes = channels * viterbi_out_row(p, steps);
+    if (ranges_overlap(in, in_bytes, out, out_bytes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must not overlap");
+    if (device_ptrs && (ranges_overlap(in, in_bytes, p->state, p->state_bytes) || ranges_overlap(out, out_bytes, p->state, p->state_bytes)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must not overlap the plan's state");
+    return SDSP_HIP_OK;
+}
+
+viterbi_args viterbi_args_of(const sdsp_hip_viterbi_plan *p, const void *in, void *out, uint64_t channels, uint64_t steps)
+{
+    const viterbi_layout l = viterbi_layout_of(p->k, p->dr, p->max_channels);
+    char *s = static_cast<char *>(p->state);
+    viterbi_args a{};
+    a.in = in;
+    a.out = out;
+    a.metrics = reinterpret_cast<uint32_t *>(s);
+    a.filled = reinterpret_cast<uint32_t *>(s + l.filled_off);
+    a.hist = reinterpret_cast<uint64_t *>(s + l.hist_off);
+    a.ring_ws = static_cast<uint64_t *>(p->ring_ws);
+    a.channels = channels;
+    a.steps = steps;
+    a.k = p->k;
+    a.n = p->n;
+    for (uint32_t j = 0; j < p->n; j++)
+        a.generators[j] = p->generators[j];
+    a.block = p->block;
+    a.depth = p->depth;
+    a.dr = p->dr;
+    a.in_kind = p->in_kind;
+    a.out_kind = p->out_kind;
+    a.scale = p->scale;
+    return a;
+}
+} // namespace
+
+int sdsp_hip_viterbi_delay(uint32_t block, uint32_t depth, uint32_t *delay)
+{
+    if (!delay)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "delay is null");
+    if (int rc = viterbi_check_traceback(block, depth, 1))
+        return rc;
+    *delay = (depth + block - 1) / block * block;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_conv_encode(uint32_t k, uint32_t n, const uint32_t *generators, const uint8_t *bits, uint64_t nbits, int terminate, uint8_t *out)
+{
+    if (int rc = viterbi_check_code(k, n, generators))
+        return rc;
+    const uint64_t total = nbits + (terminate ? k - 1 : 0);
+    if ((!bits && nbits) || (!out && total))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "bits and out must not be null");
+    uint32_t grev[3] = {};
+    for (uint32_t j = 0; j < n; j++)
+        for (uint32_t b = 0; b < k; b++)
+            grev[j] |= ((generators[j] >> b) & 1u) << (k - 1 - b);
+    uint32_t reg = 0; // the input of i steps ago in bit i
+    for (uint64_t t = 0; t < total; t++) {
+        reg = ((reg << 1) | (t < nbits && bits[t] ? 1u : 0u)) & ((1u << k) - 1);
+        for (uint32_t j = 0; j < n; j++)
+            out[t * n + j] = static_cast<uint8_t>(__builtin_popcount(grev[j] & reg) & 1);
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_create(sdsp_hip_viterbi_plan **out, uint32_t k, uint32_t n, const uint32_t *generators, uint32_t block,
+                                 uint32_t depth, int in_kind, int out_kind, float scale, uint64_t max_channels, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (int rc = viterbi_check_code(k, n, generators))
+        return rc;
+    if (int rc = viterbi_check_traceback(block, depth, k - 1))
+        return rc;
+    if (max_channels == 0 || max_channels >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "max_channels must be in [1, 2^31)");
+    if (in_kind != SDSP_HIP_VITERBI_I8 && in_kind != SDSP_HIP_VITERBI_F32)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_kind must be SDSP_HIP_VITERBI_I8 or SDSP_HIP_VITERBI_F32");
+    if (out_kind != SDSP_HIP_VITERBI_BYTES && out_kind != SDSP_HIP_VITERBI_PACKED)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "out_kind must be SDSP_HIP_VITERBI_BYTES or SDSP_HIP_VITERBI_PACKED");
+    if (in_kind == SDSP_HIP_VITERBI_F32 && !(std::isfinite(scale) && scale > 0.0f))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scale must be finite and above 0");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_viterbi_plan();
+    p->k = k;
+    p->n = n;
+    for (uint32_t j = 0; j < n; j++)
+        p->generators[j] = generators[j];
+    p->block = block;
+    p->depth = depth;
+    p->dr = (depth + block - 1) / block * block;
+    p->in_kind = in_kind;
+    p->out_kind = out_kind;
+    p->scale = in_kind == SDSP_HIP_VITERBI_F32 ? scale : 1.0f;
+    p->max_channels = max_channels;
+    p->device = device;
+    p->variant = k == 7 ? 0 : 1;
+    p->state_bytes = viterbi_layout_of(k, p->dr, max_channels).bytes;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&p->state, p->state_bytes);
+    const viterbi_shape plain = viterbi_shape_for(k, n, block, p->dr, 1);
+    if (e == hipSuccess && !plain.ring_in_lds) {
+        p->ring_bytes = max_channels * plain.ring_steps * ((1ull << (k - 1)) / 64) * 8;
+        e = hipMalloc(&p->ring_ws, p->ring_bytes);
+    }
+    if (e != hipSuccess)
+        rc = plan_fail(e, "viterbi");
+    if (!rc)
+        rc = sdsp_hip_viterbi_plan_reset(p, -1);
+    if (!rc) // the kernels' dynamic-LDS limit, so that process sets no attribute (it may be captured)
+        rc = launch_viterbi(viterbi_args{}, 0, nullptr);
+    if (rc) {
+        sdsp_hip_viterbi_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_destroy(sdsp_hip_viterbi_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->state);
+        (void)hipFree(p->ring_ws);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_process(sdsp_hip_viterbi_plan *p, const void *in, void *out, uint64_t channels, uint64_t steps, void *stream)
+{
+    if (int rc = viterbi_check(p, in, out, channels, steps, true))
+        return rc;
+    if (channels == 0 || steps == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    return launch_viterbi(viterbi_args_of(p, in, out, channels, steps), p->variant, stream);
+}
+
+int sdsp_hip_viterbi_process_host(sdsp_hip_viterbi_plan *p, const void *host_in, void *host_out, uint64_t channels, uint64_t steps)
+{
+    if (int rc = viterbi_check(p, host_in, host_out, channels, steps, false))
+        return rc;
+    if (channels == 0 || steps == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    host_stage st("viterbi", { { host_in, static_cast<size_t>(channels * steps * p->n) * viterbi_in_size(p), false },
+                           { host_out, static_cast<size_t>(channels * viterbi_out_row(p, steps)), true } });
+    int rc = st.in();
+    if (!rc)
+        rc = launch_viterbi(viterbi_args_of(p, st.dev[0], st.dev[1], channels, steps), p->variant, nullptr);
+    if (!rc) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = hip_fail(e, "viterbi process_host");
+    }
+    return st.out(rc);
+}
+
+int sdsp_hip_viterbi_plan_reset(sdsp_hip_viterbi_plan *p, int start_state)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    const uint32_t S = 1u << (p->k - 1);
+    if (start_state < -1 || start_state >= static_cast<int>(S))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "start_state must be -1 or a state of the code");
+    if (int rc = use_device(p->device))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(p->state, 0, p->state_bytes));
+    if (start_state >= 0) {
+        std::vector<int32_t> row(S, SDSP_HIP_VITERBI_START_METRIC);
+        row[static_cast<size_t>(start_state)] = 0;
+        // one row, then doubling copies on the device
+        HIP_TRY(hipMemcpy(p->state, row.data(), S * 4, hipMemcpyHostToDevice));
+        for (uint64_t have = 1; have < p->max_channels; have *= 2) {
+            const uint64_t more = std::min<uint64_t>(have, p->max_channels - have);
+            HIP_TRY(hipMemcpy(static_cast<char *>(p->state) + have * S * 4, p->state, more * S * 4, hipMemcpyDeviceToDevice));
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_get_metrics(sdsp_hip_viterbi_plan *p, int32_t *host_metrics, uint64_t channels)
+{
+    if (!p || !host_metrics)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    if (channels > p->max_channels)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be at most the plan's max_channels");
+    if (int rc = use_device(p->device))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (channels)
+        HIP_TRY(hipMemcpy(host_metrics, p->state, channels * (4ull << (p->k - 1)), hipMemcpyDeviceToHost));
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_set_metrics(sdsp_hip_viterbi_plan *p, const int32_t *host_metrics, uint64_t channels)
+{
+    if (!p || !host_metrics)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    if (channels > p->max_channels)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be at most the plan's max_channels");
+    if (int rc = use_device(p->device))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (channels)
+        HIP_TRY(hipMemcpy(p->state, host_metrics, channels * (4ull << (p->k - 1)), hipMemcpyHostToDevice));
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_state_bytes(const sdsp_hip_viterbi_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = p->state_bytes;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_set_variant(sdsp_hip_viterbi_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    if (variant == 0 && p->k != 7)
+        return fail(SDSP_HIP_ERR_UNSUPPORTED, "the wave kernel serves K = 7 only");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_launches(const sdsp_hip_viterbi_plan *p, uint64_t channels, uint64_t steps, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = channels && steps ? 1 : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_viterbi_plan_get_info(const sdsp_hip_viterbi_plan *p, sdsp_hip_viterbi_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const viterbi_shape s = viterbi_shape_for(p->k, p->n, p->block, p->dr, p->variant);
+    info->k = p->k;
+    info->n = p->n;
+    for (uint32_t j = 0; j < p->n; j++)
+        info->generators[j] = p->generators[j];
+    info->states = 1u << (p->k - 1);
+    info->block = p->block;
+    info->depth = p->depth;
+    info->delay = p->dr;
+    info->chunk = s.chunk;
+    info->threads = s.threads;
+    info->waves = s.waves;
+    info->lds_bytes = s.lds_bytes;
+    info->ring_in_lds = s.ring_in_lds;
+    info->max_channels = p->max_channels;
+    info->state_bytes = p->state_bytes;
+    info->scale = p->scale;
+    info->in_kind = p->in_kind;
+    info->out_kind = p->out_kind;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, viterbi_kernel_for(p->variant), sizeof(info->kernel) - 1);
     return SDSP_HIP_OK;
 }
 }

@@ -536,6 +536,26 @@ cfar2d_shape cfar2d_shape_for(int precision, uint32_t D, uint32_t Ld, uint32_t G
 void cfar2d_workspace(uint32_t D, uint32_t R, uint64_t max_maps, uint64_t *mask_bytes, uint64_t *cnt_bytes);
 uint64_t cfar2d_launches(int variant, bool maps_out, bool list);
 const char *cfar2d_kernel_for(int variant);
+// Viterbi decoder banks (viterbi.hip): the one launch of a call over compact rows
+struct viterbi_args {
+    const void *in; // null: launch nothing, only prepare the kernels (their dynamic-LDS limit) on the current device
+    void *out;
+    uint32_t *metrics; // the plan's state: max_channels x S path metrics,
+    uint32_t *filled;  // max_channels counts of the steps held, at most Dr,
+    uint64_t *hist;    // max_channels x Dr x max(1, S / 64) decision words, oldest step first
+    uint64_t *ring_ws; // nullable: the plain kernel's ring where it does not fit LDS (viterbi_shape::ring_in_lds == 0)
+    uint64_t channels, steps;
+    uint32_t k, n, generators[3], block, depth, dr;
+    int in_kind, out_kind;
+    float scale;
+};
+int launch_viterbi(const viterbi_args &a, int variant, void *stream);
+struct viterbi_shape {
+    uint32_t threads, waves, chunk, ring_steps, lds_bytes, ring_in_lds;
+    uint32_t wave_bytes, q_off, outw_off; // the LDS of one wave of the wave kernel and its parts
+};
+viterbi_shape viterbi_shape_for(uint32_t k, uint32_t n, uint32_t block, uint32_t dr, int variant);
+const char *viterbi_kernel_for(int variant);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
