@@ -75,6 +75,45 @@ if "--units-of-u" in sys.argv:  # that section alone (profiles/fft_accuracy_u.md
     sys.exit(0)
 
 
+# ---- the time-domain kernels against their bit-level models and in units of u (tests/recur_exact.py): per case of
+# tests/test_gpu_biquad_exact.py's and tests/test_gpu_fir_exact.py's tables the worst channel's e2 / einf for kernel, model and plain baseline
+import recur_exact as rx
+import test_gpu_biquad_exact as bq
+import test_gpu_fir_exact as fq
+
+
+def recur_section():
+    kinds = {0: "GENERIC", 1: "LP", 2: "HP", 3: "BP"}
+
+    def _row(family, case, kernel, got, ref, prec, differing):
+        _, k = rx.r2(got, ref["plain"], ref["ld"], prec)
+        _, mo = rx.r2(ref["y"], ref["plain"], ref["ld"], prec)
+        print(f"| {family} | {case} | `{kernel}` | {k['e2']:.2f} / {k['einf']:.2f} | {mo['e2']:.2f} / {mo['einf']:.2f} | {k['base2']:.2f} / {k['baseinf']:.2f} | "
+              f"{k['ratio']:.2f}{' **over**' if k['ratio'] > rx.MARGIN else ''} | {differing} |")
+
+    print("\n## Biquad and FIR banks against their models, in units of u (2^-24 f32 and mixed mode, 2^-53 f64) against the longdouble recurrence\n")
+    print("Worst channel's e2 / einf of the kernel (variant 0, one call), of the model and of the plain unfused baseline; `ratio` = the larger of the worst "
+          "per-channel e2 over max(baseline, 1 u) and the case's einf over max(baseline einf, 1 u), bound 3; `bits` = elements of output and final state "
+          "that differ from the model (R1: 0).\n")
+    print("| family | case | kernel | kernel e2 / einf | model e2 / einf | plain e2 / einf | ratio | bits |\n|---|---|---|---|---|---|---|---|")
+    for case in bq.CASES:
+        precision, kind, m, name, shape = case
+        ref, got, _, state, names = bq.run_channel_major(sd, torch, case, 0, False)
+        diff = rx.bit_diff(got, ref["y"])[0] + rx.bit_diff(state, ref["final"])[0]
+        c, n = bq.SHAPES[shape][:2]
+        _row("biquad", f"{precision}, {kinds[kind]}, {m} sections, {name}, {c} x {n}", names[0], got, ref, precision, diff)
+    for case in fq.CASES:
+        got, hist = fq.run(sd, torch, case, "f32", 0, False)
+        ref = fq.reference(case, "f32")
+        diff = rx.bit_diff(got, ref["y"], True)[0] + rx.bit_diff(hist, ref["final"])[0]
+        _row("FIR", f"f32, {case[0]} taps, {case[1]} x {case[2]}", "sdsp_fir_kernel", got, ref, "f32", diff)
+
+
+if "--recur" in sys.argv:  # that section alone (profiles/recur_accuracy.md)
+    recur_section()
+    sys.exit(0)
+
+
 def rel(got, ref):
     got = np.asarray(got, dtype=np.complex128 if np.iscomplexobj(ref) else np.float64)
     return float((np.abs(got - ref).max(axis=-1) / np.abs(ref).max(axis=-1)).max())
@@ -172,3 +211,4 @@ for n, radix in ((4096, 4), (1024, 2)):
     print(f"| fused convolution | N = {n}, radix {radix} | {rel(d.cpu().numpy(), ref):.2e} | 2e-6 (two transforms) |")
 
 units_of_u_section()
+recur_section()

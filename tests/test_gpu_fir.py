@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_max_err
+from recur_exact import fir_plain
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,8 @@ def test_f64_bit_exact_against_oracle(sd, torch_cuda, oracle, taps, channels, sa
             assert np.array_equal(bank.state.cpu().numpy(), want_state)
     for c in sorted({0, channels - 1, channels // 2}):
         assert np.array_equal(outs[0][c], oracle.fir_process(h, x[c])[0]), (taps, c)
+    # every row: the oracle's operation order vectorised over the channels (tests/recur_exact.py, equal to the oracle bit for bit on the CPU)
+    assert np.array_equal(outs[0], fir_plain(x, h, None, "f64")[0]), taps
     assert np.array_equal(outs[0], outs[1])
 
 
