@@ -2232,6 +2232,75 @@ typedef struct {
 } sdsp_hip_viterbi_plan_info;
 int sdsp_hip_viterbi_plan_get_info(const sdsp_hip_viterbi_plan *plan, sdsp_hip_viterbi_plan_info *info);
 
+/*
+ * ---- Reed-Solomon decoder banks over GF(256) for concatenated codes (rs.hip) ----
+ *
+ * The outer code behind a Viterbi decoder: errors-and-erasures decoding of many interleaved frames at once.  Everything is integer
+ * arithmetic: both kernel variants and tests/rs_ref.py give the same bytes and the same counts, with no tolerance.
+ * Field: GF(2^8) is defined by `field_poly`, a 9-bit integer with bit 8 set (0x11D, 0x187, ..), and alpha = 0x02.  Creation refuses a
+ * polynomial under which alpha does not have order 255 (0x11B: order 51).
+ * Code: the generator is g(x) = prod_{j=0}^{nroots-1} (x - alpha^(prim (fcr + j))) with 0 <= fcr < 255, gcd(prim, 255) = 1
+ * (1 <= prim < 255), 2 <= nroots <= 64, nroots < n <= 255 and k = n - nroots.  n < 255 is the shortened code, whose leading 255 - n
+ * symbols are zero and absent.  In memory order, symbol i of a codeword is the coefficient of x^(n-1-i).  The code is systematic: k
+ * data symbols, then nroots parity symbols.  CCSDS is (0x187, 112, 11, 32 or 16, 255) in the conventional basis, DVB is
+ * (0x11D, 0, 1, 16, 204).
+ * Frames: a frame is `interleave` = I codewords (1 <= I <= 16), symbol-interleaved: byte s I + j of the frame is symbol s of codeword
+ * j.  A call takes `frames` compact frames of I n bytes: the frame length is the frame distance.
+ * Erasures: an optional second input of the same layout; a non-zero byte marks that symbol as erased.
+ * Result: the result of codeword r with erased set E is defined mathematically, not by algorithm.  If |E| > nroots, the codeword is
+ * a failure.  Otherwise, look for a codeword c with 2 |{i not in E : c_i != r_i}| + |E| <= nroots; the minimum distance is
+ * nroots + 1, so at most one exists.  If one exists, the output is c, and `corrected` is the number of positions where c differs
+ * from r.  If none exists, the codeword is a failure.  A failure leaves the codeword's symbols exactly as received and writes
+ * `corrected` = -1.  A received word beyond the bound may decode to another codeword: that is part of the contract and is
+ * deterministic.
+ * Outputs: `out` is FULL (I n bytes per frame; out == in is allowed and is the in-place form) or DATA (the first I k bytes of each
+ * frame, which are exactly the data symbols in the same interleaved order).  Any other overlap of in, out, erasures and corrected is
+ * refused.  `corrected` is optional: int32, one per codeword, at [frame I + j].
+ * Limits: frames < 2^31.  frames == 0 touches nothing.
+ * Errors: sizes out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an unknown kind, a non-primitive polynomial,
+ * gcd(prim, 255) != 1, a misaligned `corrected`, or an overlap: SDSP_HIP_ERR_INVALID_ARG.  A refusal writes nothing.
+ */
+#define SDSP_HIP_RS_FULL 0
+#define SDSP_HIP_RS_DATA 1
+#define SDSP_HIP_RS_MAX_NROOTS 64
+#define SDSP_HIP_RS_MAX_INTERLEAVE 16
+typedef struct sdsp_hip_rs_plan sdsp_hip_rs_plan;
+/* host helper: the nroots + 1 coefficients of g, the highest (1) first, into HOST memory */
+int sdsp_hip_rs_generator(uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint8_t *g);
+/* host helper: the systematic encoder.  data: `frames` frames of I k HOST bytes; out: `frames` frames of I n HOST bytes, the data
+ * symbols followed by the parity symbols, interleaved as above.  data and out must not overlap. */
+int sdsp_hip_rs_encode(uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n, uint32_t interleave,
+                       const uint8_t *data, uint64_t frames, uint8_t *out);
+/* the argument checks come before the device is touched; the plan starts in variant 0.  Errors as above; no device:
+ * SDSP_HIP_ERR_NO_DEVICE; no memory for the field's table: SDSP_HIP_ERR_NOMEM. */
+int sdsp_hip_rs_plan_create(sdsp_hip_rs_plan **plan, uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n,
+                            uint32_t interleave, int out_kind, int device);
+int sdsp_hip_rs_plan_destroy(sdsp_hip_rs_plan *plan);
+/* in, erasures (nullable), out: DEVICE bytes at any address; corrected (nullable): DEVICE int32, 4-byte aligned.  Asynchronous on
+ * `stream`, one plain launch, allocates nothing (stream-capturable). */
+int sdsp_hip_rs_process(sdsp_hip_rs_plan *plan, const void *in, const void *erasures, void *out, int32_t *corrected, uint64_t frames,
+                        void *stream);
+/* same with HOST pointers (synchronous); host_out == host_in is the in-place form */
+int sdsp_hip_rs_process_host(sdsp_hip_rs_plan *plan, const void *host_in, const void *host_erasures, void *host_out,
+                             int32_t *host_corrected, uint64_t frames);
+/* kernel variants (identical bytes): 0 = sdsp_rs_wave_kernel (a wave per frame: the frame staged and de-interleaved through LDS, lane
+ * = symbol position for the syndromes and the root search, lane = coefficient for the key equation); 1 = sdsp_rs_plain_kernel (a
+ * thread per codeword, serial loops).  Errors: any other value: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_rs_plan_set_variant(sdsp_hip_rs_plan *plan, int variant);
+/* kernel launches of one process call: 1; 0 for frames == 0 */
+int sdsp_hip_rs_plan_launches(const sdsp_hip_rs_plan *plan, uint64_t frames, uint64_t *launches);
+typedef struct {
+    uint32_t field_poly, fcr, prim, nroots, n, interleave;
+    uint32_t k;         /* n - nroots */
+    uint32_t t;         /* nroots / 2 */
+    uint32_t threads;   /* per workgroup */
+    uint32_t waves;     /* per workgroup; variant 0: frames a workgroup holds at a time */
+    uint32_t lds_bytes; /* LDS of one workgroup */
+    int out_kind, device, variant;
+    char kernel[64];    /* the kernel the plan's variant runs */
+} sdsp_hip_rs_plan_info;
+int sdsp_hip_rs_plan_get_info(const sdsp_hip_rs_plan *plan, sdsp_hip_rs_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

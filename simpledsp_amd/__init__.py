@@ -16,6 +16,7 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    FFT_COLS_COMPLEX, FFT_COLS_POWER,
                    CFAR2D_EDGE_MARK, CFAR2D_EDGE_CLIP,
                    VITERBI_I8, VITERBI_F32, VITERBI_BYTES, VITERBI_PACKED,
+                   RS_FULL, RS_DATA,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -43,6 +44,7 @@ from .cfar2d import cfar2d_plan, cfar2d, cfar2d_scale, range_doppler_detect, Cfa
 from .pll import pll_bank, pll_gains
 from .timing import timing_bank, timing_step, timing_max_out, timing_gains, timing_design
 from .viterbi import viterbi_bank, viterbi_delay, viterbi_decode, conv_encode
+from .rs import rs_decoder, rs_decode, rs_encode, rs_generator
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

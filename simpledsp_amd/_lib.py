@@ -268,7 +268,17 @@ class ViterbiPlanInfo(C.Structure):
     ]
 
 
+class RsPlanInfo(C.Structure):
+    _fields_ = [
+        ("field_poly", C.c_uint32), ("fcr", C.c_uint32), ("prim", C.c_uint32), ("nroots", C.c_uint32), ("n", C.c_uint32),
+        ("interleave", C.c_uint32), ("k", C.c_uint32), ("t", C.c_uint32), ("threads", C.c_uint32), ("waves", C.c_uint32),
+        ("lds_bytes", C.c_uint32), ("out_kind", C.c_int), ("device", C.c_int), ("variant", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
 TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK = 0, 1, 2
+RS_FULL, RS_DATA = 0, 1
+RS_MAX_NROOTS, RS_MAX_INTERLEAVE = 64, 16
 VITERBI_I8, VITERBI_F32 = 0, 1
 VITERBI_BYTES, VITERBI_PACKED = 0, 1
 VITERBI_MIN_K, VITERBI_MAX_K, VITERBI_MAX_BLOCK, VITERBI_MAX_DEPTH, VITERBI_START_METRIC = 3, 9, 1024, 4096, -(1 << 20)
@@ -587,6 +597,15 @@ SIGNATURES = {
     "sdsp_hip_viterbi_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_viterbi_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_viterbi_plan_get_info": (_i, [_vp, C.POINTER(ViterbiPlanInfo)]),
+    "sdsp_hip_rs_generator": (_i, [_u32, _u32, _u32, _u32, _vp]),
+    "sdsp_hip_rs_encode": (_i, [_u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "sdsp_hip_rs_plan_create": (_i, [_pp, _u32, _u32, _u32, _u32, _u32, _u32, _i, _i]),
+    "sdsp_hip_rs_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_rs_process": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "sdsp_hip_rs_process_host": (_i, [_vp, _vp, _vp, _vp, _vp, _u64]),
+    "sdsp_hip_rs_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_rs_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_rs_plan_get_info": (_i, [_vp, C.POINTER(RsPlanInfo)]),
 }
 
 _lib = None

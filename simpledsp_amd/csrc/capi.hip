@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass, fft_cols), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing, viterbi) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing, viterbi, rs) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -557,6 +557,12 @@ struct sdsp_hip_viterbi_plan {
     void *state = nullptr;   // device: metrics, counts, decisions (the layout of sdsp_hip.h)
     void *ring_ws = nullptr; // device: the plain kernel's ring where it does not fit LDS
     uint64_t ring_bytes = 0;
+};
+
+struct sdsp_hip_rs_plan {
+    uint32_t field_poly = 0, fcr = 0, prim = 0, nroots = 0, n = 0, interleave = 0;
+    int out_kind = 0, device = 0, variant = 0;
+    void *table = nullptr; // device: exp[512], log[256]
 };
 
 struct sdsp_hip_timing_plan {
@@ -7664,6 +7670,295 @@ int sdsp_hip_viterbi_plan_get_info(const sdsp_hip_viterbi_plan *p, sdsp_hip_vite
     info->device = p->device;
     info->variant = p->variant;
     std::strncpy(info->kernel, viterbi_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+// ------------------------------------------------------------------ Reed-Solomon decoder banks (rs.hip)
+
+namespace
+{
+// exp[0 .. 512): alpha^i twice round (the last two entries stay 0), then log[0 .. 256); false where alpha = 2 has not order 255
+bool rs_field_table(uint32_t field_poly, uint8_t *t)
+{
+    std::memset(t, 0, 768);
+    uint32_t x = 1;
+    for (uint32_t i = 0; i < 255; i++) {
+        if (i && x == 1)
+            return false;
+        t[i] = t[i + 255] = static_cast<uint8_t>(x);
+        t[512 + x] = static_cast<uint8_t>(i);
+        x <<= 1;
+        if (x & 0x100)
+            x ^= field_poly;
+    }
+    return x == 1;
+}
+
+uint32_t rs_gcd(uint32_t a, uint32_t b)
+{
+    while (b) {
+        const uint32_t r = a % b;
+        a = b;
+        b = r;
+    }
+    return a;
+}
+
+// the field and the roots of a code, without a device; t receives the field's table
+int rs_check_code(uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint8_t *t)
+{
+    if (field_poly < 0x100 || field_poly >= 0x200)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "field_poly must be a 9-bit polynomial with bit 8 set");
+    if (fcr >= 255 || prim >= 255)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "fcr and prim must be below 255");
+    if (nroots < 2 || nroots > SDSP_HIP_RS_MAX_NROOTS)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "nroots must be in [2, 64]");
+    if (rs_gcd(prim, 255) != 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "gcd(prim, 255) must be 1");
+    if (!rs_field_table(field_poly, t))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "alpha = 2 must have order 255 under field_poly");
+    return SDSP_HIP_OK;
+}
+
+int rs_check_frame(uint32_t nroots, uint32_t n, uint32_t interleave)
+{
+    if (n <= nroots || n > 255)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n must be in (nroots, 255]");
+    if (interleave < 1 || interleave > SDSP_HIP_RS_MAX_INTERLEAVE)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "interleave must be in [1, 16]");
+    return SDSP_HIP_OK;
+}
+
+uint8_t rs_mul(const uint8_t *t, uint32_t a, uint32_t b) { return a && b ? t[t[512 + a] + t[512 + b]] : 0; }
+
+// g[0 .. nroots]: the highest coefficient first
+void rs_generator_of(const uint8_t *t, uint32_t fcr, uint32_t prim, uint32_t nroots, uint8_t *g)
+{
+    std::memset(g, 0, nroots + 1);
+    g[0] = 1; // of degree 0 so far, kept at the front
+    for (uint32_t j = 0; j < nroots; j++) {
+        const uint32_t root = t[(prim * (fcr + j)) % 255];
+        for (uint32_t c = j + 1; c >= 1; c--)
+            g[c] = static_cast<uint8_t>(g[c] ^ rs_mul(t, g[c - 1], root));
+    }
+}
+
+// argument checks shared by process and process_host
+int rs_check(const sdsp_hip_rs_plan *p, const void *in, const void *erasures, const void *out, const int32_t *corrected, uint64_t frames)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "frames must be below 2^31");
+    if (frames == 0)
+        return SDSP_HIP_OK;
+    if (!in || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must not be null");
+    if (corrected && misaligned(corrected, 4))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "corrected must be aligned to 4 bytes");
+    const bool data = p->out_kind == SDSP_HIP_RS_DATA;
+    const uint64_t in_bytes = frames * p->interleave * p->n, out_bytes = frames * p->interleave * (data ? p->n - p->nroots : p->n);
+    const uint64_t cor_bytes = frames * p->interleave * 4;
+    if (!(in == out && !data) && ranges_overlap(in, in_bytes, out, out_bytes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and out must be the same (FULL) or apart");
+    if (ranges_overlap(erasures, in_bytes, in, in_bytes) || ranges_overlap(erasures, in_bytes, out, out_bytes) ||
+        ranges_overlap(corrected, cor_bytes, in, in_bytes) || ranges_overlap(corrected, cor_bytes, out, out_bytes) ||
+        ranges_overlap(corrected, cor_bytes, erasures, in_bytes))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out, erasures and corrected must not overlap");
+    return SDSP_HIP_OK;
+}
+
+rs_args rs_args_of(const sdsp_hip_rs_plan *p, const void *in, const void *erasures, void *out, int32_t *corrected, uint64_t frames)
+{
+    rs_args a{};
+    a.in = in;
+    a.out = out;
+    a.erasures = erasures;
+    a.corrected = corrected;
+    a.table = p->table;
+    a.frames = frames;
+    a.n = p->n;
+    a.nroots = p->nroots;
+    a.interleave = p->interleave;
+    a.fcr = p->fcr;
+    a.prim = p->prim;
+    a.data_only = p->out_kind == SDSP_HIP_RS_DATA;
+    return a;
+}
+} // namespace
+
+int sdsp_hip_rs_generator(uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint8_t *g)
+{
+    uint8_t t[768];
+    if (int rc = rs_check_code(field_poly, fcr, prim, nroots, t))
+        return rc;
+    if (!g)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "g is null");
+    rs_generator_of(t, fcr, prim, nroots, g);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rs_encode(uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n, uint32_t interleave,
+                       const uint8_t *data, uint64_t frames, uint8_t *out)
+{
+    uint8_t t[768], g[SDSP_HIP_RS_MAX_NROOTS + 1], par[SDSP_HIP_RS_MAX_NROOTS];
+    if (int rc = rs_check_code(field_poly, fcr, prim, nroots, t))
+        return rc;
+    if (int rc = rs_check_frame(nroots, n, interleave))
+        return rc;
+    if (frames >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "frames must be below 2^31");
+    if (frames == 0)
+        return SDSP_HIP_OK;
+    if (!data || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "data and out must not be null");
+    const uint64_t k = n - nroots, I = interleave;
+    if (ranges_overlap(data, frames * I * k, out, frames * I * n))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "data and out must not overlap");
+    rs_generator_of(t, fcr, prim, nroots, g);
+    for (uint64_t f = 0; f < frames; f++) {
+        const uint8_t *d = data + f * I * k;
+        uint8_t *o = out + f * I * n;
+        std::memcpy(o, d, I * k);
+        for (uint64_t j = 0; j < I; j++) {
+            // the remainder of data(x) x^nroots by g, in a shift register
+            std::memset(par, 0, sizeof(par));
+            for (uint64_t s = 0; s < k; s++) {
+                const uint32_t fb = d[s * I + j] ^ par[0];
+                for (uint32_t c = 0; c + 1 < nroots; c++)
+                    par[c] = static_cast<uint8_t>(par[c + 1] ^ rs_mul(t, fb, g[c + 1]));
+                par[nroots - 1] = rs_mul(t, fb, g[nroots]);
+            }
+            for (uint32_t c = 0; c < nroots; c++)
+                o[(k + c) * I + j] = par[c];
+        }
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rs_plan_create(sdsp_hip_rs_plan **out, uint32_t field_poly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n,
+                            uint32_t interleave, int out_kind, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    uint8_t t[768];
+    if (int rc = rs_check_code(field_poly, fcr, prim, nroots, t))
+        return rc;
+    if (int rc = rs_check_frame(nroots, n, interleave))
+        return rc;
+    if (out_kind != SDSP_HIP_RS_FULL && out_kind != SDSP_HIP_RS_DATA)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "out_kind must be SDSP_HIP_RS_FULL or SDSP_HIP_RS_DATA");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_rs_plan();
+    p->field_poly = field_poly;
+    p->fcr = fcr;
+    p->prim = prim;
+    p->nroots = nroots;
+    p->n = n;
+    p->interleave = interleave;
+    p->out_kind = out_kind;
+    p->device = device;
+    p->variant = 0;
+    hipError_t e = hipMalloc(&p->table, sizeof(t));
+    if (e == hipSuccess)
+        e = hipMemcpy(p->table, t, sizeof(t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        const int rc = plan_fail(e, "rs");
+        sdsp_hip_rs_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rs_plan_destroy(sdsp_hip_rs_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK)
+        (void)hipFree(p->table);
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rs_process(sdsp_hip_rs_plan *p, const void *in, const void *erasures, void *out, int32_t *corrected, uint64_t frames,
+                        void *stream)
+{
+    if (int rc = rs_check(p, in, erasures, out, corrected, frames))
+        return rc;
+    if (frames == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    return launch_rs(rs_args_of(p, in, erasures, out, corrected, frames), p->variant, stream);
+}
+
+int sdsp_hip_rs_process_host(sdsp_hip_rs_plan *p, const void *host_in, const void *host_erasures, void *host_out, int32_t *host_corrected,
+                             uint64_t frames)
+{
+    if (int rc = rs_check(p, host_in, host_erasures, host_out, host_corrected, frames))
+        return rc;
+    if (frames == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const bool inplace = host_in == host_out;
+    const size_t cw = static_cast<size_t>(frames) * p->interleave;
+    const size_t in_bytes = cw * p->n, out_bytes = cw * (p->out_kind == SDSP_HIP_RS_DATA ? p->n - p->nroots : p->n);
+    host_stage st("rs", { { host_in, in_bytes, inplace },
+                          { host_erasures, in_bytes, false },
+                          { inplace ? nullptr : host_out, out_bytes, true },
+                          { host_corrected, cw * 4, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = launch_rs(rs_args_of(p, st.dev[0], st.dev[1], inplace ? st.dev[0] : st.dev[2], static_cast<int32_t *>(st.dev[3]), frames),
+                       p->variant, nullptr);
+    if (!rc) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = hip_fail(e, "rs process_host");
+    }
+    return st.out(rc);
+}
+
+int sdsp_hip_rs_plan_set_variant(sdsp_hip_rs_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rs_plan_launches(const sdsp_hip_rs_plan *p, uint64_t frames, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = frames ? 1 : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_rs_plan_get_info(const sdsp_hip_rs_plan *p, sdsp_hip_rs_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const rs_shape s = rs_shape_for(p->n, p->interleave, p->variant);
+    info->field_poly = p->field_poly;
+    info->fcr = p->fcr;
+    info->prim = p->prim;
+    info->nroots = p->nroots;
+    info->n = p->n;
+    info->interleave = p->interleave;
+    info->k = p->n - p->nroots;
+    info->t = p->nroots / 2;
+    info->threads = s.threads;
+    info->waves = s.waves;
+    info->lds_bytes = s.lds_bytes;
+    info->out_kind = p->out_kind;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, rs_kernel_for(p->variant), sizeof(info->kernel) - 1);
     return SDSP_HIP_OK;
 }
 }

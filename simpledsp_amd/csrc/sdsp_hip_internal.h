@@ -556,6 +556,24 @@ struct viterbi_shape {
 };
 viterbi_shape viterbi_shape_for(uint32_t k, uint32_t n, uint32_t block, uint32_t dr, int variant);
 const char *viterbi_kernel_for(int variant);
+// Reed-Solomon decoder banks (rs.hip): the one launch of a call over compact frames
+struct rs_args {
+    const void *in;
+    void *out;            // == in: in place
+    const void *erasures; // nullable
+    int32_t *corrected;   // nullable
+    const void *table;    // device: exp[512] (alpha^i, twice round), log[256]
+    uint64_t frames;
+    uint32_t n, nroots, interleave, fcr, prim;
+    bool data_only;
+};
+int launch_rs(const rs_args &a, int variant, void *stream);
+struct rs_shape {
+    uint32_t threads, waves, lds_bytes;
+    uint32_t image; // wave kernel: LDS bytes of one staged frame
+};
+rs_shape rs_shape_for(uint32_t n, uint32_t interleave, int variant);
+const char *rs_kernel_for(int variant);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
