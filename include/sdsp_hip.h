@@ -2301,6 +2301,116 @@ typedef struct {
 } sdsp_hip_rs_plan_info;
 int sdsp_hip_rs_plan_get_info(const sdsp_hip_rs_plan *plan, sdsp_hip_rs_plan_info *info);
 
+/*
+ * ---- streaming frame synchroniser banks between the Viterbi and the Reed-Solomon decoders (fsync.hip) ----
+ *
+ * A bank finds the attached sync marker in `channels` compact rows of bits, at any bit offset and in either polarity, follows it with
+ * a SEARCH / VERIFY / LOCK machine per channel, and writes the payloads behind accepted markers as compact frames of bytes, the
+ * inversion and a pseudo-random sequence removed: what sdsp_hip_rs_process takes as it lies.  Every operation is on integers: both
+ * kernel variants and tests/fsync_ref.py give the same frames, records and state for any split of a stream into calls.
+ * Frame: a marker of M bits (8 .. 64, a uint64_t whose bit M - 1 is the first bit on the line; bits at and above M must be 0), then P
+ * payload bytes (1 .. 8192); the period is L = M + 8 P bits.  tol: 0 .. min(15, M / 2 - 1); verify V and flywheel F: 0 .. 255;
+ * polarity NORMAL or EITHER; pn: nullable HOST array of P bytes that is XORed onto every payload.
+ * Input: BYTES: one byte per bit, non-zero counts as 1, row c at in + c nbits, any nbits; PACKED: uint32 words, the oldest bit lowest
+ * (sdsp_hip_viterbi_process's PACKED output), nbits / 32 words per row, nbits a multiple of 32.  No strides: rows are compact.
+ * Positions count the bits of a channel's stream from 0 at the last reset, as uint64_t; nothing exists in front of position 0.
+ * d(p) = popcount(bits[p .. p + M - 1] XOR marker); a normal hit is d <= tol, an inverted hit M - d <= tol (EITHER only; tol < M / 2,
+ * so never both).  A position is examined once bit p + M - 1 exists.
+ * Machine, per channel (mode, next position p, polarity, count, misses), run while p + M <= bits seen:
+ *   SEARCH at p: a hit takes its polarity, count = misses = 0; with V == 0 it goes to LOCK and accepts the frame at p, otherwise to
+ *     VERIFY; p += L either way.  No hit: p += 1.
+ *   VERIFY at p (the held polarity only): a hit: count += 1, and when count reaches V, LOCK and the frame at this p is accepted;
+ *     p += L.  A miss: SEARCH at p - L + 1, so that a false candidate does not shadow a true marker behind it.
+ *   LOCK at p: a hit: misses = 0, the frame is accepted, p += L.  A miss: misses += 1; above F: SEARCH at the same p (either polarity
+ *     again, nothing accepted); otherwise the frame is accepted with the flywheel flag, p += L.
+ * A frame accepted at p is emitted by the call that brings bit p + L - 1, so a call emits at most max_frames(nbits) = ceil(nbits / L)
+ * frames per row (sdsp_hip_fsync_max_frames), in stream order, and at most one accepted frame is pending at the end of a call.
+ * Outputs, rows compact: out (nullable) uint8 channels x max_frames x P: the payload bits p + M .. p + L - 1, the first bit the most
+ * significant of byte 0, XOR 0xFF where the polarity is inverted, XOR pn; counts uint32 per row; pos (nullable) uint64 channels x
+ * max_frames: the marker's first bit; info (nullable) uint32: bits 0-7 the polarity-corrected marker distance, bit 8 inverted, bit 9
+ * flywheel.  Slots at and beyond counts[c] are not written.
+ * State: one plan-owned device buffer of sdsp_hip_fsync_plan_state_bytes: max_channels records of 16 uint32 (0 mode: 0 SEARCH, 1
+ * VERIFY, 2 LOCK; 1 polarity; 2 count; 3 misses; 4 pending; 5 the pending frame's info; 6-7 next position; 8-9 bits seen; 10-11 the
+ * pending frame's position; 12-15 zero; 64-bit values low word first), then max_channels rings of HW = ceil((L + M) / 32) + 1 uint32:
+ * the stream's word W (bits 32 W .. 32 W + 31, the oldest lowest) lies in slot W mod HW, bits at and beyond `bits seen` are 0.  The
+ * ring always holds the last L + M bits: the oldest a later decision can need is L + M - 2 back (a VERIFY miss examined one bit
+ * behind a call's end).  Both variants read and write it, so a stream may change variant between calls.
+ * Limits: 1 <= max_channels < 2^31, 1 <= max_bits < 2^31.
+ */
+#define SDSP_HIP_FSYNC_BYTES 0
+#define SDSP_HIP_FSYNC_PACKED 1
+#define SDSP_HIP_FSYNC_NORMAL 0
+#define SDSP_HIP_FSYNC_EITHER 1
+#define SDSP_HIP_FSYNC_SEARCH 0
+#define SDSP_HIP_FSYNC_VERIFY 1
+#define SDSP_HIP_FSYNC_LOCK 2
+#define SDSP_HIP_FSYNC_MAX_PAYLOAD 8192
+#define SDSP_HIP_FSYNC_CCSDS_ASM 0x1ACFFC1Du
+typedef struct sdsp_hip_fsync_plan sdsp_hip_fsync_plan;
+/* host helper: n bytes of the CCSDS pseudo-randomiser, a[i + 8] = a[i] ^ a[i + 3] ^ a[i + 5] ^ a[i + 7] from eight ones, the first bit
+ * the most significant (FF 48 0E C0 9A 0D 70 BC ..; the period is 255 bits).  Errors: out null with n > 0: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_fsync_ccsds_pn(uint8_t *out, uint64_t n);
+/* host helper, the transmit side: nframes x P payload bytes -> nframes L bits (0 / 1 bytes): the marker, then the payload XOR pn
+ * (nullable), all of it inverted where `invert` is non-zero.  Errors: marker_bits or payload_bytes out of range:
+ * SDSP_HIP_ERR_INVALID_SIZE; a null pointer with nframes > 0, marker bits at or above marker_bits: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_fsync_attach(uint64_t marker, uint32_t marker_bits, uint32_t payload_bytes, const uint8_t *pn, const uint8_t *frames,
+                          uint64_t nframes, int invert, uint8_t *bits);
+/* host helper: ceil(nbits / L).  Errors: sizes out of range: SDSP_HIP_ERR_INVALID_SIZE; null: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_fsync_max_frames(uint32_t marker_bits, uint32_t payload_bytes, uint64_t nbits, uint64_t *frames);
+/* max_bits: the most bits per row one call may bring; it sizes the plan-owned workspace of variant 0 (three words per 32 bits and
+ * row, and the frame records), so that process allocates nothing.  The plan starts reset, in variant 0.  Errors: marker_bits,
+ * payload_bytes, verify, flywheel, max_channels or max_bits out of range: SDSP_HIP_ERR_INVALID_SIZE; a null plan pointer, tol out of
+ * range, marker bits at or above marker_bits, an unknown polarity or kind: SDSP_HIP_ERR_INVALID_ARG; no device:
+ * SDSP_HIP_ERR_NO_DEVICE; no memory: SDSP_HIP_ERR_NOMEM. */
+int sdsp_hip_fsync_plan_create(sdsp_hip_fsync_plan **plan, uint64_t marker, uint32_t marker_bits, uint32_t payload_bytes, uint32_t tol,
+                               uint32_t verify, uint32_t flywheel, int polarity, const uint8_t *pn, int in_kind, uint64_t max_channels,
+                               uint64_t max_bits, int device);
+int sdsp_hip_fsync_plan_destroy(sdsp_hip_fsync_plan *plan);
+/*
+ * in, out, counts, pos, info: DEVICE pointers, aligned to their element (in: 1 byte for BYTES, 4 for PACKED; out: 1; counts, info: 4;
+ * pos: 8).  Asynchronous on `stream`, plain launches only (sdsp_hip_fsync_plan_launches of them), allocates nothing
+ * (stream-capturable); one call per plan in flight.  Errors: channels above max_channels, nbits above max_bits, nbits not a multiple
+ * of 32 for PACKED: SDSP_HIP_ERR_INVALID_SIZE; null plan, null in or counts with work to do, a misaligned pointer, two of the ranges
+ * overlapping, or one overlapping the state: SDSP_HIP_ERR_INVALID_ARG.  channels == 0: nothing is touched.  nbits == 0: counts is
+ * zeroed and nothing else is touched.
+ */
+int sdsp_hip_fsync_process(sdsp_hip_fsync_plan *plan, const void *in, uint8_t *out, uint32_t *counts, uint64_t *pos, uint32_t *info,
+                           uint64_t channels, uint64_t nbits, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_fsync_process_host(sdsp_hip_fsync_plan *plan, const void *host_in, uint8_t *host_out, uint32_t *host_counts,
+                                uint64_t *host_pos, uint32_t *host_info, uint64_t channels, uint64_t nbits);
+/* a fresh stream in every channel: SEARCH at position 0, nothing seen, nothing pending.  Synchronous. */
+int sdsp_hip_fsync_plan_reset(sdsp_hip_fsync_plan *plan);
+/* the machine of the first `channels` channels to HOST arrays of `channels` values each (every one nullable): mode, next position,
+ * polarity, count, misses, pending (0 / 1), bits seen.  Synchronous.  Errors: a null plan: SDSP_HIP_ERR_INVALID_ARG; channels above
+ * max_channels: SDSP_HIP_ERR_INVALID_SIZE. */
+int sdsp_hip_fsync_plan_get_state(sdsp_hip_fsync_plan *plan, uint32_t *mode, uint64_t *next, uint32_t *polarity, uint32_t *count,
+                                  uint32_t *misses, uint32_t *pending, uint64_t *seen, uint64_t channels);
+/* bytes of the plan's state buffer (the layout above) */
+int sdsp_hip_fsync_plan_state_bytes(const sdsp_hip_fsync_plan *plan, uint64_t *bytes);
+/* kernel variants (identical bits, one state layout): 0 = five launches over a packed working row in the plan's workspace (pack by
+ * ballot, correlate by v_alignbit and popcount into a hit word per polarity, sdsp_fsync_walk_kernel: a wave per channel with a
+ * find-first over 64 hit words per round, extract four bytes per thread, carry); 1 = sdsp_fsync_plain_kernel (a thread per channel,
+ * bit by bit).  Errors: any other value: SDSP_HIP_ERR_INVALID_ARG. */
+int sdsp_hip_fsync_plan_set_variant(sdsp_hip_fsync_plan *plan, int variant);
+/* kernel launches of one process call: variant 0: 5 (4 without out), variant 1: 1; 0 for channels == 0 or nbits == 0 */
+int sdsp_hip_fsync_plan_launches(const sdsp_hip_fsync_plan *plan, uint64_t channels, uint64_t nbits, uint64_t *launches);
+typedef struct {
+    uint64_t marker;
+    uint32_t marker_bits, payload_bytes;
+    uint32_t period;       /* L */
+    uint32_t tol, verify, flywheel;
+    uint32_t ring_words;   /* HW */
+    uint32_t row_words;    /* words per row and array of variant 0's workspace */
+    uint32_t has_pn;
+    uint64_t max_channels, max_bits;
+    uint64_t max_frames;   /* of a call of max_bits */
+    uint64_t state_bytes, workspace_bytes;
+    int polarity, in_kind, device, variant;
+    char kernel[64];       /* the kernel that runs the machine in the plan's variant */
+} sdsp_hip_fsync_plan_info;
+int sdsp_hip_fsync_plan_get_info(const sdsp_hip_fsync_plan *plan, sdsp_hip_fsync_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

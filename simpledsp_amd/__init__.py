@@ -17,6 +17,7 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    CFAR2D_EDGE_MARK, CFAR2D_EDGE_CLIP,
                    VITERBI_I8, VITERBI_F32, VITERBI_BYTES, VITERBI_PACKED,
                    RS_FULL, RS_DATA,
+                   FSYNC_BYTES, FSYNC_PACKED, FSYNC_NORMAL, FSYNC_EITHER, FSYNC_SEARCH, FSYNC_VERIFY, FSYNC_LOCK,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -45,6 +46,7 @@ from .pll import pll_bank, pll_gains
 from .timing import timing_bank, timing_step, timing_max_out, timing_gains, timing_design
 from .viterbi import viterbi_bank, viterbi_delay, viterbi_decode, conv_encode
 from .rs import rs_decoder, rs_decode, rs_encode, rs_generator
+from .fsync import frame_sync_bank, ccsds_pn, attach_sync, fsync_max_frames, CCSDS_ASM
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

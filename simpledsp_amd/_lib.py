@@ -276,7 +276,21 @@ class RsPlanInfo(C.Structure):
     ]
 
 
+class FsyncPlanInfo(C.Structure):
+    _fields_ = [
+        ("marker", C.c_uint64), ("marker_bits", C.c_uint32), ("payload_bytes", C.c_uint32), ("period", C.c_uint32), ("tol", C.c_uint32),
+        ("verify", C.c_uint32), ("flywheel", C.c_uint32), ("ring_words", C.c_uint32), ("row_words", C.c_uint32), ("has_pn", C.c_uint32),
+        ("max_channels", C.c_uint64), ("max_bits", C.c_uint64), ("max_frames", C.c_uint64), ("state_bytes", C.c_uint64),
+        ("workspace_bytes", C.c_uint64), ("polarity", C.c_int), ("in_kind", C.c_int), ("device", C.c_int), ("variant", C.c_int),
+        ("kernel", C.c_char * 64),
+    ]
+
+
 TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK = 0, 1, 2
+FSYNC_BYTES, FSYNC_PACKED = 0, 1
+FSYNC_NORMAL, FSYNC_EITHER = 0, 1
+FSYNC_SEARCH, FSYNC_VERIFY, FSYNC_LOCK = 0, 1, 2
+FSYNC_MAX_PAYLOAD, FSYNC_CCSDS_ASM = 8192, 0x1ACFFC1D
 RS_FULL, RS_DATA = 0, 1
 RS_MAX_NROOTS, RS_MAX_INTERLEAVE = 64, 16
 VITERBI_I8, VITERBI_F32 = 0, 1
@@ -606,6 +620,19 @@ SIGNATURES = {
     "sdsp_hip_rs_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_rs_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
     "sdsp_hip_rs_plan_get_info": (_i, [_vp, C.POINTER(RsPlanInfo)]),
+    "sdsp_hip_fsync_ccsds_pn": (_i, [_vp, _u64]),
+    "sdsp_hip_fsync_attach": (_i, [_u64, _u32, _u32, _vp, _vp, _u64, _i, _vp]),
+    "sdsp_hip_fsync_max_frames": (_i, [_u32, _u32, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_fsync_plan_create": (_i, [_pp, _u64, _u32, _u32, _u32, _u32, _u32, _i, _vp, _i, _u64, _u64, _i]),
+    "sdsp_hip_fsync_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_fsync_process": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "sdsp_hip_fsync_process_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64]),
+    "sdsp_hip_fsync_plan_reset": (_i, [_vp]),
+    "sdsp_hip_fsync_plan_get_state": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64]),
+    "sdsp_hip_fsync_plan_state_bytes": (_i, [_vp, C.POINTER(_u64)]),
+    "sdsp_hip_fsync_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_fsync_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_fsync_plan_get_info": (_i, [_vp, C.POINTER(FsyncPlanInfo)]),
 }
 
 _lib = None

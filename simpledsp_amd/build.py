@@ -63,6 +63,7 @@ SOURCES = {
     # GF(256) on integers and table look-ups, no floating point at all.  The plain kernel's per-thread polynomials stay in scratch: turned
     # into registers they cost 256 VGPRs, 114 AGPRs and 1817 spilled SGPRs, one wave per SIMD (profiles/rs_kernel_regs.txt)
     "rs.hip": ["-mllvm", "-disable-promote-alloca-to-vector"],
+    "fsync.hip": [],  # bits, shifts and popcounts: no floating point at all
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA

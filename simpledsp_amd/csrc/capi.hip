@@ -1,7 +1,7 @@
 // capi.hip -- the extern "C" boundary declared in include/sdsp_hip.h: plans, launches, host and
 // multi-device convenience paths.  Everything that computes goes to the HIP kernels of the other translation units -- the
 // transforms (fft_tile, fft4096, fft1m, fft_reg, fft_reg64, fft_big, fft_big64, fft_mix, fft_wave, fft_mid, fft_2pass, fft_cols), the filters
-// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing, viterbi, rs) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
+// (iir, iir_filtfilt, fir, fir_fft, fir_resample, arb_resample, cic, cic_interp, ddc, duc, beam, lms, rank_filter, cfar, cfar2d, pll, timing, viterbi, rs, fsync) and the framed banks (stft, istft, welch, pfb, pfb_synth); there is no CPU implementation
 // behind these entry points.
 #include <hip/hip_runtime.h>
 
@@ -557,6 +557,15 @@ struct sdsp_hip_viterbi_plan {
     void *state = nullptr;   // device: metrics, counts, decisions (the layout of sdsp_hip.h)
     void *ring_ws = nullptr; // device: the plain kernel's ring where it does not fit LDS
     uint64_t ring_bytes = 0;
+};
+
+struct sdsp_hip_fsync_plan {
+    uint64_t marker = 0, max_channels = 0, max_bits = 0, max_frames = 0, state_bytes = 0, ws_bytes = 0;
+    uint32_t M = 0, P = 0, L = 0, tol = 0, V = 0, F = 0, HW = 0, RW = 0;
+    int polarity = 0, in_kind = 0, device = 0, variant = 0;
+    void *state = nullptr; // device: the records, then the rings (the layout of sdsp_hip.h)
+    void *ws = nullptr;    // device: variant 0's working rows, hit words and frame records
+    void *pn = nullptr;    // device: the pn sequence as words, or null
 };
 
 struct sdsp_hip_rs_plan {
@@ -7959,6 +7968,388 @@ int sdsp_hip_rs_plan_get_info(const sdsp_hip_rs_plan *p, sdsp_hip_rs_plan_info *
     info->device = p->device;
     info->variant = p->variant;
     std::strncpy(info->kernel, rs_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+// ------------------------------------------------------------------ frame synchroniser banks (fsync.hip)
+
+namespace
+{
+constexpr uint32_t kFsyncRecWords = 16; // a channel's record in the state, in uint32
+
+// the frame of a plan or of a host helper, without a device
+int fsync_check_frame(uint64_t marker, uint32_t M, uint32_t P)
+{
+    if (M < 8 || M > 64)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "marker_bits must be in [8, 64]");
+    if (P < 1 || P > SDSP_HIP_FSYNC_MAX_PAYLOAD)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "payload_bytes must be in [1, 8192]");
+    if (M < 64 && (marker >> M) != 0)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "the marker has bits at or above marker_bits");
+    return SDSP_HIP_OK;
+}
+
+struct fsync_ws_layout {
+    uint64_t rec_pos, work, hitn, hiti, rec_info, rec_cnt, bytes; // ws_seen lies at 0
+};
+fsync_ws_layout fsync_ws_layout_of(const sdsp_hip_fsync_plan *p)
+{
+    fsync_ws_layout l{};
+    const uint64_t mc = p->max_channels, row = mc * p->RW * 4;
+    l.rec_pos = mc * 8;
+    l.work = l.rec_pos + mc * p->max_frames * 8;
+    l.hitn = l.work + row;
+    l.hiti = l.hitn + row;
+    l.rec_info = l.hiti + row;
+    l.rec_cnt = l.rec_info + mc * p->max_frames * 4;
+    l.bytes = l.rec_cnt + mc * 4;
+    return l;
+}
+
+uint64_t fsync_in_row(const sdsp_hip_fsync_plan *p, uint64_t nbits) { return p->in_kind == SDSP_HIP_FSYNC_PACKED ? nbits / 8 : nbits; }
+uint64_t fsync_frames_of(const sdsp_hip_fsync_plan *p, uint64_t nbits) { return (nbits + p->L - 1) / p->L; }
+
+// argument checks shared by process and process_host (device pointers or not)
+int fsync_check(const sdsp_hip_fsync_plan *p, const void *in, const uint8_t *out, const uint32_t *counts, const uint64_t *pos,
+                const uint32_t *info, uint64_t channels, uint64_t nbits, bool device_ptrs)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (channels > p->max_channels)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be at most the plan's max_channels");
+    if (nbits > p->max_bits)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "nbits must be at most the plan's max_bits");
+    if (p->in_kind == SDSP_HIP_FSYNC_PACKED && nbits % 32 != 0)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "nbits must be a multiple of 32 for packed input");
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (!counts || (!in && nbits))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in and counts must not be null");
+    if (misaligned(counts, 4) || misaligned(info, 4) || misaligned(pos, 8) || (p->in_kind == SDSP_HIP_FSYNC_PACKED && misaligned(in, 4)))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in, counts, pos and info must be aligned to their element size");
+    const uint64_t mf = fsync_frames_of(p, nbits);
+    const void *ptr[7] = { in, out, counts, pos, info, device_ptrs ? p->state : nullptr, device_ptrs ? p->ws : nullptr };
+    const uint64_t bytes[7] = { channels * fsync_in_row(p, nbits), channels * mf * p->P, channels * 4, channels * mf * 8, channels * mf * 4,
+                                p->state_bytes, p->ws_bytes };
+    for (int i = 0; i < 5; i++)
+        for (int j = i + 1; j < 7; j++)
+            if (bytes[i] && bytes[j] && ranges_overlap(ptr[i], bytes[i], ptr[j], bytes[j]))
+                return fail(SDSP_HIP_ERR_INVALID_ARG, "in, out, counts, pos, info and the plan's buffers must not overlap");
+    return SDSP_HIP_OK;
+}
+
+sdsp_hip::fsync_args fsync_args_of(const sdsp_hip_fsync_plan *p, const void *in, uint8_t *out, uint32_t *counts, uint64_t *pos,
+                                   uint32_t *info, uint64_t channels, uint64_t nbits)
+{
+    const fsync_ws_layout l = fsync_ws_layout_of(p);
+    char *ws = static_cast<char *>(p->ws);
+    sdsp_hip::fsync_args a{};
+    a.in = in;
+    a.out = out;
+    a.counts = counts;
+    a.pos = pos;
+    a.info = info;
+    a.state = static_cast<uint32_t *>(p->state);
+    a.ring = a.state + p->max_channels * kFsyncRecWords;
+    a.ws_seen = reinterpret_cast<uint64_t *>(ws);
+    a.rec_pos = reinterpret_cast<uint64_t *>(ws + l.rec_pos);
+    a.work = reinterpret_cast<uint32_t *>(ws + l.work);
+    a.hitn = reinterpret_cast<uint32_t *>(ws + l.hitn);
+    a.hiti = reinterpret_cast<uint32_t *>(ws + l.hiti);
+    a.rec_info = reinterpret_cast<uint32_t *>(ws + l.rec_info);
+    a.rec_cnt = reinterpret_cast<uint32_t *>(ws + l.rec_cnt);
+    a.pnw = static_cast<const uint32_t *>(p->pn);
+    a.channels = channels;
+    a.nbits = nbits;
+    a.maxf = fsync_frames_of(p, nbits);
+    a.M = p->M;
+    a.P = p->P;
+    a.L = p->L;
+    a.tol = p->tol;
+    a.V = p->V;
+    a.F = p->F;
+    a.either = p->polarity == SDSP_HIP_FSYNC_EITHER ? 1 : 0;
+    a.packed = p->in_kind == SDSP_HIP_FSYNC_PACKED ? 1 : 0;
+    a.HW = p->HW;
+    a.RW = p->RW;
+    uint64_t rev = 0; // the marker with its first bit lowest
+    for (uint32_t i = 0; i < p->M; i++)
+        rev |= ((p->marker >> (p->M - 1 - i)) & 1ull) << i;
+    a.mrev_lo = static_cast<uint32_t>(rev);
+    a.mrev_hi = static_cast<uint32_t>(rev >> 32);
+    return a;
+}
+
+// the work of one call on device pointers: counts alone for an empty call
+int fsync_run(const sdsp_hip_fsync_plan *p, const void *in, uint8_t *out, uint32_t *counts, uint64_t *pos, uint32_t *info,
+              uint64_t channels, uint64_t nbits, hipStream_t stream)
+{
+    if (nbits == 0) {
+        const hipError_t e = hipMemsetAsync(counts, 0, channels * 4, stream);
+        return e == hipSuccess ? SDSP_HIP_OK : hip_fail(e, "fsync process");
+    }
+    return sdsp_hip::launch_fsync(fsync_args_of(p, in, out, counts, pos, info, channels, nbits), p->variant, stream);
+}
+} // namespace
+
+int sdsp_hip_fsync_ccsds_pn(uint8_t *out, uint64_t n)
+{
+    if (!out && n)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "out is null");
+    uint32_t reg = 0xff; // a[i] in bit 7 .. a[i + 7] in bit 0
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t byte = 0;
+        for (int b = 0; b < 8; b++) {
+            byte = (byte << 1) | ((reg >> 7) & 1u);
+            const uint32_t next = ((reg >> 7) ^ (reg >> 4) ^ (reg >> 2) ^ reg) & 1u;
+            reg = ((reg << 1) | next) & 0xff;
+        }
+        out[i] = static_cast<uint8_t>(byte);
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_attach(uint64_t marker, uint32_t M, uint32_t P, const uint8_t *pn, const uint8_t *frames, uint64_t nframes, int invert,
+                          uint8_t *bits)
+{
+    if (int rc = fsync_check_frame(marker, M, P))
+        return rc;
+    if (nframes && (!frames || !bits))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "frames and bits must not be null");
+    const uint8_t flip = invert ? 1 : 0;
+    for (uint64_t f = 0; f < nframes; f++) {
+        uint8_t *o = bits + f * (M + 8ull * P);
+        for (uint32_t i = 0; i < M; i++)
+            o[i] = static_cast<uint8_t>(((marker >> (M - 1 - i)) & 1ull) ^ flip);
+        for (uint32_t i = 0; i < P; i++) {
+            const uint32_t v = frames[f * P + i] ^ (pn ? pn[i] : 0);
+            for (uint32_t b = 0; b < 8; b++)
+                o[M + 8 * i + b] = static_cast<uint8_t>(((v >> (7 - b)) & 1u) ^ flip);
+        }
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_max_frames(uint32_t M, uint32_t P, uint64_t nbits, uint64_t *frames)
+{
+    if (!frames)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "frames is null");
+    if (int rc = fsync_check_frame(0, M, P))
+        return rc;
+    const uint64_t L = M + 8ull * P;
+    *frames = nbits / L + (nbits % L ? 1 : 0);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_create(sdsp_hip_fsync_plan **out, uint64_t marker, uint32_t M, uint32_t P, uint32_t tol, uint32_t verify,
+                               uint32_t flywheel, int polarity, const uint8_t *pn, int in_kind, uint64_t max_channels, uint64_t max_bits,
+                               int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    if (int rc = fsync_check_frame(marker, M, P))
+        return rc;
+    if (tol > 15 || tol + 1 > M / 2)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "tol must be in [0, min(15, marker_bits / 2 - 1)]");
+    if (verify > 255 || flywheel > 255)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "verify and flywheel must be in [0, 255]");
+    if (max_channels == 0 || max_channels >= (1ull << 31) || max_bits == 0 || max_bits >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "max_channels and max_bits must be in [1, 2^31)");
+    if (polarity != SDSP_HIP_FSYNC_NORMAL && polarity != SDSP_HIP_FSYNC_EITHER)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "polarity must be SDSP_HIP_FSYNC_NORMAL or SDSP_HIP_FSYNC_EITHER");
+    if (in_kind != SDSP_HIP_FSYNC_BYTES && in_kind != SDSP_HIP_FSYNC_PACKED)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_kind must be SDSP_HIP_FSYNC_BYTES or SDSP_HIP_FSYNC_PACKED");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_fsync_plan();
+    p->marker = marker;
+    p->M = M;
+    p->P = P;
+    p->L = M + 8 * P;
+    p->tol = tol;
+    p->V = verify;
+    p->F = flywheel;
+    p->polarity = polarity;
+    p->in_kind = in_kind;
+    p->max_channels = max_channels;
+    p->max_bits = max_bits;
+    p->max_frames = fsync_frames_of(p, max_bits);
+    p->device = device;
+    p->variant = 0;
+    p->HW = sdsp_hip::fsync_ring_words(M, P);
+    p->RW = static_cast<uint32_t>(sdsp_hip::fsync_row_words(M, P, max_bits));
+    p->state_bytes = max_channels * (kFsyncRecWords + p->HW) * 4;
+    p->ws_bytes = fsync_ws_layout_of(p).bytes;
+    int rc = SDSP_HIP_OK;
+    hipError_t e = hipMalloc(&p->state, p->state_bytes);
+    if (e == hipSuccess)
+        e = hipMalloc(&p->ws, p->ws_bytes);
+    if (e == hipSuccess && pn) {
+        std::vector<uint8_t> words((P + 3) / 4 * 4, 0);
+        std::copy(pn, pn + P, words.begin());
+        e = hipMalloc(&p->pn, words.size());
+        if (e == hipSuccess)
+            e = hipMemcpy(p->pn, words.data(), words.size(), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+        rc = plan_fail(e, "fsync");
+    if (!rc)
+        rc = sdsp_hip_fsync_plan_reset(p);
+    if (rc) {
+        sdsp_hip_fsync_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_destroy(sdsp_hip_fsync_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->state);
+        (void)hipFree(p->ws);
+        (void)hipFree(p->pn);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_process(sdsp_hip_fsync_plan *p, const void *in, uint8_t *out, uint32_t *counts, uint64_t *pos, uint32_t *info,
+                           uint64_t channels, uint64_t nbits, void *stream)
+{
+    if (int rc = fsync_check(p, in, out, counts, pos, info, channels, nbits, true))
+        return rc;
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    return fsync_run(p, in, out, counts, pos, info, channels, nbits, static_cast<hipStream_t>(stream));
+}
+
+int sdsp_hip_fsync_process_host(sdsp_hip_fsync_plan *p, const void *host_in, uint8_t *host_out, uint32_t *host_counts, uint64_t *host_pos,
+                                uint32_t *host_info, uint64_t channels, uint64_t nbits)
+{
+    if (int rc = fsync_check(p, host_in, host_out, host_counts, host_pos, host_info, channels, nbits, false))
+        return rc;
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t mf = static_cast<size_t>(fsync_frames_of(p, nbits)), ch = static_cast<size_t>(channels);
+    host_stage st("fsync", { { nbits ? host_in : nullptr, ch * static_cast<size_t>(fsync_in_row(p, nbits)), false },
+                             { mf ? host_out : nullptr, ch * mf * p->P, true },
+                             { host_counts, ch * 4, true },
+                             { mf ? host_pos : nullptr, ch * mf * 8, true },
+                             { mf ? host_info : nullptr, ch * mf * 4, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = fsync_run(p, st.dev[0], static_cast<uint8_t *>(st.dev[1]), static_cast<uint32_t *>(st.dev[2]), static_cast<uint64_t *>(st.dev[3]),
+                       static_cast<uint32_t *>(st.dev[4]), channels, nbits, nullptr);
+    if (!rc) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = hip_fail(e, "fsync process_host");
+    }
+    return st.out(rc);
+}
+
+int sdsp_hip_fsync_plan_reset(sdsp_hip_fsync_plan *p)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (int rc = use_device(p->device))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(p->state, 0, p->state_bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_get_state(sdsp_hip_fsync_plan *p, uint32_t *mode, uint64_t *next, uint32_t *polarity, uint32_t *count,
+                                  uint32_t *misses, uint32_t *pending, uint64_t *seen, uint64_t channels)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (channels > p->max_channels)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "channels must be at most the plan's max_channels");
+    if (channels == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> rec(static_cast<size_t>(channels) * kFsyncRecWords);
+    HIP_TRY(hipMemcpy(rec.data(), p->state, rec.size() * 4, hipMemcpyDeviceToHost));
+    for (uint64_t c = 0; c < channels; c++) {
+        const uint32_t *r = rec.data() + c * kFsyncRecWords;
+        if (mode)
+            mode[c] = r[0];
+        if (polarity)
+            polarity[c] = r[1];
+        if (count)
+            count[c] = r[2];
+        if (misses)
+            misses[c] = r[3];
+        if (pending)
+            pending[c] = r[4];
+        if (next)
+            next[c] = r[6] | (static_cast<uint64_t>(r[7]) << 32);
+        if (seen)
+            seen[c] = r[8] | (static_cast<uint64_t>(r[9]) << 32);
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_state_bytes(const sdsp_hip_fsync_plan *p, uint64_t *bytes)
+{
+    if (!p || !bytes)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *bytes = p->state_bytes;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_set_variant(sdsp_hip_fsync_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_launches(const sdsp_hip_fsync_plan *p, uint64_t channels, uint64_t nbits, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    *launches = channels && nbits ? sdsp_hip::fsync_launches(p->variant) : 0;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_fsync_plan_get_info(const sdsp_hip_fsync_plan *p, sdsp_hip_fsync_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->marker = p->marker;
+    info->marker_bits = p->M;
+    info->payload_bytes = p->P;
+    info->period = p->L;
+    info->tol = p->tol;
+    info->verify = p->V;
+    info->flywheel = p->F;
+    info->ring_words = p->HW;
+    info->row_words = p->RW;
+    info->has_pn = p->pn ? 1 : 0;
+    info->max_channels = p->max_channels;
+    info->max_bits = p->max_bits;
+    info->max_frames = p->max_frames;
+    info->state_bytes = p->state_bytes;
+    info->workspace_bytes = p->ws_bytes;
+    info->polarity = p->polarity;
+    info->in_kind = p->in_kind;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, sdsp_hip::fsync_kernel_for(p->variant), sizeof(info->kernel) - 1);
     return SDSP_HIP_OK;
 }
 }

@@ -574,6 +574,29 @@ struct rs_shape {
 };
 rs_shape rs_shape_for(uint32_t n, uint32_t interleave, int variant);
 const char *rs_kernel_for(int variant);
+// frame synchroniser banks (fsync.hip): the launches of one call over compact rows; the kernels take it as it is
+struct fsync_args {
+    const void *in; // BYTES: channels x nbits bytes; PACKED: channels x nbits / 32 words
+    uint8_t *out;   // nullable: channels x maxf x P
+    uint32_t *counts;
+    uint64_t *pos;  // nullable
+    uint32_t *info; // nullable
+    uint32_t *state; // the plan's state: max_channels records of 16 words,
+    uint32_t *ring;  // then max_channels x HW words of the stream's last bits
+    uint32_t *work, *hitn, *hiti; // variant 0's workspace: channels x RW words each: the working row and a hit word per polarity,
+    uint64_t *ws_seen;            // the bits seen in front of the call,
+    uint64_t *rec_pos;            // and the call's frame records, channels x maxf
+    uint32_t *rec_info, *rec_cnt;
+    const uint32_t *pnw; // nullable: the pn sequence as ceil(P / 4) words, zero behind byte P
+    uint64_t channels, nbits, maxf;
+    uint32_t M, P, L, tol, V, F, either, packed, HW, RW;
+    uint32_t mrev_lo, mrev_hi; // the marker with its first bit lowest
+};
+int launch_fsync(const fsync_args &a, int variant, void *stream);
+uint32_t fsync_ring_words(uint32_t M, uint32_t P);                  // HW = ceil((L + M) / 32) + 1
+uint64_t fsync_row_words(uint32_t M, uint32_t P, uint64_t nbits);   // RW: ring, the call's words, two zero words; even
+uint64_t fsync_launches(int variant);
+const char *fsync_kernel_for(int variant);
 // STFT banks (stft.hip): the launches of one slice around the plan's real-input transform
 enum { STFT_FRAME = 0, STFT_EMIT = 1 };
 struct stft_args {
