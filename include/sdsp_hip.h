@@ -2411,6 +2411,107 @@ typedef struct {
 } sdsp_hip_fsync_plan_info;
 int sdsp_hip_fsync_plan_get_info(const sdsp_hip_fsync_plan *plan, sdsp_hip_fsync_plan_info *info);
 
+/*
+ * ---- LDPC decoder banks for quasi-cyclic codes, layered min-sum (ldpc.hip) ----
+ *
+ * A block decoder for many independent codewords of one quasi-cyclic LDPC code: nothing is carried between calls.  Every operation
+ * but the F32 quantiser is on integers: both kernel variants and tests/ldpc_ref.py give the same bits, posteriors and status, with no
+ * tolerance.
+ * Code: a base matrix `base` of mb block rows x nb block columns of int16, row-major, and a lifting size Z.  Entry -1 is the zero
+ * block; entry s in [0, Z) is the Z x Z circulant with a one at (i, (i + s) mod Z), so check row r Z + i contains variable
+ * c Z + (i + s) mod Z.  n = nb Z variables, m = mb Z checks, one circulant per entry.
+ * Limits: 2 <= Z <= 512, 1 <= mb <= 64, mb < nb <= 128, n <= 16384, every row has 2 to 32 entries (a row's sign bits fit one word),
+ * every column has at least one entry.  Posteriors then fit int16: |L| <= 127 (1 + 64) = 8255.
+ * Soft values: positive favours bit 0, as in the Viterbi banks; 0 is an erasure, which is how punctured columns are fed.  I8: int8,
+ * -128 is read as -127.  F32: quantised on the way in as q = clamp(rint(fl32(x scale)), -127, 127) with the plan's float `scale`,
+ * ties to even, NaN becomes 0: the one floating-point operation.  One codeword is n compact values: the row length is the row
+ * distance.
+ * Decoding, each codeword on its own:
+ *  1. L[v] = q[v] as integers; all check-to-variable messages R start at 0.
+ *  2. One iteration visits the layers r = 0 .. mb - 1 in order; the Z checks of a layer touch different variables, so their order
+ *     cannot matter.
+ *  3. For a check, number the entries of row r as j = 0 .. d - 1 in ascending block column, v_j the variable of entry j:
+ *     T_j = L[v_j] - R_j, a_j = min(|T_j|, 127), sigma_j = (T_j < 0) (zero counts as positive), S = sigma_0 xor .. xor sigma_(d-1),
+ *     m1 = the smallest a_j, m2 = the smallest of the others, f(x) = max(((x norm + 8) >> 4) - beta, 0).  The new R_j has magnitude
+ *     f(m2) if a_j is the minimum and f(m1) otherwise (with a tie f(m1) = f(m2), so which j "is" the minimum does not matter) and
+ *     the sign S xor sigma_j, negative if set; L[v_j] = T_j + R_j(new).  There is no clamp anywhere but the 127 on a_j.
+ *  4. norm is 1 .. 16 (sixteenths: 12 is the usual 0.75, 16 is plain min-sum), beta is 0 .. 31; both are plan parameters.
+ *  5. The hard decision is h[v] = (L[v] < 0).
+ *  6. The syndrome test is "every check has even parity of h", made on the input before the first iteration and after the last
+ *     layer of every iteration.
+ *  7. With early_stop (a plan parameter) a codeword stops at the first test that passes, and its status is the number of iterations
+ *     run: 0 if the input already passes, otherwise 1 .. max_iter.  Without it max_iter iterations always run, and a codeword whose
+ *     final test passes has the status max_iter.
+ *  8. A codeword whose final test fails gets the status -1; its outputs are still written.
+ *  9. A codeword that passes may be another codeword than the one sent: that is deterministic and part of the contract.
+ * 10. max_iter is an argument of each call, 0 .. 255; 0 gives the hard decisions of the input and its syndrome.
+ * Outputs, each optional, at least one required.  bits: the first out_bits hard decisions of each codeword (1 <= out_bits <= n, a plan
+ * parameter: typically n, or (nb - mb) Z for the systematic part), as BYTES (0 / 1, out_bits per codeword) or PACKED (uint32 words,
+ * bit v in bit v mod 32 of word v / 32, ceil(out_bits / 32) words per codeword, the unused top bits zero).  post: the int16
+ * posteriors L, n per codeword.  status: int32, one per codeword.
+ * Buffers: bits, post and status must not overlap the input or each other; F32 input, int16, int32 and word outputs must be aligned
+ * to their element; the byte and int8 buffers may lie at any address.  codewords < 2^31; codewords == 0 touches nothing.
+ * Errors: mb, nb, Z, n, norm, beta, out_bits, max_iter or codewords out of range: SDSP_HIP_ERR_INVALID_SIZE; a null pointer, an
+ * unknown kind, a shift outside [-1, Z), a bad row or column degree, a scale that is not finite and positive (F32), no output at all,
+ * misalignment or overlap: SDSP_HIP_ERR_INVALID_ARG.  A refusal writes nothing.
+ */
+#define SDSP_HIP_LDPC_I8 0
+#define SDSP_HIP_LDPC_F32 1
+#define SDSP_HIP_LDPC_BYTES 0
+#define SDSP_HIP_LDPC_PACKED 1
+#define SDSP_HIP_LDPC_MAX_Z 512
+#define SDSP_HIP_LDPC_MAX_MB 64
+#define SDSP_HIP_LDPC_MAX_NB 128
+#define SDSP_HIP_LDPC_MAX_N 16384
+#define SDSP_HIP_LDPC_MAX_ROW_DEGREE 32
+#define SDSP_HIP_LDPC_MAX_ITER 255
+typedef struct sdsp_hip_ldpc_plan sdsp_hip_ldpc_plan;
+/* host helper for codewords [data | parity] with k = n - m: the m x ceil(k / 32) HOST words of P with parity = P data over GF(2), bit
+ * j of row i in bit j mod 32 of word j / 32, by Gaussian elimination on bit words.  Errors: the code's as above; a null pointer:
+ * SDSP_HIP_ERR_INVALID_ARG; the last m columns of H singular: SDSP_HIP_ERR_UNSUPPORTED.  A refusal writes nothing. */
+int sdsp_hip_ldpc_parity_matrix(const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, uint32_t *P);
+/* host helper: the systematic encoder of the same codes.  data: `codewords` rows of k HOST bytes (non-zero counts as 1); out:
+ * `codewords` rows of n HOST 0 / 1 bytes, the data then the parity.  data and out must not overlap; codewords < 2^31. */
+int sdsp_hip_ldpc_encode(const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, const uint8_t *data, uint64_t codewords, uint8_t *out);
+/* base: mb x nb HOST values.  scale is read by F32 plans only.  The argument checks come before the device is touched; the plan
+ * starts in variant 0.  Errors as above; no device: SDSP_HIP_ERR_NO_DEVICE; no memory for the table: SDSP_HIP_ERR_NOMEM. */
+int sdsp_hip_ldpc_plan_create(sdsp_hip_ldpc_plan **plan, const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, uint32_t norm,
+                              uint32_t beta, int early_stop, int in_kind, float scale, int out_kind, uint32_t out_bits, int device);
+int sdsp_hip_ldpc_plan_destroy(sdsp_hip_ldpc_plan *plan);
+/* llr, bits (nullable), post (nullable), status (nullable): DEVICE pointers.  Asynchronous on `stream`, plain launches only
+ * (sdsp_hip_ldpc_plan_launches of them), allocates nothing (stream-capturable); one call per plan in flight in variant 1, whose
+ * workspace belongs to the plan. */
+int sdsp_hip_ldpc_process(sdsp_hip_ldpc_plan *plan, const void *llr, void *bits, int16_t *post, int32_t *status, uint64_t codewords,
+                          uint32_t max_iter, void *stream);
+/* same with HOST pointers (synchronous) */
+int sdsp_hip_ldpc_process_host(sdsp_hip_ldpc_plan *plan, const void *host_llr, void *host_bits, int16_t *host_post, int32_t *host_status,
+                               uint64_t codewords, uint32_t max_iter);
+/* kernel variants (identical bits, posteriors and status): 0 = sdsp_ldpc_wave_kernel (lanes are the checks of a layer; a wave holds
+ * floor(64 / Z) codewords side by side where Z <= 32, one where Z <= 64, and walks a layer in ceil(Z / 64) pieces above that; L as
+ * int16 and a record of 8 bytes per check in LDS, no barrier); 1 = sdsp_ldpc_plain_kernel (a thread per codeword, L and one int8
+ * message per edge in a plan-owned global workspace of at most 256 MiB, which set_variant(1) allocates; a call goes out in pieces
+ * of the codewords that fit it).  Errors: any other value: SDSP_HIP_ERR_INVALID_ARG; no memory: SDSP_HIP_ERR_NOMEM. */
+int sdsp_hip_ldpc_plan_set_variant(sdsp_hip_ldpc_plan *plan, int variant);
+/* kernel launches of one process call: variant 0: 1; variant 1: ceil(codewords / piece); 0 for codewords == 0 */
+int sdsp_hip_ldpc_plan_launches(const sdsp_hip_ldpc_plan *plan, uint64_t codewords, uint64_t *launches);
+typedef struct {
+    uint32_t mb, nb, z;
+    uint32_t n, m;            /* nb z, mb z */
+    uint32_t edges;           /* per codeword: entries x z */
+    uint32_t max_row_degree;
+    uint32_t norm, beta, out_bits;
+    uint32_t group;           /* variant 0: codewords per wave; variant 1: 1 (per thread) */
+    uint32_t threads;         /* per workgroup */
+    uint32_t lds_bytes;       /* LDS of one workgroup */
+    uint32_t codewords_per_cu; /* variant 0: codewords a compute unit holds at a time by its LDS and wave slots; variant 1: 0 */
+    uint64_t piece;           /* variant 1: codewords per launch */
+    uint64_t workspace_bytes; /* variant 1 */
+    float scale;
+    int early_stop, in_kind, out_kind, device, variant;
+    char kernel[64];          /* the kernel the plan's variant runs */
+} sdsp_hip_ldpc_plan_info;
+int sdsp_hip_ldpc_plan_get_info(const sdsp_hip_ldpc_plan *plan, sdsp_hip_ldpc_plan_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from ._lib import (F32, F64, F32_F64STATE, FORWARD, REVERSE, IIR_GENERIC, IIR_LP
                    VITERBI_I8, VITERBI_F32, VITERBI_BYTES, VITERBI_PACKED,
                    RS_FULL, RS_DATA,
                    FSYNC_BYTES, FSYNC_PACKED, FSYNC_NORMAL, FSYNC_EITHER, FSYNC_SEARCH, FSYNC_VERIFY, FSYNC_LOCK,
+                   LDPC_I8, LDPC_F32, LDPC_BYTES, LDPC_PACKED,
                    SdspHipError, load)
 from .fft import (FftPlan, RfftPlan, fft_radix2, fft_radix4, forward_fft, reverse_fft, log2, log4, isPowerOf2,
                   isPowerOf4, digit_reverse, calc_swap_lookup, calc_twiddles, calc_wCoeffs)
@@ -47,6 +48,7 @@ from .timing import timing_bank, timing_step, timing_max_out, timing_gains, timi
 from .viterbi import viterbi_bank, viterbi_delay, viterbi_decode, conv_encode
 from .rs import rs_decoder, rs_decode, rs_encode, rs_generator
 from .fsync import frame_sync_bank, ccsds_pn, attach_sync, fsync_max_frames, CCSDS_ASM
+from .ldpc import ldpc_decoder, ldpc_decode, ldpc_encode, ldpc_parity_matrix
 
 
 def set_launch_piece_bytes(nbytes: int) -> None:

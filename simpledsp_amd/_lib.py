@@ -286,7 +286,20 @@ class FsyncPlanInfo(C.Structure):
     ]
 
 
+class LdpcPlanInfo(C.Structure):
+    _fields_ = [
+        ("mb", C.c_uint32), ("nb", C.c_uint32), ("z", C.c_uint32), ("n", C.c_uint32), ("m", C.c_uint32), ("edges", C.c_uint32),
+        ("max_row_degree", C.c_uint32), ("norm", C.c_uint32), ("beta", C.c_uint32), ("out_bits", C.c_uint32), ("group", C.c_uint32),
+        ("threads", C.c_uint32), ("lds_bytes", C.c_uint32), ("codewords_per_cu", C.c_uint32), ("piece", C.c_uint64),
+        ("workspace_bytes", C.c_uint64), ("scale", C.c_float), ("early_stop", C.c_int), ("in_kind", C.c_int), ("out_kind", C.c_int),
+        ("device", C.c_int), ("variant", C.c_int), ("kernel", C.c_char * 64),
+    ]
+
+
 TIMING_GARDNER, TIMING_ZC_QPSK, TIMING_ZC_BPSK = 0, 1, 2
+LDPC_I8, LDPC_F32 = 0, 1
+LDPC_BYTES, LDPC_PACKED = 0, 1
+LDPC_MAX_Z, LDPC_MAX_MB, LDPC_MAX_NB, LDPC_MAX_N, LDPC_MAX_ROW_DEGREE, LDPC_MAX_ITER = 512, 64, 128, 16384, 32, 255
 FSYNC_BYTES, FSYNC_PACKED = 0, 1
 FSYNC_NORMAL, FSYNC_EITHER = 0, 1
 FSYNC_SEARCH, FSYNC_VERIFY, FSYNC_LOCK = 0, 1, 2
@@ -633,6 +646,15 @@ SIGNATURES = {
     "sdsp_hip_fsync_plan_set_variant": (_i, [_vp, _i]),
     "sdsp_hip_fsync_plan_launches": (_i, [_vp, _u64, _u64, C.POINTER(_u64)]),
     "sdsp_hip_fsync_plan_get_info": (_i, [_vp, C.POINTER(FsyncPlanInfo)]),
+    "sdsp_hip_ldpc_parity_matrix": (_i, [_vp, _u32, _u32, _u32, _vp]),
+    "sdsp_hip_ldpc_encode": (_i, [_vp, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "sdsp_hip_ldpc_plan_create": (_i, [_pp, _vp, _u32, _u32, _u32, _u32, _u32, _i, _i, C.c_float, _i, _u32, _i]),
+    "sdsp_hip_ldpc_plan_destroy": (_i, [_vp]),
+    "sdsp_hip_ldpc_process": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp]),
+    "sdsp_hip_ldpc_process_host": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u32]),
+    "sdsp_hip_ldpc_plan_set_variant": (_i, [_vp, _i]),
+    "sdsp_hip_ldpc_plan_launches": (_i, [_vp, _u64, C.POINTER(_u64)]),
+    "sdsp_hip_ldpc_plan_get_info": (_i, [_vp, C.POINTER(LdpcPlanInfo)]),
 }
 
 _lib = None

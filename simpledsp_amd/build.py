@@ -64,6 +64,7 @@ SOURCES = {
     # into registers they cost 256 VGPRs, 114 AGPRs and 1817 spilled SGPRs, one wave per SIMD (profiles/rs_kernel_regs.txt)
     "rs.hip": ["-mllvm", "-disable-promote-alloca-to-vector"],
     "fsync.hip": [],  # bits, shifts and popcounts: no floating point at all
+    "ldpc.hip": [],  # integers throughout; the one float step is the product of the F32 quantiser, as in viterbi.hip
     "stft.hip": ["-ffp-contract=off"],  # power = re re + im im: two products and a sum, never an FMA
     "istft.hip": ["-ffp-contract=off"],  # overlap-add: fl(g z) then one addition per frame, never an FMA
     "welch.hip": ["-ffp-contract=off"],  # detrend, window and power: every product and sum rounded on its own, never an FMA

@@ -574,6 +574,15 @@ struct sdsp_hip_rs_plan {
     void *table = nullptr; // device: exp[512], log[256]
 };
 
+struct sdsp_hip_ldpc_plan {
+    uint32_t mb = 0, nb = 0, z = 0, n = 0, m = 0, entries = 0, entries_at = 0, max_degree = 0;
+    uint32_t norm = 0, beta = 0, out_bits = 0;
+    float scale = 1.0f;
+    int early_stop = 0, in_kind = 0, out_kind = 0, device = 0, variant = 0;
+    void *table = nullptr; // device uint32: rowptr[0 .. mb], padding to an even count, entries x (first variable of the column, shift)
+    void *ws = nullptr;    // device: variant 1's L and R of one piece; made by set_variant(1)
+};
+
 struct sdsp_hip_timing_plan {
     uint64_t channels = 0, step0 = 0;
     uint32_t phases = 1, taps = 0;
@@ -8350,6 +8359,375 @@ int sdsp_hip_fsync_plan_get_info(const sdsp_hip_fsync_plan *p, sdsp_hip_fsync_pl
     info->device = p->device;
     info->variant = p->variant;
     std::strncpy(info->kernel, sdsp_hip::fsync_kernel_for(p->variant), sizeof(info->kernel) - 1);
+    return SDSP_HIP_OK;
+}
+// ------------------------------------------------------------------ LDPC decoder banks (ldpc.hip)
+
+namespace
+{
+// the code of a plan or of a host helper, without a device; counts (nullable): the entries of H's base and the largest row degree
+int ldpc_check_code(const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, uint32_t *entries, uint32_t *max_degree)
+{
+    if (z < 2 || z > SDSP_HIP_LDPC_MAX_Z)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "z must be in [2, 512]");
+    if (mb < 1 || mb > SDSP_HIP_LDPC_MAX_MB)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "mb must be in [1, 64]");
+    if (nb <= mb || nb > SDSP_HIP_LDPC_MAX_NB)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "nb must be in (mb, 128]");
+    if (nb * z > SDSP_HIP_LDPC_MAX_N)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "n = nb z must be at most 16384");
+    if (!base)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "base is null");
+    uint32_t in_column[SDSP_HIP_LDPC_MAX_NB] = {}, total = 0, deepest = 0;
+    for (uint32_t r = 0; r < mb; r++) {
+        uint32_t d = 0;
+        for (uint32_t c = 0; c < nb; c++) {
+            const int s = base[r * nb + c];
+            if (s < -1 || s >= static_cast<int>(z))
+                return fail(SDSP_HIP_ERR_INVALID_ARG, "a shift must be -1 or in [0, z)");
+            if (s >= 0) {
+                d++;
+                in_column[c]++;
+            }
+        }
+        if (d < 2 || d > SDSP_HIP_LDPC_MAX_ROW_DEGREE)
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "every row must have 2 to 32 entries");
+        total += d;
+        deepest = std::max(deepest, d);
+    }
+    for (uint32_t c = 0; c < nb; c++)
+        if (!in_column[c])
+            return fail(SDSP_HIP_ERR_INVALID_ARG, "every column must have at least one entry");
+    if (entries)
+        *entries = total;
+    if (max_degree)
+        *max_degree = deepest;
+    return SDSP_HIP_OK;
+}
+
+// P of a checked code: m rows of ceil(k / 32) words.  The rows of H as [parity part | data part] bit words, the parity part reduced
+// to the identity by Gauss-Jordan elimination: what is left of the data part is P.
+int ldpc_parity_rows(const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, std::vector<uint32_t> &P)
+{
+    const uint32_t n = nb * z, m = mb * z, k = n - m, wp = (m + 31) / 32, wk = (k + 31) / 32, W = wp + wk;
+    std::vector<uint32_t> rows(static_cast<size_t>(m) * W, 0);
+    for (uint32_t r = 0; r < mb; r++)
+        for (uint32_t c = 0; c < nb; c++) {
+            const int s = base[r * nb + c];
+            if (s < 0)
+                continue;
+            for (uint32_t i = 0; i < z; i++) {
+                const uint32_t v = c * z + (i + static_cast<uint32_t>(s)) % z;
+                uint32_t *row = rows.data() + static_cast<size_t>(r * z + i) * W;
+                if (v >= k)
+                    row[(v - k) / 32] ^= 1u << ((v - k) % 32);
+                else
+                    row[wp + v / 32] ^= 1u << (v % 32);
+            }
+        }
+    for (uint32_t q = 0; q < m; q++) {
+        const uint32_t w = q / 32, bit = 1u << (q % 32);
+        uint32_t piv = q;
+        while (piv < m && !(rows[static_cast<size_t>(piv) * W + w] & bit))
+            piv++;
+        if (piv == m)
+            return fail(SDSP_HIP_ERR_UNSUPPORTED, "the last m columns of H are singular: the code has no [data | parity] encoder");
+        uint32_t *pr = rows.data() + static_cast<size_t>(q) * W;
+        if (piv != q)
+            std::swap_ranges(pr, pr + W, rows.data() + static_cast<size_t>(piv) * W);
+        for (uint32_t i = 0; i < m; i++) {
+            uint32_t *row = rows.data() + static_cast<size_t>(i) * W;
+            if (i != q && (row[w] & bit))
+                for (uint32_t x = w; x < W; x++) // the pivot row is zero in front of word w
+                    row[x] ^= pr[x];
+        }
+    }
+    P.assign(static_cast<size_t>(m) * wk, 0);
+    for (uint32_t i = 0; i < m; i++)
+        std::memcpy(P.data() + static_cast<size_t>(i) * wk, rows.data() + static_cast<size_t>(i) * W + wp, wk * 4);
+    return SDSP_HIP_OK;
+}
+
+uint64_t ldpc_bits_row(const sdsp_hip_ldpc_plan *p) { return p->out_kind == SDSP_HIP_LDPC_PACKED ? (p->out_bits + 31) / 32 * 4ull : p->out_bits; }
+uint64_t ldpc_in_row(const sdsp_hip_ldpc_plan *p) { return static_cast<uint64_t>(p->n) * (p->in_kind == SDSP_HIP_LDPC_F32 ? 4 : 1); }
+
+// argument checks shared by process and process_host
+int ldpc_check(const sdsp_hip_ldpc_plan *p, const void *llr, const void *bits, const int16_t *post, const int32_t *status, uint64_t codewords,
+               uint32_t max_iter)
+{
+    if (!p)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan is null");
+    if (codewords >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "codewords must be below 2^31");
+    if (max_iter > SDSP_HIP_LDPC_MAX_ITER)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "max_iter must be in [0, 255]");
+    if (codewords == 0)
+        return SDSP_HIP_OK;
+    if (!llr)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "llr must not be null");
+    if (!bits && !post && !status)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "at least one of bits, post and status is required");
+    if ((p->in_kind == SDSP_HIP_LDPC_F32 && misaligned(llr, 4)) || (p->out_kind == SDSP_HIP_LDPC_PACKED && misaligned(bits, 4)) ||
+        misaligned(post, 2) || misaligned(status, 4))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "llr, bits, post and status must be aligned to their element size");
+    const uint64_t nl = codewords * ldpc_in_row(p), nb = codewords * ldpc_bits_row(p), np = codewords * p->n * 2, ns = codewords * 4;
+    if (ranges_overlap(llr, nl, bits, nb) || ranges_overlap(llr, nl, post, np) || ranges_overlap(llr, nl, status, ns) ||
+        ranges_overlap(bits, nb, post, np) || ranges_overlap(bits, nb, status, ns) || ranges_overlap(post, np, status, ns))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "llr, bits, post and status must not overlap");
+    return SDSP_HIP_OK;
+}
+
+ldpc_args ldpc_args_of(const sdsp_hip_ldpc_plan *p, const void *llr, void *bits, int16_t *post, int32_t *status, uint64_t codewords,
+                       uint32_t max_iter)
+{
+    ldpc_args a{};
+    a.llr = llr;
+    a.bits = bits;
+    a.post = post;
+    a.status = status;
+    a.table = p->table;
+    a.table_entries_at = p->entries_at;
+    a.workspace = p->ws;
+    a.codewords = codewords;
+    a.mb = p->mb;
+    a.nb = p->nb;
+    a.z = p->z;
+    a.edges = p->entries * p->z;
+    a.norm = p->norm;
+    a.beta = p->beta;
+    a.max_iter = max_iter;
+    a.out_bits = p->out_bits;
+    a.early_stop = p->early_stop != 0;
+    a.packed = p->out_kind == SDSP_HIP_LDPC_PACKED;
+    a.f32 = p->in_kind == SDSP_HIP_LDPC_F32;
+    a.scale = p->scale;
+    return a;
+}
+
+ldpc_shape ldpc_shape_of(const sdsp_hip_ldpc_plan *p, int variant) { return ldpc_shape_for(p->mb, p->nb, p->z, p->entries * p->z, variant); }
+} // namespace
+
+int sdsp_hip_ldpc_parity_matrix(const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, uint32_t *P)
+{
+    if (int rc = ldpc_check_code(base, mb, nb, z, nullptr, nullptr))
+        return rc;
+    if (!P)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "P is null");
+    std::vector<uint32_t> rows;
+    if (int rc = ldpc_parity_rows(base, mb, nb, z, rows))
+        return rc;
+    std::memcpy(P, rows.data(), rows.size() * 4);
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_ldpc_encode(const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, const uint8_t *data, uint64_t codewords, uint8_t *out)
+{
+    if (int rc = ldpc_check_code(base, mb, nb, z, nullptr, nullptr))
+        return rc;
+    if (codewords >= (1ull << 31))
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "codewords must be below 2^31");
+    if (codewords == 0)
+        return SDSP_HIP_OK;
+    if (!data || !out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "data and out must not be null");
+    const uint32_t n = nb * z, m = mb * z, k = n - m, wk = (k + 31) / 32;
+    if (ranges_overlap(data, codewords * k, out, codewords * n))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "data and out must not overlap");
+    std::vector<uint32_t> P;
+    if (int rc = ldpc_parity_rows(base, mb, nb, z, P))
+        return rc;
+    std::vector<uint32_t> word(wk);
+    for (uint64_t f = 0; f < codewords; f++) {
+        const uint8_t *d = data + f * k;
+        uint8_t *o = out + f * n;
+        std::fill(word.begin(), word.end(), 0u);
+        for (uint32_t j = 0; j < k; j++) {
+            o[j] = d[j] != 0;
+            word[j / 32] |= static_cast<uint32_t>(d[j] != 0) << (j % 32);
+        }
+        for (uint32_t i = 0; i < m; i++) {
+            uint32_t acc = 0;
+            for (uint32_t w = 0; w < wk; w++)
+                acc ^= P[static_cast<size_t>(i) * wk + w] & word[w];
+            o[k + i] = static_cast<uint8_t>(__builtin_popcount(acc) & 1);
+        }
+    }
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_ldpc_plan_create(sdsp_hip_ldpc_plan **out, const int16_t *base, uint32_t mb, uint32_t nb, uint32_t z, uint32_t norm,
+                              uint32_t beta, int early_stop, int in_kind, float scale, int out_kind, uint32_t out_bits, int device)
+{
+    if (!out)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "plan out-pointer is null");
+    *out = nullptr;
+    uint32_t entries = 0, max_degree = 0;
+    if (int rc = ldpc_check_code(base, mb, nb, z, &entries, &max_degree))
+        return rc;
+    if (norm < 1 || norm > 16)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "norm must be in [1, 16]");
+    if (beta > 31)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "beta must be in [0, 31]");
+    if (out_bits < 1 || out_bits > nb * z)
+        return fail(SDSP_HIP_ERR_INVALID_SIZE, "out_bits must be in [1, n]");
+    if (in_kind != SDSP_HIP_LDPC_I8 && in_kind != SDSP_HIP_LDPC_F32)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "in_kind must be SDSP_HIP_LDPC_I8 or SDSP_HIP_LDPC_F32");
+    if (out_kind != SDSP_HIP_LDPC_BYTES && out_kind != SDSP_HIP_LDPC_PACKED)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "out_kind must be SDSP_HIP_LDPC_BYTES or SDSP_HIP_LDPC_PACKED");
+    if (in_kind == SDSP_HIP_LDPC_F32 && !(std::isfinite(scale) && scale > 0.0f))
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "scale must be finite and positive");
+    if (int rc = use_device(device))
+        return rc;
+    auto *p = new sdsp_hip_ldpc_plan();
+    p->mb = mb;
+    p->nb = nb;
+    p->z = z;
+    p->n = nb * z;
+    p->m = mb * z;
+    p->entries = entries;
+    p->entries_at = (mb + 2) & ~1u;
+    p->max_degree = max_degree;
+    p->norm = norm;
+    p->beta = beta;
+    p->out_bits = out_bits;
+    p->scale = in_kind == SDSP_HIP_LDPC_F32 ? scale : 1.0f;
+    p->early_stop = early_stop ? 1 : 0;
+    p->in_kind = in_kind;
+    p->out_kind = out_kind;
+    p->device = device;
+    p->variant = 0;
+    std::vector<uint32_t> t(p->entries_at + 2 * static_cast<size_t>(entries), 0);
+    uint32_t e = 0;
+    for (uint32_t r = 0; r < mb; r++) {
+        t[r] = e;
+        for (uint32_t c = 0; c < nb; c++)
+            if (base[r * nb + c] >= 0) {
+                t[p->entries_at + 2 * e] = c * z;
+                t[p->entries_at + 2 * e + 1] = static_cast<uint32_t>(base[r * nb + c]);
+                e++;
+            }
+    }
+    t[mb] = e;
+    hipError_t err = hipMalloc(&p->table, t.size() * 4);
+    if (err == hipSuccess)
+        err = hipMemcpy(p->table, t.data(), t.size() * 4, hipMemcpyHostToDevice);
+    int rc = err == hipSuccess ? SDSP_HIP_OK : plan_fail(err, "ldpc");
+    if (!rc)
+        rc = ldpc_prepare(in_kind, ldpc_shape_of(p, 0).lds_bytes);
+    if (rc) {
+        sdsp_hip_ldpc_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_ldpc_plan_destroy(sdsp_hip_ldpc_plan *p)
+{
+    if (!p)
+        return SDSP_HIP_OK;
+    if (use_device(p->device) == SDSP_HIP_OK) {
+        (void)hipFree(p->table);
+        (void)hipFree(p->ws);
+    }
+    delete p;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_ldpc_process(sdsp_hip_ldpc_plan *p, const void *llr, void *bits, int16_t *post, int32_t *status, uint64_t codewords,
+                          uint32_t max_iter, void *stream)
+{
+    if (int rc = ldpc_check(p, llr, bits, post, status, codewords, max_iter))
+        return rc;
+    if (codewords == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    return launch_ldpc(ldpc_args_of(p, llr, bits, post, status, codewords, max_iter), p->variant, stream);
+}
+
+int sdsp_hip_ldpc_process_host(sdsp_hip_ldpc_plan *p, const void *host_llr, void *host_bits, int16_t *host_post, int32_t *host_status,
+                               uint64_t codewords, uint32_t max_iter)
+{
+    if (int rc = ldpc_check(p, host_llr, host_bits, host_post, host_status, codewords, max_iter))
+        return rc;
+    if (codewords == 0)
+        return SDSP_HIP_OK;
+    if (int rc = use_device(p->device))
+        return rc;
+    const size_t cw = static_cast<size_t>(codewords);
+    host_stage st("ldpc", { { host_llr, cw * ldpc_in_row(p), false },
+                            { host_bits, cw * ldpc_bits_row(p), true },
+                            { host_post, cw * p->n * 2, true },
+                            { host_status, cw * 4, true } });
+    int rc = st.in();
+    if (!rc)
+        rc = launch_ldpc(ldpc_args_of(p, st.dev[0], st.dev[1], static_cast<int16_t *>(st.dev[2]), static_cast<int32_t *>(st.dev[3]), codewords,
+                                      max_iter),
+                         p->variant, nullptr);
+    if (!rc) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = hip_fail(e, "ldpc process_host");
+    }
+    return st.out(rc);
+}
+
+int sdsp_hip_ldpc_plan_set_variant(sdsp_hip_ldpc_plan *p, int variant)
+{
+    if (!p || variant < 0 || variant > 1)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "variant must be 0 or 1");
+    if (variant == 1 && !p->ws) {
+        if (int rc = use_device(p->device))
+            return rc;
+        const hipError_t e = hipMalloc(&p->ws, ldpc_shape_of(p, 1).workspace_bytes);
+        if (e != hipSuccess) {
+            p->ws = nullptr;
+            return plan_fail(e, "ldpc");
+        }
+    }
+    p->variant = variant;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_ldpc_plan_launches(const sdsp_hip_ldpc_plan *p, uint64_t codewords, uint64_t *launches)
+{
+    if (!p || !launches)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    const uint64_t piece = ldpc_shape_of(p, p->variant).piece;
+    *launches = (codewords + piece - 1) / piece;
+    return SDSP_HIP_OK;
+}
+
+int sdsp_hip_ldpc_plan_get_info(const sdsp_hip_ldpc_plan *p, sdsp_hip_ldpc_plan_info *info)
+{
+    if (!p || !info)
+        return fail(SDSP_HIP_ERR_INVALID_ARG, "null argument");
+    std::memset(info, 0, sizeof(*info));
+    const ldpc_shape s = ldpc_shape_of(p, p->variant);
+    info->mb = p->mb;
+    info->nb = p->nb;
+    info->z = p->z;
+    info->n = p->n;
+    info->m = p->m;
+    info->edges = p->entries * p->z;
+    info->max_row_degree = p->max_degree;
+    info->norm = p->norm;
+    info->beta = p->beta;
+    info->out_bits = p->out_bits;
+    info->group = s.group;
+    info->threads = s.threads;
+    info->lds_bytes = s.lds_bytes;
+    info->codewords_per_cu = s.per_cu;
+    info->piece = p->variant == 1 ? s.piece : 0;
+    info->workspace_bytes = s.workspace_bytes;
+    info->scale = p->scale;
+    info->early_stop = p->early_stop;
+    info->in_kind = p->in_kind;
+    info->out_kind = p->out_kind;
+    info->device = p->device;
+    info->variant = p->variant;
+    std::strncpy(info->kernel, ldpc_kernel_for(p->variant), sizeof(info->kernel) - 1);
     return SDSP_HIP_OK;
 }
 }

@@ -574,6 +574,33 @@ struct rs_shape {
 };
 rs_shape rs_shape_for(uint32_t n, uint32_t interleave, int variant);
 const char *rs_kernel_for(int variant);
+// LDPC decoder banks (ldpc.hip): the launches of one call over compact codewords
+struct ldpc_args {
+    const void *llr;
+    void *bits;        // nullable
+    int16_t *post;     // nullable
+    int32_t *status;   // nullable
+    const void *table; // device uint32: rowptr[0 .. mb], padding to an even count, then per entry (first variable of the column, shift)
+    uint32_t table_entries_at; // where the entries start, in uint32
+    void *workspace;   // variant 1: L (int16) and R (int8) of one piece, codeword-minor
+    uint64_t codewords;
+    uint32_t mb, nb, z, edges; // edges per codeword
+    uint32_t norm, beta, max_iter, out_bits;
+    bool early_stop, packed, f32;
+    float scale;
+};
+int launch_ldpc(const ldpc_args &a, int variant, void *stream);
+struct ldpc_shape {
+    uint32_t threads, waves, lds_bytes;
+    uint32_t group;      // wave kernel: codewords per wave
+    uint32_t wave_bytes; // wave kernel: LDS of one wave
+    uint32_t per_cu;     // wave kernel: codewords a CU holds at a time
+    uint64_t piece;      // codewords of one launch
+    uint64_t workspace_bytes; // variant 1
+};
+ldpc_shape ldpc_shape_for(uint32_t mb, uint32_t nb, uint32_t z, uint32_t edges, int variant);
+int ldpc_prepare(int in_kind, uint32_t lds_bytes);
+const char *ldpc_kernel_for(int variant);
 // frame synchroniser banks (fsync.hip): the launches of one call over compact rows; the kernels take it as it is
 struct fsync_args {
     const void *in; // BYTES: channels x nbits bytes; PACKED: channels x nbits / 32 words
